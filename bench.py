@@ -14,8 +14,11 @@ N > 1: one process per GPU; the sweep is sharded by point range, the map is repl
 normal equations each iteration (RCCL all-reduce by default, `--transport peer`: direct stores over xGMI) -- strong scaling of one sweep,
 the design north_star names.  `--mode replay` runs N independent sweeps instead (config 5).  torch.distributed is control plane only (gloo).
 
-Everything else the line carries is measured BEHIND the timed region by tools/benchlib (the file the driver hashes holds the loop that
-produces `value`; the legs live beside it):
+A plain run sets up, warms up, times the K steps and prints the line: the contract keys and what the timed region itself yields (ESIKF
+iterations and launches per solve, arm statistics).  `--dump-outputs DIR` writes what the last timed step computed (the solved state, the
+filter's state and covariance, iterations, residuals) as DIR/<name>.npy; the inputs depend on the arguments alone.
+With `--full`, everything else the line carries is measured BEHIND the timed region by tools/benchlib (the file the driver hashes holds the
+loop that produces `value`; the legs live beside it):
   roofline      aux_legs.kernel_time_leg: the same loop again with HIP events on the context's stream (>= 200 launch durations) -> algorithmic
                 bytes / duration vs the HBM roofline; counter-measured traffic and the instruction-issue roofline from profiles/r06_*
   stream        >= 1 000 solves with a stamp per solve; the unfiltered-seed, iteration-weighted rate
@@ -68,7 +71,21 @@ def parse_args():
     ap.add_argument("--sharded-config", default="C4", choices=sorted(synth.CONFIGS), help="N > 1: the configuration of the sharded-config leg")
     ap.add_argument("--no-other-transport", action="store_true", help="N > 1: do not run the stream on the transport the timed region did not use")
     ap.add_argument("--force-comm", action="store_true", help="attach an RCCL communicator even at world size 1")
+    ap.add_argument("--full", action="store_true", help="also run every leg behind the timed region (roofline, long stream, A/B and PCIe forms, CPU "
+                                                        "baselines and parity, every configuration; N > 1: the other transport, the sharded configuration, "
+                                                        "the replicas) and write the detail file.  The --no-* options above trim these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+def dump_outputs(path, r, lio):
+    """the arrays a caller of the timed path receives from its last step: srl_lio_stream_step's state_io, iteration and residual counts, and
+    the filter's state and covariance after the solve (lioOptimization::updateIEKF leaves the posterior in the eskfEstimator)"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"state": r["state"], "eskf_state": lio.eskf_get_state(), "eskf_cov": lio.eskf_get_cov(),
+              "iterations": r["iters"], "num_residuals": r["num_residuals"]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def main():
@@ -108,25 +125,12 @@ def main():
     if comm_state.get("transport_used") == "peer":
         rep, failed = lio.ctx.peer_stats()
         comm_state.update(passes_repeated_for_a_late_rank=rep, session_failed=failed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, lio)       # (before any leg behind the region solves on this context again)
 
-    # ---------------- behind the region: the kernel's duration (roofline), the long stamped stream, A/B and PCIe forms
-    tim = aux_legs.kernel_time_leg(run, 8 if args.no_aux_legs else 200)        # (profiling runs keep the trace to the timed form: --no-aux-legs)
-    stream_long, stream_states = (None, {}) if args.no_aux_legs else aux_legs.long_stream_leg(run, max(1000, args.steps))
-    unfiltered = None if (args.no_aux_legs or sharded) else aux_legs.unfiltered_stream_leg(run)
-    extra, launch_ab = {}, None
-    if world == 1 and not args.no_aux_legs and not args.no_armed:
-        launch_ab, extra["tim_unarmed"] = aux_legs.launch_ab_leg(run, stream_states, elapsed * 1e6 / max(iters_timed, 1))
-    other_transport = multi.other_transport_leg(run, args.steps) if (sharded and world > 1 and not args.no_aux_legs and not args.no_other_transport) else None
-    r0, res_legs = aux_legs.resident_legs(run)
-    extra.update(res_legs)
-    rates, medians, stalls, n_pcie = aux_legs.pcie_legs(run, stream_long)
-    nb = 2 if args.frame_id < 20 else 1
-    roof = aux_legs.roofline_block(run, tim, iters_timed, nb, extra)
-    replicas = multi.replicas_leg(run, args.steps) if sharded else None
-
+    # ---------------- the headline: the contract keys and what the timed region itself yields
     S, stream = run.S, run.stream
-    tf = extra["tim_full"]
-    fcalls = max(tf.calls, 1)
+    nb = 2 if args.frame_id < 20 else 1
     out = {
         "metric": "sweeps/s (full ESIKF solve of a 64k-pt Livox sweep vs 1M-pt voxel map)",
         "value": value, "unit": "sweeps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -139,41 +143,63 @@ def main():
                                f"{[x['seed'] for x in stream[0]['skipped']]}; the unfiltered rate: `stream.unfiltered`)",
                    "parallelism": ("point-range shards x%d + %s of the 6x6 normal equations" % (world, "direct peer exchange" if args.transport == "peer" else "RCCL all-reduce")) if sharded
                                   else ("replicas x%d" % world if world > 1 else "single GPU"),
-                   "esikf_iterations_per_solve": iters_timed / max(args.steps, 1), "residuals_used": r0["num_residuals"], "kernel_launches_per_solve": launches_per_solve,
+                   "esikf_iterations_per_solve": iters_timed / max(args.steps, 1), "residuals_used": r["num_residuals"], "kernel_launches_per_solve": launches_per_solve,
                    "launch_mode": "one launch per ESIKF iteration" if (args.no_armed or arm_stats["fired"] == 0)
                                   else "armed launches: the kernel of pass k+1 is enqueued while pass k runs and receives its pose through the pose box -- across "
                                        "srl_sweep_swap too (the launch armed behind a sweep's last pass is the next sweep's first pass)",
                    "value_is": "SURVEY 8(d)'s metric: sweeps/s of a stream of distinct sweeps, H2D of every sweep included (overlapped with the solve before it); "
-                               "the K-step region holds no event record.  Upload-then-solve without overlap:",
-                   "pcie_inclusive_sweeps_per_s": {"pipelined_prefetch": rates["pipelined"], "pinned_upload_then_solve": rates["pinned"],
-                                                   "pageable_upload_then_solve": rates["pageable"]}},
+                               "the K-step region holds no event record."},
         "ms_per_esikf_iter": elapsed * 1e3 / max(iters_timed, 1),
-        "roofline": roof, "launch_ab": launch_ab,
         "per_step_us": [round(float(x), 1) for x in np.diff(np.concatenate([[t1], step_end])) * 1e6],
         "arm_stats_timed_region": arm_stats,
-        "stream": dict(stream_long or {}, sweeps=S, unfiltered=unfiltered,
-                       value_over_long_mean=(value / stream_long["sweeps_per_s_mean"]) if stream_long else None,
-                       state_of_sweep0_equals_resident_solve=bool(0 in stream_states and np.array_equal(stream_states[0][2], r0["state"]))),
-        "resident_resolve": extra.get("resident_resolve"), "sharded_path_one_rank": extra.get("sharded_path_one_rank"),
-        "host_us_per_iter": {"enqueue": tf.sum_host_launch_us / fcalls, "wait_results": tf.sum_host_wait_us / fcalls, "build_residuals_call": tf.sum_host_total_us / fcalls,
-                             "whole_iteration": ms_per_step * 1e3 / max(r0["iters"], 1),
-                             "note": "first three: extra solves after the timed region with full event profiling (adds ~20 us/iter); whole_iteration: the timed region"},
         "host_placement": dict(run.pin_info, what="the process runs on the CPUs of the GPU's NUMA node (srl_thread_pin_to_gpu_numa)"),
-        "pcie": {"from_pinned_host_memory_sweeps_per_s": rates["pinned"], "from_pageable_host_memory_sweeps_per_s": rates["pageable"],
-                 "pipelined_prefetch_sweeps_per_s": rates["pipelined"], "median_based": medians, "solves_per_leg": n_pcie, "steps_over_1ms": stalls,
-                 "bytes_h2d_per_sweep": int(run.sweep["raw"].nbytes)},
         "setup_s": run.setup_s, "clock_warmup": {"ms": args.clock_warmup_ms, "solves": n_cw},
     }
+
+    # ---------------- --full, behind the region: the kernel's duration (roofline), the long stamped stream, A/B and PCIe forms
+    tf, other_transport, replicas, po = None, None, None, None
+    if args.full:
+        tim = aux_legs.kernel_time_leg(run, 8 if args.no_aux_legs else 200)        # (profiling runs keep the trace to the timed form: --no-aux-legs)
+        stream_long, stream_states = (None, {}) if args.no_aux_legs else aux_legs.long_stream_leg(run, max(1000, args.steps))
+        unfiltered = None if (args.no_aux_legs or sharded) else aux_legs.unfiltered_stream_leg(run)
+        extra, launch_ab = {}, None
+        if world == 1 and not args.no_aux_legs and not args.no_armed:
+            launch_ab, extra["tim_unarmed"] = aux_legs.launch_ab_leg(run, stream_states, elapsed * 1e6 / max(iters_timed, 1))
+        other_transport = multi.other_transport_leg(run, args.steps) if (sharded and world > 1 and not args.no_aux_legs and not args.no_other_transport) else None
+        r0, res_legs = aux_legs.resident_legs(run)
+        extra.update(res_legs)
+        rates, medians, stalls, n_pcie = aux_legs.pcie_legs(run, stream_long)
+        roof = aux_legs.roofline_block(run, tim, iters_timed, nb, extra)
+        replicas = multi.replicas_leg(run, args.steps) if sharded else None
+        tf = extra["tim_full"]
+        fcalls = max(tf.calls, 1)
+        out["config"]["value_is"] += "  Upload-then-solve without overlap:"
+        out["config"]["pcie_inclusive_sweeps_per_s"] = {"pipelined_prefetch": rates["pipelined"], "pinned_upload_then_solve": rates["pinned"],
+                                                        "pageable_upload_then_solve": rates["pageable"]}
+        out.update({
+            "roofline": roof, "launch_ab": launch_ab,
+            "stream": dict(stream_long or {}, sweeps=S, unfiltered=unfiltered,
+                           value_over_long_mean=(value / stream_long["sweeps_per_s_mean"]) if stream_long else None,
+                           state_of_sweep0_equals_resident_solve=bool(0 in stream_states and np.array_equal(stream_states[0][2], r0["state"]))),
+            "resident_resolve": extra.get("resident_resolve"), "sharded_path_one_rank": extra.get("sharded_path_one_rank"),
+            "host_us_per_iter": {"enqueue": tf.sum_host_launch_us / fcalls, "wait_results": tf.sum_host_wait_us / fcalls, "build_residuals_call": tf.sum_host_total_us / fcalls,
+                                 "whole_iteration": ms_per_step * 1e3 / max(r0["iters"], 1),
+                                 "note": "first three: extra solves after the timed region with full event profiling (adds ~20 us/iter); whole_iteration: the timed region"},
+            "pcie": {"from_pinned_host_memory_sweeps_per_s": rates["pinned"], "from_pageable_host_memory_sweeps_per_s": rates["pageable"],
+                     "pipelined_prefetch_sweeps_per_s": rates["pipelined"], "median_based": medians, "solves_per_leg": n_pcie, "steps_over_1ms": stalls,
+                     "bytes_h2d_per_sweep": int(run.sweep["raw"].nbytes)},
+        })
     if run.comm_info is not None or world > 1:
         # every --gpus N line explains what it ran on: the transport the library actually used, the ranks the communicator itself counts,
-        # each rank's own per-iteration time, the time behind the association kernel, the OTHER transport on the same stream
+        # each rank's own per-iteration time; with --full the time behind the association kernel and the OTHER transport on the same stream
         ci = dict(run.comm_info or {}, **comm_state)
         us_rank = elapsed_rank * 1e6 / max(iters_timed, 1)
         if run.dist is not None:
             per_rank = [None] * world
             run.dist.all_gather_object(per_rank, us_rank)
             ci["us_per_iter_per_rank"] = {"min": float(min(per_rank)), "max": float(max(per_rank))}
-        ci["behind_association_kernel_us"] = tf.sum_reduce_ms / fcalls * 1e3
+        if tf is not None:
+            ci["behind_association_kernel_us"] = tf.sum_reduce_ms / fcalls * 1e3
         ci[args.transport] = {"us_per_esikf_iter": elapsed * 1e6 / max(iters_timed, 1), "sweeps_per_s": value, "arm_stats": arm_stats, "timed_region": True}
         if other_transport is not None:
             ci[other_transport.pop("transport")] = other_transport
@@ -183,24 +209,24 @@ def main():
     if replicas is not None:
         out["aux_independent_sweeps_per_s"] = replicas
 
-    # ---------------- CPU baselines + parity (rank 0, N = 1 only): the ONLY use of oracle/ in this process, behind the timed region
-    po = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # ---------------- --full, CPU baselines + parity (rank 0, N = 1 only): the ONLY use of oracle/ in this process, behind the timed region
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from benchlib import cpu
         blocks, po = cpu.cpu_baselines_and_parity(run, r0, stream_states)
         out.update(blocks)
     run.close()
 
-    # ---------------- every BASELINE configuration + shipped setting + init mode + the off-cache sweep + the frame pipeline (rank 0, N = 1);
-    # N > 1: BASELINE config 4 -- the configuration DEFINED as sharded over 8 GPUs -- sharded over the N ranks (every rank takes part)
-    if rank == 0 and world == 1 and not args.no_configs:
+    # ---------------- --full, every BASELINE configuration + shipped setting + init mode + the off-cache sweep + the frame pipeline (rank 0,
+    # N = 1); N > 1: BASELINE config 4 -- the configuration DEFINED as sharded over 8 GPUs -- sharded over the N ranks (every rank takes part)
+    if args.full and rank == 0 and world == 1 and not args.no_configs:
         from benchlib import legs
         out.update(legs.all_configs(run.local_rank, po))
-    if sharded and world > 1 and not args.no_configs:
+    if args.full and sharded and world > 1 and not args.no_configs:
         out["sharded_config"] = multi.sharded_config_leg(run, args.transport, args.sharded_config)
     if rank == 0:
-        line_mod.write_detail(out)
-        print(line_mod.compact_line(out), flush=True)
+        if args.full:
+            line_mod.write_detail(out)
+        print(line_mod.compact_line(out, detail=args.full), flush=True)
     if run.dist is not None:
         with launcher.c_stdout_to_stderr():
             run.dist.destroy_process_group()

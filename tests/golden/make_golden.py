@@ -23,6 +23,21 @@ from sr_livo_amd import synth  # noqa: E402
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+def save_golden(path, data):
+    """np.savez_compressed in two files, `path` and `<path>_part2.npz`, split by compressed size: each stays below the 1 MiB a committed
+    file may take.  Readers merge the two."""
+    import zlib
+    size = {k: len(zlib.compress(np.ascontiguousarray(v).tobytes())) for k, v in data.items()}
+    total, acc, first = sum(size.values()), 0, {}
+    for k in data:
+        if acc >= total / 2:
+            break
+        first[k] = data[k]
+        acc += size[k]
+    np.savez_compressed(path, **first)
+    np.savez_compressed(path[: -len(".npz")] + "_part2.npz", **{k: v for k, v in data.items() if k not in first})
+
+
 def solve_case(m, sweep, frame_id, max_res, backend):
     opts = po.default_opts(max_num_residuals=max_res)
     one = m.build_plane_residuals(opts, sweep["raw"], sweep["q_pred"], sweep["t_pred"], sweep["t_last"], frame_id=frame_id)
@@ -75,8 +90,8 @@ def main():
         print(name, "keypoints", len(tsw["raw"]), "with ties", one["neq"].num_ties, "residuals", one["neq"].num_residuals)
     data["eig_solver"] = "eigen-3.3.7-ql"
     path = os.path.join(HERE, "golden_small.npz")
-    np.savez_compressed(path, **data)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB; map", m.size(), "pts", m.num_voxels(), "voxels; backend", backend)
+    save_golden(path, data)
+    print("wrote", path, "(+ _part2)", os.path.getsize(path) // 1024, "KiB; map", m.size(), "pts", m.num_voxels(), "voxels; backend", backend)
     for name in ("full", "cut600", "init", "neg1"):
         print(name, "one-pass residuals", data[f"{name}_one_num_residuals"], "ties", data[f"{name}_one_num_ties"],
               "solve iters", data[f"{name}_solve_rc"], "final t err", np.linalg.norm(data[f"{name}_solve_state"][4:7] - sweep["t_gt"]))

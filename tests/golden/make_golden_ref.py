@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 from oracle import pyoracle as po  # noqa: E402
 from oracle import pyref as pr  # noqa: E402
 from sr_livo_amd import synth  # noqa: E402
+from make_golden import save_golden  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = (("full", 100, 2**31 - 1), ("cut600", 100, 600), ("init", 5, 2**31 - 1), ("neg1", 100, -1))
@@ -79,7 +80,7 @@ def replay(data):
 
 
 def main():
-    g = np.load(os.path.join(HERE, "golden_small.npz"), allow_pickle=False)
+    g = {k: v for p in ("golden_small.npz", "golden_small_part2.npz") for k, v in np.load(os.path.join(HERE, p), allow_pickle=False).items()}
     data = dict(source=pr.load().ref_describe().decode())
     rm = pr.Map(g["map_keys"], g["map_counts"], g["map_xyz"])
     raw, q, t, t_last, vel = g["raw"], g["q_pred"], g["t_pred"], g["t_last"], g["vel"]
@@ -115,8 +116,8 @@ def main():
         print(name, "residuals", r["num_residuals"])
     replay(data)
     path = os.path.join(HERE, "golden_ref_tu.npz")
-    np.savez_compressed(path, **data)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    save_golden(path, data)
+    print("wrote", path, "(+ _part2)", os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":

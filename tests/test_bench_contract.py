@@ -317,3 +317,27 @@ def test_round6_committed_line_has_no_event_record_in_the_region_and_quotes_its_
     assert cfg["SPREAD"]["l2_hit_rate"] < 0.2 and cfg["SPREAD"]["hbm_measured_GBs"] > 2000 and cfg["SPREAD"]["us_per_iter"] > cfg["HEADLINE@600"]["us_per_iter"]
     frames = {f["points"]: f["frames_per_s"] for f in d["pipeline"]["frames"]}
     assert frames[24000] >= 4000 and frames[262144] >= 1500                # item 6: a 256k-point frame on the device
+
+
+def test_a_plain_run_line_keeps_the_contract_and_carries_no_leg_it_did_not_run(monkeypatch):
+    """bench.py without --full measures the headline alone: its line (compact_line(..., detail=False)) keeps every contract key and the exact
+    value / ms_per_step pair, and says nothing of the roofline, the PCIe forms or a detail file, which only --full produces"""
+    line = _mod("benchlib.line")
+    full = json.load(open(os.path.join(ROOT, "profiles", "r06_bench_detail.json")))
+    keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
+    plain = {k: full[k] for k in keys + ("ms_per_esikf_iter", "arm_stats_timed_region", "clock_warmup")}
+    plain["config"] = {k: v for k, v in full["config"].items() if k != "pcie_inclusive_sweeps_per_s"}
+    text = line.compact_line(plain, detail=False)
+    d = json.loads(text, parse_constant=lambda x: (_ for _ in ()).throw(AssertionError(x)))
+    for k in keys + ("config",):
+        assert k in d, k
+    assert d["value"] == full["value"] and d["ms_per_step"] == full["ms_per_step"] and "workload" in d["config"]
+    for k in ("roofline", "pcie_inclusive_sweeps_per_s", "detail", "cpu_baseline", "configs", "stream", "parity"):
+        assert k not in d, k
+    bench = _mod("bench")
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "9", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.steps == 9 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "out"

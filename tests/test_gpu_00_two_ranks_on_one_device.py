@@ -29,7 +29,8 @@ def test_bench_two_ranks_on_one_device(transport):
     # launcher of its own ranks (WORLD_SIZE must not leak in from the test environment)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--transport", transport, "--sharded-config", "C1"]
+    # (--full: the other transport, the sharded configuration, the replicas and the roofline are legs of the full run)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--transport", transport, "--sharded-config", "C1", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().split("\n") if ln.strip()]

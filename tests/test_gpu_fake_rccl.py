@@ -46,7 +46,7 @@ from sr_livo_amd import capi
 rank, G, d, max_res, fused, fake = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], int(sys.argv[5]), int(sys.argv[6]), sys.argv[7]
 srl.comm_set_library(fake)                               # explicit: this process's nccl* entry points come from the stand-in
 assert srl.comm_backend_info()[1] == 99901, srl.comm_backend_info()
-g = np.load(os.path.join(sys.argv[1], "tests", "golden", "golden_small.npz"))
+g = {k: v for p in ("golden_small.npz", "golden_small_part2.npz") for k, v in np.load(os.path.join(sys.argv[1], "tests", "golden", p)).items()}
 ctx = srl.Context(0)
 ctx.map_upload(g["map_keys"], g["map_counts"], g["map_xyz"])
 ctx.set_fused_reduce(fused)
@@ -135,7 +135,7 @@ import sr_livo_amd as srl
 from sr_livo_amd import capi
 rank, G, d, fake, expire = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5], int(sys.argv[6])
 srl.comm_set_library(fake)
-g = np.load(os.path.join(sys.argv[1], "tests", "golden", "golden_small.npz"))
+g = {k: v for p in ("golden_small.npz", "golden_small_part2.npz") for k, v in np.load(os.path.join(sys.argv[1], "tests", "golden", p)).items()}
 rng = np.random.default_rng(11)
 raw = np.concatenate([g["raw"] + rng.normal(0, 2e-3, g["raw"].shape) for _ in range(2 * G)])     # 4 096 keypoints per rank: sixteen-wave workgroups, fused
 ctx = srl.Context(0)

@@ -51,7 +51,7 @@ def test_reference_node_with_the_hip_binding_matches_the_all_cpu_reference_node(
     pr, lib = hip_node_lib
     from oracle import pyoracle as po
     from replay_reference import REPLAY_OO, REPLAY_SEQ, replay_inputs
-    gref = dict(np.load(os.path.join(HERE, "golden", "golden_ref_tu.npz"), allow_pickle=False))
+    gref = {k: v for p in ("golden_ref_tu.npz", "golden_ref_tu_part2.npz") for k, v in np.load(os.path.join(HERE, "golden", p), allow_pickle=False).items()}
     st, parts, _ = replay_inputs()
     oo = dict(REPLAY_OO, motion_compensation=mc)
     icp = po.default_opts(max_num_residuals=REPLAY_SEQ["max_num_residuals"])
@@ -111,7 +111,7 @@ def test_the_binding_rebuilds_a_device_map_that_fell_out_of_step(hip_node_lib):
     from oracle import pyoracle as po
     from replay_reference import REPLAY_OO, REPLAY_SEQ, replay_inputs
     lib.srl_integration_resyncs.argtypes = [C.c_void_p]; lib.srl_integration_resyncs.restype = C.c_long
-    gref = dict(np.load(os.path.join(HERE, "golden", "golden_ref_tu.npz"), allow_pickle=False))
+    gref = {k: v for p in ("golden_ref_tu.npz", "golden_ref_tu_part2.npz") for k, v in np.load(os.path.join(HERE, "golden", p), allow_pickle=False).items()}
     st, parts, _ = replay_inputs()
     pr.set_params(*pr.params_from_options(dict(REPLAY_OO, motion_compensation=1), po.default_opts(max_num_residuals=REPLAY_SEQ["max_num_residuals"])))
     node = pr.Node(True)

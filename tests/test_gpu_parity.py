@@ -95,7 +95,8 @@ def check_pass_against(g, ref, prefix, tol=TIGHT, well_posed=None):
 def gref():
     """tests/golden/golden_ref_tu.npz: outputs of /root/reference/src/optimize.cpp & co. compiled in place
     (oracle/_ref/libref_path.so, tests/golden/make_golden_ref.py) on the scenes of golden_small.npz."""
-    return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_ref_tu.npz"), allow_pickle=False))
+    return {k: v for p in ("golden_ref_tu.npz", "golden_ref_tu_part2.npz")
+            for k, v in np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", p), allow_pickle=False).items()}
 
 
 def check_pass_against_reference_tu(g, gref, prefix, raw, tol=TIGHT, ok=None):

@@ -474,7 +474,7 @@ from sr_livo_amd import capi
 rank, G, d, max_res, scene, fused = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], int(sys.argv[5]), sys.argv[6], int(sys.argv[7])
 ctx = srl.Context(0)
 if scene == "golden":
-    g = np.load(os.path.join(sys.argv[1], "tests", "golden", "golden_small.npz"))
+    g = {k: v for p in ("golden_small.npz", "golden_small_part2.npz") for k, v in np.load(os.path.join(sys.argv[1], "tests", "golden", p)).items()}
     ctx.map_upload(g["map_keys"], g["map_counts"], g["map_xyz"])
 else:
     from sr_livo_amd import synth

@@ -33,7 +33,7 @@ live = pytest.mark.skipif(not pr.available(), reason="oracle/_ref/libref_path.so
 
 @pytest.fixture(scope="module")
 def gref():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "golden_ref_tu.npz"), allow_pickle=False))
+    return {k: v for p in ("golden_ref_tu.npz", "golden_ref_tu_part2.npz") for k, v in np.load(os.path.join(ROOT, "tests", "golden", p), allow_pickle=False).items()}
 
 
 def accepted(o):

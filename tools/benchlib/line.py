@@ -35,25 +35,27 @@ def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE stdout line of the bench contract, from the full result dictionary: contract keys, config.workload, a compact roofline
     and cpu_baseline, parity, the PCIe-inclusive rates and one short tuple per BASELINE configuration.  Everything else (per-config
-    profile blocks, A/B legs, notes) goes to gpurun_out/bench_detail.json (`detail`).  Strict JSON, < LINE_LIMIT_BYTES."""
+    profile blocks, A/B legs, notes) goes to the detail file, DETAIL_PATH (`detail`).  Strict JSON, < LINE_LIMIT_BYTES.
+    A plain run (no --full) measured no roofline and no PCIe forms and wrote no detail file (detail=False): the line carries none of them."""
     line = {k: out.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                      "vs_baseline", "dtype", "data")}
     cfg = out.get("config", {})
     line["config"] = _pick(cfg, ("workload", "parallelism", "esikf_iterations_per_solve", "residuals_used", "kernel_launches_per_solve", "launch_mode"))
     line["ms_per_esikf_iter"] = out.get("ms_per_esikf_iter")
-    r = out.get("roofline") or {}
-    roof = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
-    roof.update(_pick(r, ("kernel", "avg_launch_ms", "launches", "measured_over", "event_period", "algorithmic_bytes_per_launch", "compulsory_bytes_per_launch",
-                          "hbm_measured_GBs", "traffic_source", "profile_stale", "launch_duration_includes")))
-    if isinstance(r.get("issue"), dict):
-        roof["issue"] = _pick(r["issue"], ("bound", "frac", "floor_us", "valu_floor_us", "salu_floor_us", "lds_floor_us"))
-    for k in ("association_only", "unarmed"):
-        if isinstance(r.get(k), dict):
-            roof[k] = _pick(r[k], ("avg_launch_ms", "frac", "launches"))
-    line["roofline"] = roof
+    if "roofline" in out:
+        r = out.get("roofline") or {}
+        roof = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
+        roof.update(_pick(r, ("kernel", "avg_launch_ms", "launches", "measured_over", "event_period", "algorithmic_bytes_per_launch", "compulsory_bytes_per_launch",
+                              "hbm_measured_GBs", "traffic_source", "profile_stale", "launch_duration_includes")))
+        if isinstance(r.get("issue"), dict):
+            roof["issue"] = _pick(r["issue"], ("bound", "frac", "floor_us", "valu_floor_us", "salu_floor_us", "lds_floor_us"))
+        for k in ("association_only", "unarmed"):
+            if isinstance(r.get(k), dict):
+                roof[k] = _pick(r[k], ("avg_launch_ms", "frac", "launches"))
+        line["roofline"] = roof
     for k in ("cpu_baseline", "cpu_baseline_port", "cpu_baseline_all_cores"):
         c = out.get(k)
         if isinstance(c, dict):
@@ -63,9 +65,10 @@ def compact_line(out):
             line[k] = e
     if isinstance(out.get("parity"), dict):
         line["parity"] = out["parity"]
-    pc = cfg.get("pcie_inclusive_sweeps_per_s") or {}
-    line["pcie_inclusive_sweeps_per_s"] = {"pipelined_prefetch": pc.get("pipelined_prefetch"), "pinned": pc.get("pinned_upload_then_solve"),
-                                           "pageable": pc.get("pageable_upload_then_solve")}
+    if "pcie_inclusive_sweeps_per_s" in cfg:
+        pc = cfg.get("pcie_inclusive_sweeps_per_s") or {}
+        line["pcie_inclusive_sweeps_per_s"] = {"pipelined_prefetch": pc.get("pipelined_prefetch"), "pinned": pc.get("pinned_upload_then_solve"),
+                                               "pageable": pc.get("pageable_upload_then_solve")}
     if isinstance(out.get("stream"), dict):
         line["stream"] = _pick(out["stream"], ("sweeps", "solves", "sweeps_per_s_mean", "sweeps_per_s_median", "value_over_long_mean", "arm_stats",
                                                "state_of_sweep0_equals_resident_solve"))
@@ -96,7 +99,8 @@ def compact_line(out):
                             probed_voxels=c.get("probed_voxels"))
     if cfgs:
         line["configs"] = cfgs
-    line["detail"] = os.path.relpath(DETAIL_PATH, ROOT)
+    if detail:
+        line["detail"] = os.path.relpath(DETAIL_PATH, ROOT)
     line = _num(line)
     # value and ms_per_step keep their full precision: the driver cross-checks one against the other
     line["value"], line["ms_per_step"] = out.get("value"), out.get("ms_per_step")

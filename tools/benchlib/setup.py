@@ -156,16 +156,17 @@ class Run:
 
     def clock_warmup(self):
         """setup, untimed: bring GPU and host core to their steady clocks (a timed region of 20 solves lasts 2 ms: measured right after the map
-        build, its steps kept getting faster until the end -- 107 -> 103 us per solve); the W warm-up steps of the contract follow"""
+        build, its steps kept getting faster until the end -- 107 -> 103 us per solve); the W warm-up steps of the contract follow.
+        It ends on a whole lap of the stream, so that the sweep each later step solves depends on W and K alone (--dump-outputs)."""
         ms = self.args.clock_warmup_ms
         n = 0
         self.streamer.begin()
         if self.dist is None:
             t = time.perf_counter()
-            while time.perf_counter() - t < ms * 1e-3:
+            while time.perf_counter() - t < ms * 1e-3 or n % self.S:
                 self.streamer.step(); n += 1
         else:
-            for _ in range(int(ms * 4)):      # ranks solve in lock-step (the exchange is collective): a count, not a clock
+            for _ in range(-(-int(ms * 4) // self.S) * self.S):      # ranks solve in lock-step (the exchange is collective): a count, not a clock (whole laps)
                 self.streamer.step(); n += 1
         return n
 

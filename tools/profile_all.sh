@@ -2,7 +2,8 @@
 # Run on the GPU box (via gpurun): the un-profiled bench line + rocprofv3 (kernel trace + separate PMC passes) of every
 # configuration quoted in DESIGN.md section 5.  Summaries land in gpurun_out/prof_<tag>/ and gpurun_out/bench_final.json.
 R=${1:-r06}
-python bench.py --steps 20 --warmup 5 > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err; cp gpurun_out/bench_detail.json gpurun_out/bench_final_detail.json
+D=$(dirname "$(cd tools && python -c 'from benchlib.line import DETAIL_PATH; print(DETAIL_PATH)')")      # where bench.py --full writes its detail file
+python bench.py --steps 20 --warmup 5 --full > $D/bench_final.json 2> $D/bench_final.err; cp $D/bench_detail.json $D/bench_final_detail.json
 tools/profile_gpu.sh ${R}_headline 10 "" > /dev/null 2>&1
 tools/profile_gpu.sh ${R}_headline_unarmed 10 "--no-armed" > /dev/null 2>&1
 tools/profile_gpu.sh ${R}_headline_unfused 10 "--no-fused-reduce --no-armed" > /dev/null 2>&1

@@ -1263,6 +1263,11 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
             s_pimu[kq * 3 + 0] = p_imu.x; s_pimu[kq * 3 + 1] = p_imu.y; s_pimu[kq * 3 + 2] = p_imu.z;
         }
         s_pw[kq * 3 + 0] = p_w.x; s_pw[kq * 3 + 1] = p_w.y; s_pw[kq * 3 + 2] = p_w.z;
+        // static_cast<short>(point / size_voxel_map): truncation toward zero (optimize.cpp:372-374)
+        // (x / 1.0 == x exactly: the shipped size_voxel_map = 1.0 skips three FP64 divisions)
+        const bool unit = A.size_voxel == 1.0;
+        const int kv[3] = {(int)(short)(int)(unit ? p_w.x : p_w.x / A.size_voxel), (int)(short)(int)(unit ? p_w.y : p_w.y / A.size_voxel),
+                           (int)(short)(int)(unit ? p_w.z : p_w.z / A.size_voxel)};
         {
             // FP32 prefilter constants of this keypoint (used once per keypoint by every lane of the wave later):
             // error model of select_topk_f32_r, m(T) = 4 a (T + 1)/2 + 8 u T + 4 a^2 at T = 2 tau + 1e-6, thr = (tau + 2 m)(1 + 1e-6)
@@ -1279,24 +1284,40 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
             qf[4] = (1.0f + 2.0f * m1) * 1.00001f;                                  // c1
             // squared cull radius from the previous pass's bound (SrlAssocArgs::bound_in): r = sqrt(tau) + |p_w - p_w_prev| + slack for
             // everything that is rounded on the way (the stored FP32 positions -- a point may sit one ulp across its voxel's face --, the
-            // FP32 query and box faces of probe_finish, tau's and the distance's own rounding); +inf = visit every voxel
+            // FP32 query and box faces of probe_finish, tau's and the distance's own rounding); +inf = visit every voxel.
+            // The radius holds only while the previous pass's K neighbours are candidates of this pass, and searchNeighbors visits the
+            // (2 NB + 1)^3 voxels around the CURRENT key alone: a keypoint that crossed a voxel face may have left its neighbours behind
+            // with the layer it no longer probes, and its K nearest here may lie beyond r.  So the bound is used only where the ball
+            // B(p_w_prev, sqrt(tau)) lies inside the union of those boxes -- per axis, [lo(key - NB), hi(key + NB)] with the truncation
+            // boxes of probe_finish (key 0: (-1, 1)), the same slack on both sides.  Sparse neighbourhoods that reach beyond the region
+            // visit every voxel instead (tests/test_gpu_bound_culling_sparse.py).
             float r2 = __builtin_huge_valf();
             if (use_bounds && g < A.bound_use) {
                 const float4 bp = reinterpret_cast<const float4 *>(A.bound_in)[g];
                 const float ex = qxf - bp.x, ey = qyf - bp.y, ez = qzf - bp.z;
-                const float mag = fabsf(qxf) + fabsf(qyf) + fabsf(qzf);
-                const float r = sqrtf(bp.w) * 1.000001f + sqrtf(ex * ex + ey * ey + ez * ez) * 1.000001f + (1e-3f + 1e-6f * mag);
-                r2 = (r * r) * 1.00001f;                                            // (tau = +inf: no K-th neighbour was known -- stays +inf)
+                const float mag = fmaxf(fabsf(qxf) + fabsf(qyf) + fabsf(qzf), fabsf(bp.x) + fabsf(bp.y) + fabsf(bp.z));
+                const float slack = 1e-3f + 1e-6f * mag;
+                const float rt = sqrtf(bp.w) * 1.000001f;
+                const float sz = (float)A.size_voxel;
+                const float bq[3] = {bp.x, bp.y, bp.z};
+                bool inside = true;                                                 // (tau = +inf or NaN: every comparison fails)
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    const int vlo = kv[ax] - NB, vhi = kv[ax] + NB;
+                    const float lo = (float)(vlo > 0 ? vlo : vlo - 1) * sz, hi = (float)(vhi < 0 ? vhi : vhi + 1) * sz;
+                    inside = inside && (bq[ax] - rt) - slack >= lo && (bq[ax] + rt) + slack <= hi;
+                }
+                if (inside) {
+                    const float r = rt + sqrtf(ex * ex + ey * ey + ez * ez) * 1.000001f + slack;
+                    r2 = (r * r) * 1.00001f;
+                }
             }
             qf[5] = r2;
             *reinterpret_cast<double *>(qf + 6) = __builtin_huge_val();             // this pass's tau: set by whoever finishes the keypoint on the fast path
         }
-        // static_cast<short>(point / size_voxel_map): truncation toward zero (optimize.cpp:372-374)
-        // (x / 1.0 == x exactly: the shipped size_voxel_map = 1.0 skips three FP64 divisions)
-        const bool unit = A.size_voxel == 1.0;
-        s_kv[kq * 4 + 0] = (int)(short)(int)(unit ? p_w.x : p_w.x / A.size_voxel);
-        s_kv[kq * 4 + 1] = (int)(short)(int)(unit ? p_w.y : p_w.y / A.size_voxel);
-        s_kv[kq * 4 + 2] = (int)(short)(int)(unit ? p_w.z : p_w.z / A.size_voxel);
+        s_kv[kq * 4 + 0] = kv[0];
+        s_kv[kq * 4 + 1] = kv[1];
+        s_kv[kq * 4 + 2] = kv[2];
         s_nfound[kq] = 0;
         s_ncand[kq] = 0;
     } else if (wave == WPB - 1 && lane < KPW + 2) {

@@ -845,17 +845,100 @@ int srl_get_arm_stats(srl_ctx *ctx, uint64_t out[4]) {
 #define SRL_INTERNAL_PEER_TIMEOUT 3       // ... a peer's row had not arrived within the kernel's bounded spin: the HOST decides what follows
 #define SRL_INTERNAL_ARM_EXPIRED 2        // the armed launch this pass fired had given up waiting: the pass is repeated with a normal launch
 
-// the kernel arguments of one pass
-static int prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, int n_eff, SrlAssocArgs &a, int &nb_out) {
-    // init-mode switches (optimize.cpp:21-23)
+// Can the ordered cut-off (optimize.cpp:107) trigger?  Only when max_num_residuals <= number of keypoints; max_num_residuals <= 0:
+// the loop stops at the first keypoint with a plane, wherever (in whichever shard) that is.
+static bool cut_possible(const srl_ctx *ctx, const srl_icp_opts *o) {
+    return o->max_num_residuals <= 0 || (long long)o->max_num_residuals <= (long long)ctx->total_n;
+}
+
+// How this rank's result meets the other ranks': one rank; direct peer exchange (srl_peer_attach); RCCL on the context's stream
+// (SRL_FORCE_COLLECTIVES: with one rank too); the caller's callbacks (srl_comm_set_host_callbacks, srl_debug_set_gather_counts).
+// Peers and a communicator never meet: srl_peer_attach refuses a communicator (parked by srl_comm_suspend too), srl_comm_init_rank and
+// srl_comm_set_host_callbacks refuse peers.  Peers with one rank (srl_comm_suspend, srl_debug_set_gather_counts(NULL)) exchange nothing.
+enum class Transport { single, peer, rccl, host_callback };
+static Transport pass_transport(const srl_ctx *ctx) {
+    if (ctx->peer_on && ctx->nranks > 1) return Transport::peer;
+    if (ctx->comm && (ctx->nranks > 1 || ctx->force_coll)) return Transport::rccl;
+    return ctx->nranks > 1 ? Transport::host_callback : Transport::single;
+}
+
+// Every decision of one pass, taken before anything is allocated, recorded or launched: the steps below only read it.
+struct PassPlan {
+    int nb, thr, K;                  // voxel neighbourhood, occupancy threshold (init mode: optimize.cpp:21-23), neighbours
+    int kpw, wpb, kpb, nblocks;      // launch shape
+    bool cut;                        // cut_possible
+    Transport transport;
+    bool dbg_gather;                 // srl_debug_set_gather_counts: the other ranks' counts are preloaded in d_gather
+    bool fused, fuse_cut;            // the last workgroup does the final reduction (one kernel per pass) ... and the ordered cut
+    bool tagged_mail, mailbox;       // the result reaches the host as tagged granules / the pass ends in the host mailbox (else d_out)
+    bool arm_ok;                     // the next pass may be armed behind this one
+};
+
+static int plan_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, int n_eff, PassPlan &p) {
     const bool init_mode = f->frame_id < o->init_num_frames;
-    const int nb = init_mode ? 2 : o->voxel_neighborhood;
-    const int thr = init_mode ? 1 : o->threshold_voxel_occupancy;
-    const int K = o->max_number_neighbors;
-    if (nb < 1 || nb > 2) { ctx->err = "voxel_neighborhood must be 1 or 2"; return SRL_ERR_UNSUPPORTED; }
-    if (K < 1 || K > SRL_MAX_NEIGHBORS) { ctx->err = "max_number_neighbors must be in [1,32]"; return SRL_ERR_UNSUPPORTED; }
+    p.nb = init_mode ? 2 : o->voxel_neighborhood;
+    p.thr = init_mode ? 1 : o->threshold_voxel_occupancy;
+    p.K = o->max_number_neighbors;
+    if (p.nb < 1 || p.nb > 2) { ctx->err = "voxel_neighborhood must be 1 or 2"; return SRL_ERR_UNSUPPORTED; }
+    if (p.K < 1 || p.K > SRL_MAX_NEIGHBORS) { ctx->err = "max_number_neighbors must be in [1,32]"; return SRL_ERR_UNSUPPORTED; }
     if (!(o->size_voxel_map > 0.0)) return SRL_ERR_BAD_ARG;
 
+    // Launch shape.  Sweeps of >= 2 048 keypoints: 16-wave workgroups (one per CU) with the smallest instantiated
+    // keypoints-per-wave count that still places the sweep in ONE round of workgroups -- a wave's serial chain is as short as
+    // the sweep allows and no CU idles while another runs a second workgroup.  Per call, kernel / wall us (tools/shape_sweep.py):
+    //    4 096 keypoints  fused: 4 per wave 25.5 / 31.0 -> 2 per wave 21.5 / 26.8
+    //   24 576 keypoints  fused: 8 per wave (192 workgroups) 36.7 / 45.9 -> 6 per wave (256) 33.4 / 42.4;  two kernels: 4-wave
+    //                     workgroups x 8 per wave 29.2 / 49.6 -> 27.8 / 47.2
+    //   16 384 keypoints  fused: 2 per wave (512 workgroups, two rounds) 37.0 / 42.2 against 4 per wave 28.3 / 33.7
+    // Smaller sweeps, or K too large for the 16-wave LDS footprint: 4-wave workgroups with keypoints per wave by sweep size.
+    p.kpw = srl_keypoints_per_wave(n_eff);
+    p.wpb = 4;
+    const int k1 = srl_keypoints_per_wave_one_round(n_eff, ctx->num_cu);
+    if (n_eff >= 2048 && srl_assoc_lds_bytes(p.K, p.nb, k1, 16) <= SRL_LDS_LIMIT) { p.kpw = k1; p.wpb = 16; }
+    if (ctx->force_kpw) {            // srl_debug_set_launch_shape: tuning experiments only
+        p.kpw = ctx->force_kpw;
+        const bool only16 = p.kpw != 4 && p.kpw != 8 && p.kpw != 16;
+        p.wpb = ((ctx->force_wpb == 16 || only16) && srl_assoc_lds_bytes(p.K, p.nb, p.kpw, 16) <= SRL_LDS_LIMIT) ? 16 : 4;
+        if (only16 && p.wpb != 16) p.kpw = 4;
+    }
+    if (ctx->ablate != 0 && srl_assoc_lds_bytes(p.K, p.nb, 16, 16) <= SRL_LDS_LIMIT) { p.kpw = 16; p.wpb = 16; }   // the one shape that carries the debug switches
+    p.kpb = p.kpw * p.wpb;
+    p.nblocks = (n_eff + p.kpb - 1) / p.kpb;
+
+    p.cut = cut_possible(ctx, o);
+    p.transport = pass_transport(ctx);
+    p.dbg_gather = ctx->dbg_gather;
+    // Fused final reduction (the last workgroup sums the block partials and publishes the result itself: one kernel per ESIKF
+    // iteration) needs: every accepted residual counts (no ordered cut can trigger), nobody reads per-keypoint records, and few,
+    // large workgroups -- every workgroup publishes a row through memory and the last one re-reads them all.  Measured per
+    // srl_build_residuals call (tools/shape_sweep.py; kernel us / wall us):
+    //   16k keypoints  4-wave workgroups, 2 kernels 23.4 / 41.1    16-wave fused 27.0 / 32.4
+    //   24k keypoints                               30.4 / 47.2                  35.7 / 41.3
+    //   64k keypoints  16-wave, 2 kernels           52   / 78                    58   / 72     (1 000 small workgroups fused: +14 us)
+    // A sharded sweep fuses too when no ordered cut can trigger: the rank's totals go straight into the peers' inboxes (still ONE kernel
+    // per pass), into a device-side mailbox the RCCL all-reduce works on, or into the host mailbox for the all-reduce callback.  With the
+    // ordered cut a rank's budget depends on the counts of the ranks before it: count kernel, exchange, reduce kernel.  A single rank
+    // fuses the cut too: the finisher locates the workgroup that holds the max-th accepted residual and re-accumulates that workgroup's
+    // records, which travel as tagged granules like the rows (small workgroups only: one record granule per finisher thread).
+    const bool fusable = !ctx->taps && ctx->ablate == 0 && o->max_num_residuals > 0 && ctx->fuse_reduce && !ctx->dbg_gather;
+    p.fuse_cut = fusable && p.cut && p.transport == Transport::single && p.wpb == 16 && p.kpb <= SRL_FUSED_CUT_MAX_KPB && p.nblocks <= 512;
+    p.fused = p.fuse_cut || (fusable && !p.cut && p.wpb == 16 && p.nblocks <= SRL_FUSED_MAX_BLOCKS);
+    p.tagged_mail = p.fused && p.transport != Transport::rccl;
+    // one rank: the reduce kernel publishes straight into host-mapped memory and the host spins on the sequence word -- no D2H copy,
+    // no stream synchronisation on the per-iteration critical path (a fused pass without RCCL ends there as well)
+    p.mailbox = p.transport != Transport::rccl && (p.transport == Transport::single || p.fused);
+    // Armed launches (arm_next): a fused pass whose one kernel reports to this host, sharded ones too -- every rank arms and fires its own
+    // launch from its own copy of the 17-dim update, a rank whose launch was cancelled or gave up simply launches the pass.  Peers: the
+    // armed launch carries the tag of the NEXT exchange.  RCCL: it is enqueued BEHIND this pass's all-reduce and publish kernel, so it is
+    // resident about when the host reads the result; a launch that gave up adds a time-out flag to the reduced range (assoc_body's
+    // prologue) so that every rank repeats the pass.  (fused implies 16-wave workgroups, no ablation and no taps)
+    const bool fast_sel = ctx->select_mode == 0 || ctx->select_mode == 4;
+    p.arm_ok = ctx->arm_mode != 0 && p.fused && fast_sel && ctx->profiling != 1 && (p.transport != Transport::host_callback || ctx->cb_ar);
+    return SRL_OK;
+}
+
+// the kernel arguments of one pass (all but its sequence number and exchange tag)
+static void prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, int n_eff, const PassPlan &p, SrlAssocArgs &a) {
     std::memset(&a, 0, sizeof a);
     a.raw_x = ctx->d_raw;
     a.raw_y = ctx->d_raw + ctx->sweep_cap;
@@ -867,9 +950,9 @@ static int prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_op
     a.slabs = ctx->d_slabs;
     a.inf_off = ctx->slab_cap * (unsigned)SRL_SLAB_BYTES;
     // records {J, d, w} + status feed the ordered cut-off (optimize.cpp:107) and the parity taps only: 4 MB of stores per
-    // 64k sweep that the throughput configuration (max_num_residuals > number of keypoints) never reads
-    const bool cut_possible_here = o->max_num_residuals <= 0 || (long long)o->max_num_residuals <= (long long)ctx->total_n;
-    a.write_rec = (ctx->taps || cut_possible_here) ? 1 : 0;
+    // 64k sweep that the throughput configuration (max_num_residuals > number of keypoints) never reads -- nor does a fused cut,
+    // whose finisher has the record granules
+    a.write_rec = ((ctx->taps || p.cut) && !p.fuse_cut) ? 1 : 0;
     {
         const srl::Quat q(f->q[0], f->q[1], f->q[2], f->q[3]);
         const srl::Mat3 Rn = q.normalized().toRotationMatrix();    // optimize.cpp:35
@@ -893,9 +976,9 @@ static int prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_op
     }
     a.power_planarity = o->power_planarity;
     a.nbr_scale = o->max_dist_to_plane_icp * o->min_number_neighbors;   // kMaxPointToPlane * kMinNumNeighbors
-    a.K = K;
+    a.K = p.K;
     a.min_nb = o->min_number_neighbors;
-    a.thr_cap = thr;
+    a.thr_cap = p.thr;
     a.select_mode = ctx->select_mode;                           // 0 unless srl_debug_set_select_mode was called (tests)
     a.ablate = ctx->ablate;                                     // 0 unless srl_debug_set_ablate was called (profiling tools only)
     a.stamps = ctx->h_arm_stamps;                               // null unless srl_debug_pass_stamps is on
@@ -903,346 +986,242 @@ static int prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_op
     a.status = ctx->d_status;
     a.partials = ctx->d_partials;
     a.binfo = ctx->d_binfo;
-    {
-        // bounds of the previous pass: usable when they were written with these options (sweep and map changes reset bound_n themselves)
-        float sv = (float)o->size_voxel_map;
-        int sv_bits; std::memcpy(&sv_bits, &sv, 4);
-        const int sig[4] = {K, nb, thr, sv_bits};
-        if (std::memcmp(sig, ctx->bound_sig, sizeof sig) != 0) { ctx->bound_n = 0; std::memcpy(ctx->bound_sig, sig, sizeof sig); }
-        a.bound_out = ctx->d_bound;
-        a.bound_in = ctx->bound_mode != 0 ? ctx->d_bound : nullptr;
-        a.bound_use = a.bound_in ? std::min(ctx->bound_n, n_eff) : 0;
-    }
-    nb_out = nb;
-    return SRL_OK;
-}
-
-static int build_residuals_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, srl_normal_eq *out, int n_eff) {
-    const auto t_entry = std::chrono::steady_clock::now();
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    SrlAssocArgs a;
-    int nb = 1;
-    { const int rca = prepare_assoc_args(ctx, f, o, n_eff, a, nb); if (rca) return rca; }
-    const int K = o->max_number_neighbors;
-    const bool cut_possible_here = o->max_num_residuals <= 0 || (long long)o->max_num_residuals <= (long long)ctx->total_n;
-    ctx->taps_valid = false;
     if (ctx->taps) {
-        int rc = ensure_taps(ctx, ctx->n, K);
-        if (rc) return rc;
         a.tap_ids = ctx->d_tap_ids;
         a.tap_ncand = ctx->d_tap_ncand;
         a.tap_normal = ctx->d_tap_normal;
         a.tap_a2d = ctx->d_tap_a2d;
         a.tap_offset = ctx->d_tap_offset;
+    }
+    {
+        // bounds of the previous pass: usable when they were written with these options (sweep and map changes reset bound_n themselves)
+        float sv = (float)o->size_voxel_map;
+        int sv_bits; std::memcpy(&sv_bits, &sv, 4);
+        const int sig[4] = {p.K, p.nb, p.thr, sv_bits};
+        if (std::memcmp(sig, ctx->bound_sig, sizeof sig) != 0) { ctx->bound_n = 0; std::memcpy(ctx->bound_sig, sig, sizeof sig); }
+        a.bound_out = ctx->d_bound;
+        a.bound_in = ctx->bound_mode != 0 ? ctx->d_bound : nullptr;
+        a.bound_use = a.bound_in ? std::min(ctx->bound_n, n_eff) : 0;
+    }
+    if (p.fused) {
+        a.granules = ctx->d_granules;
+        a.mailbox = p.transport == Transport::rccl ? ctx->d_mail : ctx->h_mail;
+        a.mail_tagged = p.tagged_mail ? 1 : 0;
+    }
+    if (p.fuse_cut) {
+        a.rec_granules = ctx->d_rec_granules;
+        a.cut_max = o->max_num_residuals;
+    }
+}
+
+// the per-pass buffers beyond ensure_work's (taps, forced launch shape, light-profiling ring, RCCL mailbox, fused-cut record granules)
+static int grow_pass_buffers(srl_ctx *ctx, const PassPlan &p) {
+    int rc;
+    ctx->taps_valid = false;
+    if (ctx->taps) {
+        if ((rc = ensure_taps(ctx, ctx->n, p.K))) return rc;
         if (ctx->n > 0) {
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_ids, 0xFF, (size_t)ctx->n * K * sizeof(int), ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_ids, 0xFF, (size_t)ctx->n * p.K * sizeof(int), ctx->stream));
             HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_normal, 0, (size_t)ctx->n * 3 * sizeof(double), ctx->stream));
             HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_a2d, 0, (size_t)ctx->n * sizeof(double), ctx->stream));
             HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_offset, 0, (size_t)ctx->n * sizeof(double), ctx->stream));
         }
     }
-    // launch shape: keypoints per wave by sweep size; 16-wave workgroups (one per CU) whenever their LDS footprint fits
-    int kpw = srl_keypoints_per_wave(n_eff);
-    // Fused final reduction (the last workgroup sums the block partials and publishes the result itself: one kernel per ESIKF
-    // iteration) needs: single rank, every accepted residual counts (no ordered cut can trigger), nobody reads per-keypoint
-    // records, and few, large workgroups -- every workgroup publishes a row through memory and the last one re-reads them
-    // all.  Measured per srl_build_residuals call (tools/shape_sweep.py; kernel us / wall us):
-    //   16k keypoints  4-wave workgroups, 2 kernels 23.4 / 41.1    16-wave fused 27.0 / 32.4
-    //   24k keypoints                               30.4 / 47.2                  35.7 / 41.3
-    //   64k keypoints  16-wave, 2 kernels           52   / 78                    58   / 72     (1 000 small workgroups fused: +14 us)
-    const bool single_rank = ctx->nranks == 1 && !(ctx->comm && ctx->force_coll);
-    // A sharded sweep fuses too when no ordered cut can trigger (every rank's finishing workgroup then sums its own shard):
-    // the rank's totals go  - straight into the peers' inboxes (direct peer exchange: still ONE kernel per pass),
-    //                       - into a device-side mailbox the RCCL all-reduce works on,  or
-    //                       - into the host mailbox, for the host all-reduce callback.
-    // With the ordered cut a rank's budget depends on the counts of the ranks before it: count kernel, exchange, reduce kernel.
-    const bool fuse_any = !ctx->taps && a.ablate == 0 && o->max_num_residuals > 0 && ctx->fuse_reduce && !ctx->dbg_gather;
-    const bool fuse_base = single_rank && fuse_any;
-    const bool can_fuse = fuse_any && !cut_possible_here;
-    // ... and WITH the ordered cut (the shipped max_num_residuals = 600): the finisher also locates the workgroup that holds the
-    // max-th accepted residual and re-accumulates that workgroup's records, which travel as tagged granules like the rows
-    // (small workgroups only: one record granule per finisher thread)
-    bool can_fuse_cut = fuse_base && cut_possible_here;
-    // Launch shape.  Sweeps of >= 2 048 keypoints: 16-wave workgroups (one per CU) with the smallest instantiated
-    // keypoints-per-wave count that still places the sweep in ONE round of workgroups -- a wave's serial chain is as short as
-    // the sweep allows and no CU idles while another runs a second workgroup.  Per call, kernel / wall us (tools/shape_sweep.py):
-    //    4 096 keypoints  fused: 4 per wave 25.5 / 31.0 -> 2 per wave 21.5 / 26.8
-    //   24 576 keypoints  fused: 8 per wave (192 workgroups) 36.7 / 45.9 -> 6 per wave (256) 33.4 / 42.4;  two kernels: 4-wave
-    //                     workgroups x 8 per wave 29.2 / 49.6 -> 27.8 / 47.2
-    //   16 384 keypoints  fused: 2 per wave (512 workgroups, two rounds) 37.0 / 42.2 against 4 per wave 28.3 / 33.7
-    // Smaller sweeps, or K too large for the 16-wave LDS footprint: 4-wave workgroups.
-    int wpb = 4;
-    {
-        const int k1 = srl_keypoints_per_wave_one_round(n_eff, ctx->num_cu);
-        if (n_eff >= 2048 && srl_assoc_lds_bytes(K, nb, k1, 16) <= SRL_LDS_LIMIT) { kpw = k1; wpb = 16; }
+    ctx->last_nblocks = p.nblocks;
+    if (p.nblocks > ctx->block_cap) {  // a forced launch shape can need more workgroups than ensure_work provided for
+        if ((rc = ensure(ctx, ctx->d_partials, (size_t)p.nblocks * SRL_PART_STRIDE))) return rc;
+        if ((rc = ensure(ctx, ctx->d_binfo, (size_t)p.nblocks))) return rc;
+        ctx->block_cap = p.nblocks;
     }
-    if (ctx->force_kpw) {            // srl_debug_set_launch_shape: tuning experiments only
-        kpw = ctx->force_kpw;
-        const bool only16 = kpw != 4 && kpw != 8 && kpw != 16;
-        wpb = ((ctx->force_wpb == 16 || only16) && srl_assoc_lds_bytes(K, nb, kpw, 16) <= SRL_LDS_LIMIT) ? 16 : 4;
-        if (only16 && wpb != 16) kpw = 4;
+    if (ctx->profiling == 2 && ctx->ring_head - ctx->ring_tail >= (unsigned)srl_ctx::PROF_RING && (rc = drain_ring(ctx, true))) return rc;
+    if (p.fused && p.transport == Transport::rccl && !ctx->d_mail && (rc = ensure(ctx, ctx->d_mail, 1))) return rc;
+    const size_t need = (size_t)p.nblocks * p.kpb * 16;
+    if (p.fuse_cut && need > ctx->rec_granule_cap) {
+        if ((rc = ensure(ctx, ctx->d_rec_granules, need))) return rc;
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_rec_granules, 0, need * sizeof(unsigned long long), ctx->stream));   // no stale tag can match
+        ctx->rec_granule_cap = need;
     }
-    if (ctx->ablate != 0 && srl_assoc_lds_bytes(K, nb, 16, 16) <= SRL_LDS_LIMIT) { kpw = 16; wpb = 16; }   // the one shape that carries the debug switches
-    const int kpb = kpw * wpb;
-    const int nblocks = (n_eff + kpb - 1) / kpb;
-    ctx->last_nblocks = nblocks;
-    if (nblocks > ctx->block_cap) {  // a forced launch shape can need more workgroups than ensure_work provided for
-        int rcb;
-        if ((rcb = ensure(ctx, ctx->d_partials, (size_t)nblocks * SRL_PART_STRIDE))) return rcb;
-        if ((rcb = ensure(ctx, ctx->d_binfo, (size_t)nblocks))) return rcb;
-        ctx->block_cap = nblocks;
-        a.partials = ctx->d_partials;
-        a.binfo = ctx->d_binfo;
-    }
-    const bool prof = ctx->profiling == 1;
-    const bool prof_light = ctx->profiling == 2;
-    hipEvent_t *ring_ev = nullptr;
-    if (prof_light) {
-        if (ctx->ring_head - ctx->ring_tail >= (unsigned)srl_ctx::PROF_RING) { int rc = drain_ring(ctx, true); if (rc) return rc; }
-        ring_ev = ctx->ring[ctx->ring_head % srl_ctx::PROF_RING];
-    }
+    return SRL_OK;
+}
 
-    can_fuse_cut = can_fuse_cut && wpb == 16 && kpb <= SRL_FUSED_CUT_MAX_KPB && nblocks <= 512;      // (the finisher reads one row's counters per thread)
-    const bool fused = (can_fuse && wpb == 16 && nblocks <= SRL_FUSED_MAX_BLOCKS) || can_fuse_cut;
-    unsigned long long seq_now = ++ctx->seq;          // (a cancelled armed launch below takes this number with it: see there)
-    const bool coll = ctx->comm && (ctx->nranks > 1 || ctx->force_coll) && !ctx->peer_on;
-    const bool peer = ctx->peer_on && ctx->nranks > 1;
-    if (peer && ctx->peer_failed) {
-        ctx->err = "direct peer exchange: this session has failed (a rank's row never arrived); srl_peer_detach, srl_peer_export and srl_peer_attach on every rank start a new one";
-        return SRL_ERR_COMM;
-    }
-    unsigned peer_epoch = 0;
-    int peer_slot = 0;
-    auto next_exchange = [&]() {           // one tag per exchange, the same on every rank (never 0: an untouched inbox holds zeros)
-        ++ctx->peer_seq;
-        peer_epoch = (unsigned)(ctx->peer_seq & 0xFFFFFFFFull);
-        if (peer_epoch == 0) { ++ctx->peer_seq; peer_epoch = 1; }
-        peer_slot = (int)(ctx->peer_seq & 1ull);
-    };
-    const bool tagged_mail = fused && !(ctx->comm && (ctx->nranks > 1 || ctx->force_coll) && !ctx->peer_on);   // fused and not the RCCL form: the finisher reports to the host
-    if (fused) {
-        a.granules = ctx->d_granules;
-        a.mailbox = ctx->h_mail;
-        a.mail_tagged = tagged_mail ? 1 : 0;
-        a.seq = seq_now;
-        if (peer) {
-            next_exchange();
-            a.peer = ctx->d_peer; a.peer_epoch = peer_epoch; a.peer_slot = peer_slot;
-        } else if (coll) {
-            if (!ctx->d_mail) { int rcm = ensure(ctx, ctx->d_mail, 1); if (rcm) return rcm; }
-            a.mailbox = ctx->d_mail;
-        }
-    }
-    if (can_fuse_cut) {
-        const size_t need = (size_t)nblocks * kpb * 16;
-        if (need > ctx->rec_granule_cap) {
-            int rcg;
-            if ((rcg = ensure(ctx, ctx->d_rec_granules, need))) return rcg;
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_rec_granules, 0, need * sizeof(unsigned long long), ctx->stream));   // no stale tag can match
-            ctx->rec_granule_cap = need;
-        }
-        a.rec_granules = ctx->d_rec_granules;
-        a.cut_max = o->max_num_residuals;
-        a.write_rec = 0;                                    // nobody reads the global records: the finisher has the granules
-    }
+// The tag of the exchange counted `seq`, the same on every rank.  Tag 0 is skipped (an untouched inbox holds zeros): `seq` then
+// moves on by one.  The two inbox slots alternate.
+struct ExchangeTag { unsigned long long seq; unsigned epoch; int slot; };
+static ExchangeTag exchange_tag(unsigned long long seq) {
+    if ((unsigned)seq == 0u) ++seq;
+    return {seq, (unsigned)seq, (int)(seq & 1ull)};
+}
+static ExchangeTag next_exchange(srl_ctx *ctx) {
+    const ExchangeTag t = exchange_tag(ctx->peer_seq + 1);
+    ctx->peer_seq = t.seq;
+    return t;
+}
 
-    // ---- armed launch: fire the kernel that is already waiting for this pass, if its arguments are this pass's
-    const bool fast_sel = ctx->select_mode == 0 || ctx->select_mode == 4;
-    // (a grid larger than the chip is armed too: its first round waits resident, the later rounds find the pose in the box when they start)
-    // SHARDED passes are armed too where the rank's pass is ONE kernel that reports to this host: the direct peer exchange (the rows of the
-    // ranks meet inside the finishing workgroups; the armed launch carries the tag of the NEXT exchange -- every fused pass is exactly one)
-    // and the host-callback transport.  Every rank arms and fires its own launch from its own copy of the 17-dim update; a rank whose
-    // launch was cancelled or gave up simply launches the pass -- the exchange does not care how a kernel got there.  Not with RCCL
-    // (the all-reduce and the publish kernel sit between two passes on the stream) and not with the ordered cut (three exchanges per pass).
-    const bool host_cb = ctx->nranks > 1 && !coll && !peer && ctx->cb_ar != nullptr && !ctx->dbg_gather;
-    // RCCL: armed as well when the pass is fused -- the launch is enqueued BEHIND this pass's all-reduce and publish kernel (stream order),
-    // so it is resident about when the host reads the result; a launch that gave up contributes a time-out flag to the reduced range
-    // (assoc_body's prologue) so that every rank repeats the pass.
-    const bool arm_ok = ctx->arm_mode != 0 && fused && (single_rank || peer || host_cb || coll) && wpb == 16 && fast_sel &&
-                        a.ablate == 0 && !prof && !ctx->taps;
-    auto signature = [](const SrlAssocArgs &src) {
-        SrlAssocArgs sg = src;
-        std::memset(sg.Rn, 0, sizeof sg.Rn); std::memset(sg.R, 0, sizeof sg.R); std::memset(sg.t, 0, sizeof sg.t);
-        std::memset(sg.t_last, 0, sizeof sg.t_last);       // (optimize.cpp:25: per sweep -- it travels through the pose box with the pose)
-        sg.pose_box = nullptr; sg.pose_relay = nullptr; sg.pose_relayed = 0; sg.pose_epoch = 0; sg.arm_linger_ticks = 0;
-        // the sweep (either buffer of the context) and its keypoint count travel with the pose: compared separately below
-        sg.raw_x = sg.raw_y = sg.raw_z = nullptr; sg.alt_x = sg.alt_y = sg.alt_z = nullptr; sg.n = 0; sg.aos = nullptr; sg.alt_aos = nullptr;
-        sg.bound_use = 0;        // (an armed launch carries its own: the keypoints of the pass it was armed behind)
-        return sg;
-    };
+// what an armed launch and a pass must agree on: the arguments without the pose and the sweep (those travel through the pose box)
+static SrlAssocArgs arm_signature(const SrlAssocArgs &src) {
+    SrlAssocArgs sg = src;
+    std::memset(sg.Rn, 0, sizeof sg.Rn); std::memset(sg.R, 0, sizeof sg.R); std::memset(sg.t, 0, sizeof sg.t);
+    std::memset(sg.t_last, 0, sizeof sg.t_last);       // (optimize.cpp:25: per sweep -- it travels through the pose box with the pose)
+    sg.pose_box = nullptr; sg.pose_relay = nullptr; sg.pose_relayed = 0; sg.pose_epoch = 0; sg.arm_linger_ticks = 0;
+    // the sweep (either buffer of the context) and its keypoint count travel with the pose: compared separately (fire_or_cancel)
+    sg.raw_x = sg.raw_y = sg.raw_z = nullptr; sg.alt_x = sg.alt_y = sg.alt_z = nullptr; sg.n = 0; sg.aos = nullptr; sg.alt_aos = nullptr;
+    sg.bound_use = 0;        // (an armed launch carries its own: the keypoints of the pass it was armed behind)
+    return sg;
+}
+
+// The armed launch: FIRE it when its arguments are this pass's (the host only writes the pose box), else cancel it.  A cancelled launch
+// carried this pass's sequence number, and if it has already given up on its own it has left its "expired" report under that number in
+// the mailbox -- so the pass takes the next one (a launch that reused the number would read that report as its own result).
+static int fire_or_cancel(srl_ctx *ctx, const PassPlan &p, SrlAssocArgs &a, unsigned long long &seq_now, bool &fired) {
+    fired = false;
     // The current sweep was swapped in when only its PREFIX had landed (srl_sweep_swap): a pass inside the prefix may fire a waiting launch;
     // anything else is launched normally BEHIND the full upload (a resident kernel cannot be made to wait for an event)
     bool needs_tail = false;
     if (ctx->tail_pending) {
         if (hipEventQuery(ctx->up_ev[ctx->cur_slot][1]) == hipSuccess) { ctx->tail_pending = false; ctx->cur_prefix_n = ctx->n; }
-        else needs_tail = n_eff > ctx->cur_prefix_n;
+        else needs_tail = a.n > ctx->cur_prefix_n;
         (void)hipGetLastError();
     }
-    bool fired = false;
-    if (ctx->armed) {
-        const SrlAssocArgs sg = signature(a);
-        const double age_us = (double)(steady_ns() - ctx->armed_at_ns) * 1e-3;
-        // which of the launch's two sweep buffers holds this pass's sweep (the one it was armed on, or -- after srl_sweep_swap -- the other)
-        // (on the buffer it was armed on the launch reads the SoA planes: they must be valid; on the other one it reads the staging buffer)
-        const bool on_raw = a.raw_x == ctx->armed_raw && ctx->sweep_cap == ctx->armed_raw_cap && a.aos == nullptr;
-        const bool on_alt = !on_raw && ctx->armed_alt != nullptr && a.raw_x == ctx->armed_alt && ctx->sweep_cap == ctx->armed_alt_cap &&
-                            a.aos != nullptr && a.aos == ctx->armed_alt_aos;
-        if (arm_ok && !needs_tail && age_us < ctx->arm_host_linger_us && nb == ctx->armed_nb && kpw == ctx->armed_kpw && nblocks <= ctx->armed_nblocks && (on_raw || on_alt) &&
-            std::memcmp(&sg, &ctx->armed_sig, sizeof sg) == 0) {
-            pose_box_write(ctx, a.Rn, a.R, a.t, (unsigned)seq_now, SRL_ARM_GO | (on_alt ? SRL_ARM_ALT : 0u), (unsigned)a.n, a.t_last);
-            ctx->armed = false;
-            ctx->armed_ring = -1;
-            ctx->arm_stats[1]++;
-            fired = true;
-        } else {
-            // not this pass's launch: cancel it.  It carried THIS pass's sequence number, and if it has already given up on its own it
-            // has left its "expired" report under that number in the mailbox -- so the pass takes the next one (a launch that
-            // reuses the number would read that report as its own result)
-            const int rcd = srl_ctx_disarm(ctx);
-            if (rcd) return rcd;
-            seq_now = ++ctx->seq;
-            if (fused) a.seq = seq_now;
-        }
-    }
-    const auto t_prep = std::chrono::steady_clock::now();
-    // Light profiling with a period P > 1 (srl_set_profiling_period): of every P association launches the second is TIMED and the first only
-    // leaves its end event as the second's start; the others carry no event at all (an event record costs ~2.5 us of the loop).
-    auto prof_role = [&](unsigned long long count) -> int {        // 2 = timed, 1 = start marker of the next launch, 0 = no events
-        if (ctx->prof_period <= 1) return 2;
-        const unsigned long long r = count % (unsigned long long)ctx->prof_period;
-        return r == 1 ? 2 : (r == 0 ? 1 : 0);
-    };
-    if (fired) {
+    if (!ctx->armed) return SRL_OK;
+    const SrlAssocArgs sg = arm_signature(a);
+    const double age_us = (double)(steady_ns() - ctx->armed_at_ns) * 1e-3;
+    // which of the launch's two sweep buffers holds this pass's sweep (the one it was armed on, or -- after srl_sweep_swap -- the other)
+    // (on the buffer it was armed on the launch reads the SoA planes: they must be valid; on the other one it reads the staging buffer)
+    const bool on_raw = a.raw_x == ctx->armed_raw && ctx->sweep_cap == ctx->armed_raw_cap && a.aos == nullptr;
+    const bool on_alt = !on_raw && ctx->armed_alt != nullptr && a.raw_x == ctx->armed_alt && ctx->sweep_cap == ctx->armed_alt_cap &&
+                        a.aos != nullptr && a.aos == ctx->armed_alt_aos;
+    if (p.arm_ok && !needs_tail && age_us < ctx->arm_host_linger_us && p.nb == ctx->armed_nb && p.kpw == ctx->armed_kpw &&
+        p.nblocks <= ctx->armed_nblocks && (on_raw || on_alt) && std::memcmp(&sg, &ctx->armed_sig, sizeof sg) == 0) {
+        pose_box_write(ctx, a.Rn, a.R, a.t, (unsigned)seq_now, SRL_ARM_GO | (on_alt ? SRL_ARM_ALT : 0u), (unsigned)a.n, a.t_last);
+        ctx->armed = false;
+        ctx->armed_ring = -1;
+        ctx->arm_stats[1]++;
         ctx->cur_measured = ctx->armed_measured;
         ctx->cur_gen = ctx->armed_gen;
-    } else {
-        if (ctx->tail_pending) {             // a normal launch reads whatever it likes of the sweep: behind the whole upload
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->up_ev[ctx->cur_slot][1], 0));
-            ctx->tail_pending = false; ctx->cur_prefix_n = ctx->n;
-        }
-        ctx->cur_gen = ctx->timing_gen;
-        const int role = prof_light ? prof_role(ctx->prof_count) : 0;
-        if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        if (role == 2) HIPCHK(ctx, hipEventRecord(ring_ev[0], ctx->stream));
-        HIPCHK(ctx, srl_launch_assoc(a, nb, kpw, wpb, ctx->stream));
-        if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-        if (role != 0) {
-            const unsigned slot = ctx->ring_head % srl_ctx::PROF_RING;
-            HIPCHK(ctx, hipEventRecord(ring_ev[1], ctx->stream));
-            ctx->ring_prev[slot] = -1; ctx->ring_marker[slot] = role == 1; ctx->ring_void[slot] = false; ctx->ring_gen[slot] = ctx->timing_gen;
-            ctx->ring_last_count = (long long)ctx->prof_count;
-            ctx->ring_head++;
-        }
-        if (prof_light) ctx->prof_count++;
-        ctx->cur_measured = !prof_light || role == 2;
-    }
-    const auto t_launched = std::chrono::steady_clock::now();
-    if (ctx->h_arm_stamps) {
-        long long *hs = ctx->arm_host_stamps[seq_now & 63ull];
-        hs[0] = std::chrono::duration_cast<std::chrono::nanoseconds>(t_entry.time_since_epoch()).count();
-        hs[1] = std::chrono::duration_cast<std::chrono::nanoseconds>(t_launched.time_since_epoch()).count();
-        hs[3] = fired ? 1 : 0;
-    }
-    // Arm only where the launch is likely to be fired (an armed launch nobody fires holds one workgroup per CU until it is cancelled or
-    // leaves by itself): not behind the pass that is expected to be the last of this solve -- the previous solve's pass count,
-    // srl_solve_end -- unless a prefetched sweep is waiting, in which case the launch becomes the first pass of THAT sweep
-    // (srl_sweep_swap); and not while another context of this process lives on the same device.  arm_mode 2: always.
-    const bool arm_wanted = ctx->arm_mode == 2 ||
-                            (live_contexts(ctx->device) <= 1 && !ctx->peer_shares_device && !ctx->comm_shares_device &&
-                             (ctx->next_n >= 0 || ctx->expected_passes == 0 || ctx->passes_in_solve + 1 < ctx->expected_passes));
-    auto arm_next = [&]() -> int {
-        // ... and arm the next pass now, while this one runs: same arguments, the sequence number this context hands out next
-        int rcp = ensure_pose_box(ctx);
-        if (rcp) return rcp;
-        SrlAssocArgs nx = a;
-        nx.seq = ctx->seq + 1;
-        nx.bound_use = a.bound_in ? a.n : 0;              // this pass writes the bounds of its a.n keypoints; the kernel drops them if fired for another sweep
-        // the context's other sweep buffer, if it exists: the launch can then be fired for the sweep srl_sweep_swap makes current
-        // (sharded ranks too: every rank prefetches and swaps its own point range, the launch learns its count with the pose)
-        const bool has_alt = ctx->d_raw_next != nullptr && ctx->next_cap > 0 && ctx->d_stage_next != nullptr;
-        nx.aos = nullptr;                                  // (its own buffer's planes are valid once this pass has run)
-        nx.alt_aos = has_alt ? ctx->d_stage_next : nullptr;
-        nx.alt_x = has_alt ? ctx->d_raw_next : nullptr;
-        nx.alt_y = has_alt ? ctx->d_raw_next + ctx->next_cap : nullptr;
-        nx.alt_z = has_alt ? ctx->d_raw_next + 2 * (size_t)ctx->next_cap : nullptr;
-        if (peer) {                                        // the exchange this launch will take part in: the one after this pass's
-            unsigned long long s2 = ctx->peer_seq + 1;
-            unsigned e2 = (unsigned)(s2 & 0xFFFFFFFFull);
-            if (e2 == 0) { ++s2; e2 = 1; }
-            nx.peer_epoch = e2;
-            nx.peer_slot = (int)(s2 & 1ull);
-        }
-        nx.pose_box = ctx->h_pose_box;                    // (host-mapped pinned memory and CPU-visible device memory: one address for both sides)
-        nx.pose_relay = ctx->d_pose_relay;
-        nx.pose_relayed = ctx->pose_box_kind == 1 ? 0 : 1;
-        nx.pose_epoch = (unsigned)nx.seq;
-        nx.arm_linger_ticks = ctx->arm_linger_ticks;
-        hipEvent_t *nev = nullptr;
-        bool own_start = true;
-        const int arole = prof_light ? prof_role(ctx->prof_count) : 0;
-        if (arole != 0) {
-            if (ctx->ring_head - ctx->ring_tail >= (unsigned)srl_ctx::PROF_RING - 2) { int rc = drain_ring(ctx, true); if (rc) return rc; }
-            nev = ctx->ring[ctx->ring_head % srl_ctx::PROF_RING];
-            // the launch before this one is the ring entry before (if it left one): its end event is the armed launch's start (an event
-            // record between the two kernels would sit on the path the armed launch is there to shorten: measured +5 us per iteration)
-            own_start = ctx->ring_head == 0 || ctx->ring_void[(ctx->ring_head - 1) % srl_ctx::PROF_RING] ||
-                        ctx->ring_last_count != (long long)ctx->prof_count - 1;
-            if (own_start && arole == 2) HIPCHK(ctx, hipEventRecord(nev[0], ctx->stream));
-        }
-        HIPCHK(ctx, srl_launch_assoc(nx, nb, kpw, wpb, ctx->stream));
-        ctx->armed_ring = -1;
-        ctx->armed_measured = !prof_light;
-        ctx->armed_gen = ctx->timing_gen;
-        if (arole != 0) {
-            HIPCHK(ctx, hipEventRecord(nev[1], ctx->stream));
-            ctx->armed_ring = (int)(ctx->ring_head % srl_ctx::PROF_RING);
-            ctx->ring_void[ctx->armed_ring] = false;
-            ctx->ring_marker[ctx->armed_ring] = arole == 1;
-            ctx->ring_gen[ctx->armed_ring] = ctx->timing_gen;
-            ctx->ring_prev[ctx->armed_ring] = own_start ? -1 : (int)((ctx->ring_head - 1) % srl_ctx::PROF_RING);
-            ctx->ring_last_count = (long long)ctx->prof_count;
-            ctx->ring_head++;
-            ctx->armed_measured = arole == 2;
-        }
-        if (prof_light) ctx->prof_count++;
-        ctx->armed_sig = signature(nx);
-        ctx->armed_nb = nb; ctx->armed_kpw = kpw; ctx->armed_nblocks = nblocks;
-        ctx->armed_raw = nx.raw_x; ctx->armed_raw_cap = ctx->sweep_cap;
-        ctx->armed_alt = nx.alt_x; ctx->armed_alt_cap = has_alt ? ctx->next_cap : 0; ctx->armed_alt_aos = nx.alt_aos;
-        ctx->armed_at_ns = steady_ns();
-        ctx->armed = true;
-        ctx->arm_stats[0]++;
+        fired = true;
         return SRL_OK;
-    };
-    if (arm_ok && arm_wanted && !coll) { const int rca = arm_next(); if (rca) return rca; }
+    }
+    if (const int rc = srl_ctx_disarm(ctx)) return rc;
+    seq_now = ++ctx->seq;
+    if (p.fused) a.seq = seq_now;
+    return SRL_OK;
+}
 
-    // residual budget of this rank (sequential early exit, optimize.cpp:107, across ordered shards)
+// Light profiling with a period P > 1 (srl_set_profiling_period): of every P association launches the second is TIMED and the first only
+// leaves its end event as the second's start; the others carry no event at all (an event record costs ~2.5 us of the loop).
+// 2 = timed, 1 = start marker of the next launch, 0 = no events
+static int prof_role(const srl_ctx *ctx) {
+    if (ctx->prof_period <= 1) return 2;
+    const unsigned long long r = ctx->prof_count % (unsigned long long)ctx->prof_period;
+    return r == 1 ? 2 : (r == 0 ? 1 : 0);
+}
+
+// Enqueue an association launch with its profiling events: the pass's own launch, or (armed) the next pass's.  Light profiling files
+// the launch's event pair in the ring; prev: the entry whose end event is the launch's start (-1: the entry's own start event).
+static int launch_assoc(srl_ctx *ctx, const PassPlan &p, const SrlAssocArgs &args, bool armed) {
+    if (!armed && ctx->tail_pending) {       // a normal launch reads whatever it likes of the sweep: behind the whole upload
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->up_ev[ctx->cur_slot][1], 0));
+        ctx->tail_pending = false; ctx->cur_prefix_n = ctx->n;
+    }
+    const bool prof = ctx->profiling == 1, prof_light = ctx->profiling == 2;
+    const int role = prof_light ? prof_role(ctx) : 0;
+    int prev = -1;
+    if (armed && role != 0) {
+        int rc;
+        if (ctx->ring_head - ctx->ring_tail >= (unsigned)srl_ctx::PROF_RING - 2 && (rc = drain_ring(ctx, true))) return rc;
+        // the launch before this one is the ring entry before (if it left one): its end event is the armed launch's start (an event
+        // record between the two kernels would sit on the path the armed launch is there to shorten: measured +5 us per iteration)
+        if (ctx->ring_head != 0 && !ctx->ring_void[(ctx->ring_head - 1) % srl_ctx::PROF_RING] && ctx->ring_last_count == (long long)ctx->prof_count - 1)
+            prev = (int)((ctx->ring_head - 1) % srl_ctx::PROF_RING);
+    }
+    const unsigned slot = ctx->ring_head % srl_ctx::PROF_RING;
+    if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (role == 2 && prev < 0) HIPCHK(ctx, hipEventRecord(ctx->ring[slot][0], ctx->stream));
+    HIPCHK(ctx, srl_launch_assoc(args, p.nb, p.kpw, p.wpb, ctx->stream));
+    if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    if (role != 0) {
+        HIPCHK(ctx, hipEventRecord(ctx->ring[slot][1], ctx->stream));
+        ctx->ring_prev[slot] = prev; ctx->ring_marker[slot] = role == 1; ctx->ring_void[slot] = false; ctx->ring_gen[slot] = ctx->timing_gen;
+        ctx->ring_last_count = (long long)ctx->prof_count;
+        ctx->ring_head++;
+    }
+    if (prof_light) ctx->prof_count++;
+    const bool measured = !prof_light || role == 2;       // one of the timed launches?
+    if (armed) { ctx->armed_ring = role != 0 ? (int)slot : -1; ctx->armed_measured = measured; ctx->armed_gen = ctx->timing_gen; }
+    else { ctx->cur_measured = measured; ctx->cur_gen = ctx->timing_gen; }
+    return SRL_OK;
+}
+
+// Arm only where the launch is likely to be fired (an armed launch nobody fires holds one workgroup per CU until it is cancelled or
+// leaves by itself): not behind the pass that is expected to be the last of this solve -- the previous solve's pass count,
+// srl_solve_end -- unless a prefetched sweep is waiting, in which case the launch becomes the first pass of THAT sweep
+// (srl_sweep_swap); and not while another context of this process lives on the same device.  arm_mode 2: always.
+static bool arm_wanted(const srl_ctx *ctx) {
+    return ctx->arm_mode == 2 ||
+           (live_contexts(ctx->device) <= 1 && !ctx->peer_shares_device && !ctx->comm_shares_device &&
+            (ctx->next_n >= 0 || ctx->expected_passes == 0 || ctx->passes_in_solve + 1 < ctx->expected_passes));
+}
+
+// Arm the next pass now, while this one runs: this pass's arguments, the sequence number this context hands out next, the pose to come
+static int arm_next(srl_ctx *ctx, const PassPlan &p, const SrlAssocArgs &a) {
+    int rc;
+    if ((rc = ensure_pose_box(ctx))) return rc;
+    SrlAssocArgs nx = a;
+    nx.seq = ctx->seq + 1;
+    nx.bound_use = a.bound_in ? a.n : 0;              // this pass writes the bounds of its a.n keypoints; the kernel drops them if fired for another sweep
+    // the context's other sweep buffer, if it exists: the launch can then be fired for the sweep srl_sweep_swap makes current
+    // (sharded ranks too: every rank prefetches and swaps its own point range, the launch learns its count with the pose)
+    const bool has_alt = ctx->d_raw_next != nullptr && ctx->next_cap > 0 && ctx->d_stage_next != nullptr;
+    nx.aos = nullptr;                                  // (its own buffer's planes are valid once this pass has run)
+    nx.alt_aos = has_alt ? ctx->d_stage_next : nullptr;
+    nx.alt_x = has_alt ? ctx->d_raw_next : nullptr;
+    nx.alt_y = has_alt ? ctx->d_raw_next + ctx->next_cap : nullptr;
+    nx.alt_z = has_alt ? ctx->d_raw_next + 2 * (size_t)ctx->next_cap : nullptr;
+    if (p.transport == Transport::peer) {             // the exchange this launch will take part in: the one after this pass's
+        const ExchangeTag t = exchange_tag(ctx->peer_seq + 1);
+        nx.peer_epoch = t.epoch;
+        nx.peer_slot = t.slot;
+    }
+    nx.pose_box = ctx->h_pose_box;                    // (host-mapped pinned memory and CPU-visible device memory: one address for both sides)
+    nx.pose_relay = ctx->d_pose_relay;
+    nx.pose_relayed = ctx->pose_box_kind == 1 ? 0 : 1;
+    nx.pose_epoch = (unsigned)nx.seq;
+    nx.arm_linger_ticks = ctx->arm_linger_ticks;
+    if ((rc = launch_assoc(ctx, p, nx, true))) return rc;
+    ctx->armed_sig = arm_signature(nx);
+    ctx->armed_nb = p.nb; ctx->armed_kpw = p.kpw; ctx->armed_nblocks = p.nblocks;
+    ctx->armed_raw = nx.raw_x; ctx->armed_raw_cap = ctx->sweep_cap;
+    ctx->armed_alt = nx.alt_x; ctx->armed_alt_cap = has_alt ? ctx->next_cap : 0; ctx->armed_alt_aos = nx.alt_aos;
+    ctx->armed_at_ns = steady_ns();
+    ctx->armed = true;
+    ctx->arm_stats[0]++;
+    return SRL_OK;
+}
+
+// An unfused pass: the rank's residual budget (sequential early exit, optimize.cpp:107, across ordered shards), the reduce kernel, and
+// with peers the exchange of its row.  A sharded pass that the ordered cut may end exchanges the per-rank counts first (accepted
+// residuals; keypoints with a plane when max_num_residuals <= 0): the reduce kernel derives budget and mode from them itself.
+static int reduce_unfused(srl_ctx *ctx, const PassPlan &p, const srl_icp_opts *o, int n_eff, unsigned long long seq) {
     int64_t budget = o->max_num_residuals;
     int mode = 0;
-    const bool multi = ctx->nranks > 1 || coll;
-    // the ordered cut can only trigger when max_num_residuals <= number of keypoints: otherwise no exchange of counts.
-    // max_num_residuals <= 0: the loop stops at the first keypoint with a plane, wherever (in whichever shard) that is.
-    const bool cut_possible = o->max_num_residuals <= 0 || (long long)o->max_num_residuals <= (long long)ctx->total_n;
-    const long long *gather_dev = nullptr;
-    if (!multi || !cut_possible) {
+    const long long *gather = nullptr;
+    if (p.transport == Transport::single || !p.cut) {
         srl_shard_budget(o->max_num_residuals, nullptr, ctx->nranks, ctx->rank, &budget, &mode);
     } else {
-        // per-rank counts (accepted residuals; keypoints with a plane when max_num_residuals <= 0)
-        HIPCHK(ctx, srl_launch_count(ctx->d_binfo, nblocks, o->max_num_residuals <= 0 ? 1 : 0, ctx->d_count, ctx->stream));
-        if (peer) {
+        HIPCHK(ctx, srl_launch_count(ctx->d_binfo, p.nblocks, o->max_num_residuals <= 0 ? 1 : 0, ctx->d_count, ctx->stream));
+        if (p.transport == Transport::peer) {
             // the counts travel like the rows: every rank stores its word into every inbox, one wave collects them
-            next_exchange();
-            HIPCHK(ctx, srl_launch_peer_counts(ctx->d_peer, peer_epoch, peer_slot, ctx->d_count, ctx->d_gather, ctx->stream));
-            gather_dev = ctx->d_gather;
-        } else if (coll) {
-            // gathered on the stream; the reduce kernel derives its budget and mode from the counts of earlier ranks
-            // itself -- no D2H copy, no host synchronisation in the loop
+            const ExchangeTag t = next_exchange(ctx);
+            HIPCHK(ctx, srl_launch_peer_counts(ctx->d_peer, t.epoch, t.slot, ctx->d_count, ctx->d_gather, ctx->stream));
+            gather = ctx->d_gather;
+        } else if (p.transport == Transport::rccl) {
+            // gathered on the stream -- no D2H copy, no host synchronisation in the loop
             NCCLCHK(ctx, AllGather(ctx->d_count, ctx->d_gather, 1, ncclInt64, ctx->comm, ctx->stream));
-            gather_dev = ctx->d_gather;
-        } else if (ctx->dbg_gather) {
+            gather = ctx->d_gather;
+        } else if (p.dbg_gather) {
             // srl_debug_set_gather_counts: the counts of the other ranks are already in d_gather -- the reduce kernel derives
             // budget and mode from them exactly as behind a real all-gather (test hook for rank > 0 on a single GPU)
-            gather_dev = ctx->d_gather;
+            gather = ctx->d_gather;
         } else {
             HIPCHK(ctx, hipMemcpyAsync(ctx->h_count, ctx->d_count, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1253,146 +1232,137 @@ static int build_residuals_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_
             srl_shard_budget(o->max_num_residuals, all64.data(), ctx->nranks, ctx->rank, &budget, &mode);
         }
     }
-
     SrlReduceArgs ra;
     ra.rec = ctx->d_rec;
     ra.status = ctx->d_status;
     ra.partials = ctx->d_partials;
     ra.binfo = ctx->d_binfo;
     ra.n = n_eff;
-    ra.kpb = kpb;
-    ra.nblocks = nblocks;
+    ra.kpb = p.kpb;
+    ra.nblocks = p.nblocks;
     ra.max_res = budget;
-    ra.gather = gather_dev;
+    ra.gather = gather;
     ra.rank = ctx->rank;
     ra.max_num_residuals = o->max_num_residuals;
     ra.out = ctx->d_out;
-    // single rank: the reduce kernel publishes straight into host-mapped memory and the host spins on the
-    // sequence word -- no D2H copy, no stream synchronisation on the per-iteration critical path
-    // (a fused pass of a sharded sweep without RCCL / peers also ends in the host mailbox: the callback all-reduce follows it)
-    const bool mailbox = ((ctx->nranks == 1) && !coll) || (fused && !coll);
-    ra.mailbox = (mailbox && !fused) ? ctx->h_mail : nullptr;
-    ra.seq = seq_now;
-    if (!fused) {
-        HIPCHK(ctx, srl_launch_reduce(ra, mode, ctx->stream));
-        if (peer) {
-            next_exchange();
-            HIPCHK(ctx, srl_launch_peer_rows(ctx->d_peer, peer_epoch, peer_slot, ctx->d_out, ctx->h_mail, seq_now, gather_dev, ctx->stream));
-        }
+    ra.mailbox = p.mailbox ? ctx->h_mail : nullptr;
+    ra.seq = seq;
+    HIPCHK(ctx, srl_launch_reduce(ra, mode, ctx->stream));
+    if (p.transport == Transport::peer) {
+        const ExchangeTag t = next_exchange(ctx);
+        HIPCHK(ctx, srl_launch_peer_rows(ctx->d_peer, t.epoch, t.slot, ctx->d_out, ctx->h_mail, seq, gather, ctx->stream));
     }
-    if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    const auto t_enq = std::chrono::steady_clock::now();
-    // everything is enqueued: the caller's H-independent host work runs now, beside the kernels (srl_build_residuals_overlap)
-    if (ctx->overlap_fn) {
-        void (*fn)(void *) = ctx->overlap_fn;
-        ctx->overlap_fn = nullptr;                 // once per call, in the first pass
-        fn(ctx->overlap_user);
-    }
+    return SRL_OK;
+}
 
-    // the one exchange step: sum of the normal equations over the point-range shards
-    const int n_red = SRL_REDUCED_DOUBLES;   // HtH, Hth, loss, 6 counters carried as doubles (incl. visited keypoints), fused time-out flag
-    long long visited_local = 0;
-    if (coll) {
-        // one ncclAllReduce of 50 doubles on the context's stream; last_visited sits behind the reduced range
-        SrlDevOut *mine = fused ? &ctx->d_mail->out : ctx->d_out;
-        NCCLCHK(ctx, AllReduce(mine, mine, n_red, ncclDouble, ncclSum, ctx->comm, ctx->stream));
-        HIPCHK(ctx, srl_launch_publish(mine, ctx->h_mail, ra.seq, ctx->stream));
-        if (arm_ok && arm_wanted) { const int rca = arm_next(); if (rca) return rca; }       // (behind the collective: see arm_ok)
-    }
-    const bool host_reduce = ctx->nranks > 1 && !coll && !peer;      // the caller's all-reduce callback (CPU / gloo tests, foreign transports)
-    if (coll || mailbox || peer) {
-        constexpr int NW = (int)(sizeof(SrlDevOut) / 8);
-        const unsigned tag32 = (unsigned)ra.seq;
-        unsigned long long *gran = ctx->h_mail->g;
-        // arrived: the plain form's sequence word; the tagged form: every granule carries this pass's tag (the last one is looked at
-        // first: while it is stale nothing else is read)
-        auto arrived = [&]() -> bool {
-            if (!tagged_mail) return __atomic_load_n(&ctx->h_mail->seq, __ATOMIC_ACQUIRE) == ra.seq;
-            if ((unsigned)(__atomic_load_n(&gran[2 * NW - 1], __ATOMIC_RELAXED) >> 32) != tag32) return false;
-            for (int i = 0; i < 2 * NW - 1; i++) if ((unsigned)(__atomic_load_n(&gran[i], __ATOMIC_RELAXED) >> 32) != tag32) return false;
-            return true;
-        };
-        unsigned long long spins = 0;
-        bool arm_expired = false;
-        while (!arrived()) {
-            if (fired && __atomic_load_n(&ctx->h_mail->expired, __ATOMIC_ACQUIRE) == ra.seq) { arm_expired = true; break; }   // the launch this pass fired had left
-            if ((++spins & 0xFFFFF) == 0) {           // every ~1M polls: make sure the stream has not faulted
-                const hipError_t qe = hipStreamQuery(ctx->stream);
-                if (qe != hipSuccess && qe != hipErrorNotReady) { ctx->err = std::string("reduce kernel: ") + hipGetErrorString(qe); return SRL_ERR_HIP; }
-                if (qe == hipSuccess && !arrived()) {
-                    char dbg[256];
-                    int bad = -1; unsigned bad_tag = 0;
-                    if (tagged_mail) for (int i = 0; i < 2 * NW; i++) if ((unsigned)(gran[i] >> 32) != tag32) { bad = i; bad_tag = (unsigned)(gran[i] >> 32); break; }
-                    std::snprintf(dbg, sizeof dbg, "reduce kernel finished without publishing (seq %llu, tagged %d, fired %d, fused %d, blocks %d, first stale granule %d tag %u, plain seq %llu)",
-                                  (unsigned long long)ra.seq, (int)tagged_mail, (int)fired, (int)fused, nblocks, bad, bad_tag, (unsigned long long)ctx->h_mail->seq);
-                    ctx->err = dbg;
-                    return SRL_ERR_HIP;
-                }
-            }
-        }
-        if (arm_expired) {
+// the caller's all-reduce callback over the reduced range of `out` (host_callback transport: CPU / gloo tests, foreign transports)
+static int host_allreduce(srl_ctx *ctx, SrlDevOut *out) {
+    if (!ctx->cb_ar) { ctx->err = "nranks > 1 without communicator"; return SRL_ERR_COMM; }
+    if (ctx->cb_ar(reinterpret_cast<double *>(out), SRL_REDUCED_DOUBLES, ctx->cb_user) != 0) { ctx->err = "allreduce callback failed"; return SRL_ERR_COMM; }
+    return SRL_OK;
+}
+
+// Has the result of pass `seq` arrived in the host mailbox?  The plain form: its sequence word.  The tagged form: every granule carries
+// the pass's tag (the last one is looked at first: while it is stale nothing else is read).
+static constexpr int OUT_WORDS = (int)(sizeof(SrlDevOut) / 8);
+static bool mail_arrived(const srl_ctx *ctx, bool tagged, unsigned long long seq) {
+    if (!tagged) return __atomic_load_n(&ctx->h_mail->seq, __ATOMIC_ACQUIRE) == seq;
+    const unsigned long long *gran = ctx->h_mail->g;
+    const unsigned tag32 = (unsigned)seq;
+    if ((unsigned)(__atomic_load_n(&gran[2 * OUT_WORDS - 1], __ATOMIC_RELAXED) >> 32) != tag32) return false;
+    for (int i = 0; i < 2 * OUT_WORDS - 1; i++) if ((unsigned)(__atomic_load_n(&gran[i], __ATOMIC_RELAXED) >> 32) != tag32) return false;
+    return true;
+}
+
+// spin until the result of pass `seq` is in the host mailbox (or the launch it fired has left, or the stream has faulted); copy it to h_out
+static int read_mailbox(srl_ctx *ctx, const PassPlan &p, unsigned long long seq, bool fired) {
+    unsigned long long spins = 0;
+    while (!mail_arrived(ctx, p.tagged_mail, seq)) {
+        if (fired && __atomic_load_n(&ctx->h_mail->expired, __ATOMIC_ACQUIRE) == seq) {   // the launch this pass fired had left
             ctx->arm_stats[3]++;
             ctx->err = "armed launch expired";
             return SRL_INTERNAL_ARM_EXPIRED;
         }
-        if (tagged_mail) {
-            unsigned long long *w = reinterpret_cast<unsigned long long *>(ctx->h_out);
-            for (int i = 0; i < NW; i++)
-                w[i] = (__atomic_load_n(&gran[2 * i], __ATOMIC_RELAXED) & 0xFFFFFFFFull) | (__atomic_load_n(&gran[2 * i + 1], __ATOMIC_RELAXED) << 32);
-        } else {
-            std::memcpy(ctx->h_out, &ctx->h_mail->out, sizeof(SrlDevOut));
-        }
-        visited_local = ctx->h_out->last_visited + 1;
-        if (host_reduce) {
-            if (!ctx->cb_ar) { ctx->err = "nranks > 1 without communicator"; return SRL_ERR_COMM; }
-            if (ctx->cb_ar(reinterpret_cast<double *>(ctx->h_out), n_red, ctx->cb_user) != 0) { ctx->err = "allreduce callback failed"; return SRL_ERR_COMM; }
-        }
-        if (ctx->h_out->pad == SRL_PEER_TIMEOUT_MARK) {
-            // A rank's row had not arrived when the kernel's bounded spin ran out (~0.3-1 s: a kernel must not hold the GPU for ever).  Whether
-            // that rank is late or gone is not decided in the kernel: srl_build_residuals repeats the pass with the SAME exchange tags until
-            // the wall-clock deadline of srl_peer_set_deadline_ms, then gives the session up for every rank (peer_pass_timed_out below).
-            ctx->err = "direct peer exchange: a rank's row has not arrived yet";
-            return SRL_INTERNAL_PEER_TIMEOUT;
-        }
-        if (ctx->h_out->pad != 0 || ctx->h_out->d_timeout > 0.5) {     // (summed over the ranks: all of them repeat the pass together)
-            // the finishing workgroup gave up waiting for a row (bounded spin: another process holding compute units back, a
-            // preempted queue): not an error of the data -- the caller repeats the pass with the reduction in its own kernel
-            ctx->err = "fused final reduction timed out waiting for a workgroup's row";
-            if (fired && coll) ctx->arm_stats[3]++;      // (RCCL form: this is how a fired launch that had given up shows -- its record carries the flag)
-            return SRL_INTERNAL_FUSED_TIMEOUT;
-        }
-    } else {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, sizeof(SrlDevOut), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        visited_local = ctx->h_out->last_visited + 1;
-        if (ctx->nranks > 1) {
-            if (!ctx->cb_ar) { ctx->err = "nranks > 1 without communicator"; return SRL_ERR_COMM; }
-            if (ctx->cb_ar(reinterpret_cast<double *>(ctx->h_out), n_red, ctx->cb_user) != 0) { ctx->err = "allreduce callback failed"; return SRL_ERR_COMM; }
-            // another rank's fused pass timed out (its flag is part of the sum): this rank repeats the pass with it
-            if (ctx->h_out->d_timeout > 0.5) { ctx->err = "fused final reduction timed out on another rank"; return SRL_INTERNAL_FUSED_TIMEOUT; }
+        if ((++spins & 0xFFFFF) == 0) {           // every ~1M polls: make sure the stream has not faulted
+            const hipError_t qe = hipStreamQuery(ctx->stream);
+            if (qe != hipSuccess && qe != hipErrorNotReady) { ctx->err = std::string("reduce kernel: ") + hipGetErrorString(qe); return SRL_ERR_HIP; }
+            if (qe == hipSuccess && !mail_arrived(ctx, p.tagged_mail, seq)) {
+                const unsigned long long *gran = ctx->h_mail->g;
+                char dbg[256];
+                int bad = -1; unsigned bad_tag = 0;
+                if (p.tagged_mail) for (int i = 0; i < 2 * OUT_WORDS; i++) if ((unsigned)(gran[i] >> 32) != (unsigned)seq) { bad = i; bad_tag = (unsigned)(gran[i] >> 32); break; }
+                std::snprintf(dbg, sizeof dbg, "reduce kernel finished without publishing (seq %llu, tagged %d, fired %d, fused %d, blocks %d, first stale granule %d tag %u, plain seq %llu)",
+                              seq, (int)p.tagged_mail, (int)fired, (int)p.fused, p.nblocks, bad, bad_tag, (unsigned long long)ctx->h_mail->seq);
+                ctx->err = dbg;
+                return SRL_ERR_HIP;
+            }
         }
     }
-    if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    const auto t_res = std::chrono::steady_clock::now();
-    if (ctx->armed) ctx->armed_at_ns = steady_ns();      // the armed launch starts waiting about now (when this pass ends): its age counts from here
-    if (ctx->h_arm_stamps) ctx->arm_host_stamps[seq_now & 63ull][2] = std::chrono::duration_cast<std::chrono::nanoseconds>(t_res.time_since_epoch()).count();
+    if (p.tagged_mail) {
+        const unsigned long long *gran = ctx->h_mail->g;
+        unsigned long long *w = reinterpret_cast<unsigned long long *>(ctx->h_out);
+        for (int i = 0; i < OUT_WORDS; i++)
+            w[i] = (__atomic_load_n(&gran[2 * i], __ATOMIC_RELAXED) & 0xFFFFFFFFull) | (__atomic_load_n(&gran[2 * i + 1], __ATOMIC_RELAXED) << 32);
+    } else {
+        std::memcpy(ctx->h_out, &ctx->h_mail->out, sizeof(SrlDevOut));
+    }
+    return SRL_OK;
+}
 
+// Wait for the pass's (reduced) result in ctx->h_out.  last_visited_local: this rank's last visited keypoint, read before any reduction.
+static int wait_result(srl_ctx *ctx, const PassPlan &p, unsigned long long seq, bool fired, long long &last_visited_local) {
+    // every pass but an unfused one of the callback transport ends in the host mailbox: the reduce kernel's, the fused finisher's, the
+    // peer rows' or the publish kernel's behind RCCL
+    const bool copied = p.transport == Transport::host_callback && !p.fused;
+    int rc;
+    if (copied) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, sizeof(SrlDevOut), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    } else if ((rc = read_mailbox(ctx, p, seq, fired))) {
+        return rc;
+    }
+    last_visited_local = ctx->h_out->last_visited;
+    if (p.transport == Transport::host_callback && (rc = host_allreduce(ctx, ctx->h_out))) return rc;
+    if (copied) {
+        // another rank's fused pass timed out (its flag is part of the sum): this rank repeats the pass with it
+        if (ctx->h_out->d_timeout > 0.5) { ctx->err = "fused final reduction timed out on another rank"; return SRL_INTERNAL_FUSED_TIMEOUT; }
+        return SRL_OK;
+    }
+    if (ctx->h_out->pad == SRL_PEER_TIMEOUT_MARK) {
+        // A rank's row had not arrived when the kernel's bounded spin ran out (~0.3-1 s: a kernel must not hold the GPU for ever).  Whether
+        // that rank is late or gone is not decided in the kernel: srl_build_residuals repeats the pass with the SAME exchange tags until
+        // the wall-clock deadline of srl_peer_set_deadline_ms, then gives the session up for every rank.
+        ctx->err = "direct peer exchange: a rank's row has not arrived yet";
+        return SRL_INTERNAL_PEER_TIMEOUT;
+    }
+    if (ctx->h_out->pad != 0 || ctx->h_out->d_timeout > 0.5) {     // (summed over the ranks: all of them repeat the pass together)
+        // the finishing workgroup gave up waiting for a row (bounded spin: another process holding compute units back, a
+        // preempted queue): not an error of the data -- the caller repeats the pass with the reduction in its own kernel
+        ctx->err = "fused final reduction timed out waiting for a workgroup's row";
+        if (fired && p.transport == Transport::rccl) ctx->arm_stats[3]++;      // (RCCL form: this is how a fired launch that had given up shows -- its record carries the flag)
+        return SRL_INTERNAL_FUSED_TIMEOUT;
+    }
+    return SRL_OK;
+}
+
+// the normal equations of the pass, and what the context remembers of it
+static int finish_pass(srl_ctx *ctx, const PassPlan &p, const srl_icp_opts *o, const SrlAssocArgs &a, int n_eff, long long last_visited_local,
+                       unsigned long long seq, bool fired, srl_normal_eq *out) {
+    const SrlDevOut &r = *ctx->h_out;
     // total visited keypoints over all shards (part of the reduced range) -> global index of the last visited one
-    const long long visited_total = (long long)(ctx->h_out->d_visited + 0.5);
-    if (fused && !can_fuse_cut) {
+    const long long visited_total = (long long)(r.d_visited + 0.5);
+    if (p.fused && !p.fuse_cut) {
         // a fused pass without a cut visits every keypoint it was given, on every rank: anything else means workgroups ran on another
         // keypoint count than the host fired them with (a relayed pose box once lost the count of a swapped-in sweep)
         const long long expect = ctx->nranks > 1 ? (long long)ctx->total_n : (long long)n_eff;
         if (visited_total != expect) {
             char buf[256];
             std::snprintf(buf, sizeof buf, "fused pass visited %lld of %lld keypoints (fired %d, seq %llu; residuals %.0f, time-out flag %.0f, marker %lld)", visited_total, expect,
-                          (int)fired, (unsigned long long)seq_now, ctx->h_out->d_num_res, ctx->h_out->d_timeout, (long long)ctx->h_out->pad);
+                          (int)fired, seq, r.d_num_res, r.d_timeout, (long long)r.pad);
             ctx->err = buf;
             return SRL_ERR_HIP;
         }
     }
-
-    const SrlDevOut &r = *ctx->h_out;
     std::memcpy(out->HtH, r.HtH, sizeof out->HtH);
     std::memcpy(out->Hth, r.Hth, sizeof out->Hth);
     out->loss_sum = r.loss;
@@ -1405,11 +1375,25 @@ static int build_residuals_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_
 
     if (a.aos != nullptr && n_eff > ctx->soa_valid_n) ctx->soa_valid_n = n_eff;      // this pass filed the SoA planes of its keypoints
     ctx->bound_n = n_eff;                                                            // ... and the bounds of its keypoints (entries behind them: an earlier, shorter or longer pass -- never read)
-    ctx->last_K = K;
-    ctx->last_nb = nb;
-    ctx->last_visited_local = visited_local - 1;
+    ctx->last_K = p.K;
+    ctx->last_nb = p.nb;
+    ctx->last_visited_local = last_visited_local;
     ctx->taps_valid = ctx->taps;
+    return SRL_OK;
+}
 
+// host clock of one pass: entry, arguments prepared, launched (or fired), everything enqueued, result read
+struct PassClock { std::chrono::steady_clock::time_point entry, prep, launched, enq, res; };
+
+static long long clock_ns(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration_cast<std::chrono::nanoseconds>(t.time_since_epoch()).count();
+}
+
+// timing and algorithmic bytes of the pass (profiling 1: events around every stage; 2: the ring's launches; 3: host stamps only)
+static int account_pass(srl_ctx *ctx, const PassPlan &p, int n_eff, const PassClock &c) {
+    using us = std::chrono::duration<double, std::micro>;
+    using ms = std::chrono::duration<double, std::milli>;
+    const bool prof = ctx->profiling == 1, prof_light = ctx->profiling == 2;
     if (prof) {
         HIPCHK(ctx, hipEventSynchronize(ctx->ev[3]));
         hipEventElapsedTime(&ctx->timing.assoc_ms, ctx->ev[0], ctx->ev[1]);
@@ -1421,31 +1405,85 @@ static int build_residuals_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_
         ctx->timing.sum_total_ms += ctx->timing.total_ms;
         ctx->timing.sum_keypoints += n_eff;
         const auto t_end = std::chrono::steady_clock::now();
-        ctx->timing.sum_host_launch_us += std::chrono::duration<double, std::micro>(t_enq - t_entry).count();
-        ctx->timing.sum_host_wait_us += std::chrono::duration<double, std::micro>(t_res - t_enq).count();
-        ctx->timing.sum_host_total_us += std::chrono::duration<double, std::micro>(t_end - t_entry).count();
+        ctx->timing.sum_host_launch_us += us(c.enq - c.entry).count();
+        ctx->timing.sum_host_wait_us += us(c.res - c.enq).count();
+        ctx->timing.sum_host_total_us += us(t_end - c.entry).count();
     }
-    {
-        // algorithmic bytes of this rank's association pass: 24 + 12*(2r+1)^3 + 12*P_k per keypoint.
-        // sum_pk in h_out is the all-reduced value; the per-rank value is recomputed from the ratio when sharded.
-        const long long side = 2 * nb + 1;
-        const long long per_kp = 24 + 12 * side * side * side;
-        const double pk_share = (ctx->nranks > 1 && ctx->total_n > 0) ? r.d_sum_pk * ((double)ctx->n / (double)ctx->total_n) : r.d_sum_pk;
-        ctx->timing.algorithmic_bytes = per_kp * (long long)n_eff + (long long)(12.0 * pk_share);
-        // (light profiling with a period: only the passes whose launch is one of the timed ones count, so bytes and durations pair up)
-        if (prof || (prof_light && ctx->cur_measured && ctx->cur_gen == ctx->timing_gen)) {
-            ctx->timing.sum_algorithmic_bytes += ctx->timing.algorithmic_bytes; ctx->timing.sum_keypoints += prof_light ? n_eff : 0; ctx->timing.sum_passes += 1;
-        }
+    // algorithmic bytes of this rank's association pass: 24 + 12*(2r+1)^3 + 12*P_k per keypoint.
+    // sum_pk in h_out is the all-reduced value; the per-rank value is recomputed from the ratio when sharded.
+    const double sum_pk = ctx->h_out->d_sum_pk;
+    const long long side = 2 * p.nb + 1;
+    const long long per_kp = 24 + 12 * side * side * side;
+    const double pk_share = (ctx->nranks > 1 && ctx->total_n > 0) ? sum_pk * ((double)ctx->n / (double)ctx->total_n) : sum_pk;
+    ctx->timing.algorithmic_bytes = per_kp * (long long)n_eff + (long long)(12.0 * pk_share);
+    // (light profiling with a period: only the passes whose launch is one of the timed ones count, so bytes and durations pair up)
+    if (prof || (prof_light && ctx->cur_measured && ctx->cur_gen == ctx->timing_gen)) {
+        ctx->timing.sum_algorithmic_bytes += ctx->timing.algorithmic_bytes; ctx->timing.sum_keypoints += prof_light ? n_eff : 0; ctx->timing.sum_passes += 1;
     }
     if (ctx->profiling == 3) {
         // host stamps only (no events): argument preparation, the launch call itself, the wait for the result
         ctx->timing.calls += 1;
-        ctx->timing.sum_host_launch_us += std::chrono::duration<double, std::micro>(t_launched - t_prep).count();
-        ctx->timing.sum_host_wait_us += std::chrono::duration<double, std::micro>(t_res - t_enq).count();
-        ctx->timing.sum_host_total_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_entry).count();
-        ctx->timing.sum_assoc_ms += std::chrono::duration<double, std::milli>(t_prep - t_entry).count();      // argument preparation (ms)
-        ctx->timing.sum_reduce_ms += std::chrono::duration<double, std::milli>(t_enq - t_launched).count();  // launch returned -> everything enqueued + overlap callback (ms)
+        ctx->timing.sum_host_launch_us += us(c.launched - c.prep).count();
+        ctx->timing.sum_host_wait_us += us(c.res - c.enq).count();
+        ctx->timing.sum_host_total_us += us(std::chrono::steady_clock::now() - c.entry).count();
+        ctx->timing.sum_assoc_ms += ms(c.prep - c.entry).count();      // argument preparation (ms)
+        ctx->timing.sum_reduce_ms += ms(c.enq - c.launched).count();   // launch returned -> everything enqueued + overlap callback (ms)
     }
+    return SRL_OK;
+}
+
+static int build_residuals_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, srl_normal_eq *out, int n_eff) {
+    PassClock clk{std::chrono::steady_clock::now()};
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PassPlan p;
+    int rc;
+    if ((rc = plan_pass(ctx, f, o, n_eff, p))) return rc;
+    if ((rc = grow_pass_buffers(ctx, p))) return rc;
+    SrlAssocArgs a;
+    prepare_assoc_args(ctx, f, o, n_eff, p, a);
+    unsigned long long seq_now = ++ctx->seq;          // (a cancelled armed launch takes this number with it: fire_or_cancel)
+    if (p.transport == Transport::peer && ctx->peer_failed) {
+        ctx->err = "direct peer exchange: this session has failed (a rank's row never arrived); srl_peer_detach, srl_peer_export and srl_peer_attach on every rank start a new one";
+        return SRL_ERR_COMM;
+    }
+    if (p.fused) a.seq = seq_now;
+    if (p.fused && p.transport == Transport::peer) {  // a fused pass is one exchange: its tag is taken before the next pass is armed
+        const ExchangeTag t = next_exchange(ctx);
+        a.peer = ctx->d_peer; a.peer_epoch = t.epoch; a.peer_slot = t.slot;
+    }
+    bool fired = false;
+    if ((rc = fire_or_cancel(ctx, p, a, seq_now, fired))) return rc;
+    clk.prep = std::chrono::steady_clock::now();
+    if (!fired && (rc = launch_assoc(ctx, p, a, false))) return rc;
+    clk.launched = std::chrono::steady_clock::now();
+    long long *stamps = ctx->h_arm_stamps ? ctx->arm_host_stamps[seq_now & 63ull] : nullptr;
+    if (stamps) { stamps[0] = clock_ns(clk.entry); stamps[1] = clock_ns(clk.launched); stamps[3] = fired ? 1 : 0; }
+    // the next pass is armed behind this one -- with RCCL behind the all-reduce and the publish kernel
+    const bool arm = p.arm_ok && arm_wanted(ctx);
+    if (arm && p.transport != Transport::rccl && (rc = arm_next(ctx, p, a))) return rc;
+    if (!p.fused && (rc = reduce_unfused(ctx, p, o, n_eff, seq_now))) return rc;
+    if (ctx->profiling == 1) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    clk.enq = std::chrono::steady_clock::now();
+    // everything is enqueued: the caller's H-independent host work runs now, beside the kernels (srl_build_residuals_overlap)
+    if (ctx->overlap_fn) {
+        void (*fn)(void *) = ctx->overlap_fn;
+        ctx->overlap_fn = nullptr;                 // once per call, in the first pass
+        fn(ctx->overlap_user);
+    }
+    if (p.transport == Transport::rccl) {         // one ncclAllReduce of the reduced range (last_visited sits behind it), the publish kernel
+        SrlDevOut *mine = p.fused ? &ctx->d_mail->out : ctx->d_out;
+        NCCLCHK(ctx, AllReduce(mine, mine, SRL_REDUCED_DOUBLES, ncclDouble, ncclSum, ctx->comm, ctx->stream));
+        HIPCHK(ctx, srl_launch_publish(mine, ctx->h_mail, seq_now, ctx->stream));
+        if (arm && (rc = arm_next(ctx, p, a))) return rc;
+    }
+    long long last_visited_local = -1;
+    if ((rc = wait_result(ctx, p, seq_now, fired, last_visited_local))) return rc;
+    if (ctx->profiling == 1) HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    clk.res = std::chrono::steady_clock::now();
+    if (ctx->armed) ctx->armed_at_ns = steady_ns();      // the armed launch starts waiting about now (when this pass ends): its age counts from here
+    if (stamps) stamps[2] = clock_ns(clk.res);
+    if ((rc = finish_pass(ctx, p, o, a, n_eff, last_visited_local, seq_now, fired, out))) return rc;
+    if ((rc = account_pass(ctx, p, n_eff, clk))) return rc;
     if (out->nan_error) { ctx->err = "NaN planarity"; return SRL_ERR_NAN_PLANARITY; }
     return SRL_OK;
 }
@@ -1669,8 +1707,7 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
     // same cut as the full pass; the sums agree up to FP64 summation order (a short pass uses fewer keypoints per
     // workgroup, srl_keypoints_per_block).  Taps keep the full pass.
     int n_eff = ctx->n;
-    const bool single = ctx->nranks == 1 && !(ctx->comm && ctx->force_coll);
-    if (single && !ctx->taps && o->max_num_residuals > 0) {
+    if (pass_transport(ctx) == Transport::single && !ctx->taps && o->max_num_residuals > 0) {
         const long long pre = ((4LL * o->max_num_residuals + 2048 + 63) / 64) * 64;
         if (pre < (long long)ctx->n) n_eff = (int)pre;
     }
@@ -1928,7 +1965,7 @@ int srl_peer_detach(srl_ctx *ctx) {
 int srl_peer_attach(srl_ctx *ctx, int nranks, int rank, const void *ipc_handles, void *const *local_ptrs) {
     if (!ctx || nranks < 1 || nranks > SRL_MAX_PEERS || rank < 0 || rank >= nranks || (nranks > 1 && !ipc_handles && !local_ptrs)) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);
-    if (ctx->comm || ctx->cb_ar) { ctx->err = "srl_peer_attach: another transport is attached (srl_comm_destroy first)"; return SRL_ERR_BAD_ARG; }
+    if (ctx->comm || ctx->parked_comm || ctx->cb_ar) { ctx->err = "srl_peer_attach: another transport is attached (srl_comm_destroy first)"; return SRL_ERR_BAD_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_inbox) { ctx->err = "srl_peer_attach: srl_peer_export first (it creates and resets this rank's inbox)"; return SRL_ERR_BAD_ARG; }
     { const int rcd = srl_peer_detach(ctx); if (rcd) return rcd; }

@@ -104,6 +104,14 @@ int srl_map_insert(srl_ctx *ctx, const double *world_xyz, int n, double voxel_si
 int srl_map_size(srl_ctx *ctx, int64_t *num_points, int32_t *num_voxels);
 /* copies the device map back in creation order (same layout as srl_map_upload) */
 int srl_map_download(srl_ctx *ctx, int16_t *keys_xyz, int32_t *counts, float *xyz, int max_voxels);
+/* replaces lioOptimization::removePointsFarFromLocation (lioOptimization.cpp:556-572): erases every voxel whose FIRST stored point
+ * (slot 0, FP32) p0 satisfies ((dx*dx + dy*dy) + dz*dz) > distance*distance with d = (double)p0 - location, all FP64 (a negative distance
+ * acts like its absolute value; +inf or a NaN distance / location erases nothing).  The survivors are RENUMBERED: slab index = rank
+ * among the surviving voxels in creation order (point id = slab * 20 + slot, as on a map rebuilt from them), and voxels created later
+ * go behind them; a key that was erased and is hit again by an insert becomes a new voxel at the end.  Cancels an armed launch, folds a
+ * deferred insert in first, voids the neighbourhood bounds and the taps of the last pass, and waits for the device once (the counts).
+ * No map, or an empty one: SRL_OK with nothing removed.  Both counts are optional. */
+int srl_map_remove_far(srl_ctx *ctx, const double location[3], double distance, int32_t *num_voxels_removed, int64_t *num_points_removed);
 /* A cheap fingerprint of the part of the map a set of points falls into -- what a caller that keeps a map of its OWN (the node's
  * tsl::robin_map, lioOptimization.h:274) compares frame by frame instead of walking both maps: for every point the voxel it belongs to
  * (key = short(float(p) / voxel_size), lioOptimization.cpp:403-405) contributes srl_probe_mix(key, points in the voxel, position of the

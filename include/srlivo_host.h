@@ -48,6 +48,11 @@ int srl_lio_eskf_observe(srl_lio *lio, const double dx[17]);
 int srl_lio_add_points_to_map(srl_lio *lio, const double *world_xyz, int n, double voxel_size,
                               int max_num_points_in_voxel, double min_distance_points, int min_num_points);
 int srl_lio_map_size(srl_lio *lio, int64_t *num_points);
+/* lioOptimization::removePointsFarFromLocation (lioOptimization.cpp:556-572) on the device map: srl_map_remove_far.  The reference
+ * calls it right after addPointsToMap in stateEstimation (lioOptimization.cpp:1032, commented out in the shipped node); a caller of
+ * srl_lio_run_measurement does the same with srl_lio_remove_points_far_from_location(lio, result.state + 4, max_distance) after every
+ * processed, successful measurement. */
+int srl_lio_remove_points_far_from_location(srl_lio *lio, const double location[3], double distance);
 /* srl_map_probe_checksum over the world points the last srl_lio_commit_frame left in HBM (the frame the node inserts next) */
 int srl_lio_probe_checksum_of_committed_frame(srl_lio *lio, int stride, double voxel_size, uint64_t *checksum, int32_t *num_voxels);
 

@@ -115,6 +115,7 @@ def load_library():
         "srl_map_insert": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_map_size": ([p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
         "srl_map_download": ([p, p, p, p, C.c_int], C.c_int),
+        "srl_map_remove_far": ([p, dp, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64)], C.c_int),
         "srl_map_probe_checksum": ([p, p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_uint64)], C.c_int),
         "srl_sweep_upload": ([p, p, C.c_int], C.c_int),
         "srl_sweep_shard": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
@@ -199,6 +200,7 @@ def load_library():
         "srl_lio_eskf_observe": ([p, dp], C.c_int),
         "srl_lio_add_points_to_map": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
         "srl_lio_map_size": ([p, C.POINTER(C.c_int64)], C.c_int),
+        "srl_lio_remove_points_far_from_location": ([p, dp, C.c_double], C.c_int),
         "srl_lio_probe_checksum_of_committed_frame": ([p, C.c_int, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)], C.c_int),
         "srl_lio_resident_sweep": ([p, p, C.c_int], C.c_int),
         "srl_lio_prefetch_sweep": ([p, p, C.c_int], C.c_int),
@@ -444,6 +446,14 @@ class Context:
         xyz = np.zeros((nv, cap, 3), dtype=np.float32)
         self._chk(self.lib.srl_map_download(self.h, _ptr(keys), _ptr(counts), _ptr(xyz), nv), "srl_map_download")
         return keys, counts, xyz
+
+    def map_remove_far(self, location, distance):
+        """srl_map_remove_far (removePointsFarFromLocation): erase the voxels whose first point lies farther than `distance` from
+        `location`; the survivors keep their creation order.  Returns (voxels_removed, points_removed)."""
+        nv, npnt = C.c_int32(), C.c_int64()
+        loc = _f64(location).ravel()
+        self._chk(self.lib.srl_map_remove_far(self.h, _dptr(loc), float(distance), C.byref(nv), C.byref(npnt)), "srl_map_remove_far")
+        return nv.value, npnt.value
 
     def sweep_upload(self, raw_xyz):
         r = _f64(raw_xyz, (-1, 3))
@@ -862,6 +872,11 @@ class Lio:
         n = C.c_int64()
         self._chk(self.lib.srl_lio_map_size(self.h, C.byref(n)), "map_size")
         return n.value
+
+    def remove_points_far_from_location(self, location, distance):
+        """lioOptimization::removePointsFarFromLocation on the device map (srl_map_remove_far)"""
+        loc = _f64(location).ravel()
+        self._chk(self.lib.srl_lio_remove_points_far_from_location(self.h, _dptr(loc), float(distance)), "remove_points_far_from_location")
 
     def resident_sweep(self, raw_xyz):
         r = _f64(raw_xyz, (-1, 3))

@@ -488,6 +488,11 @@ void lioOptimization::addPointsToMap(voxelHashMap &map, cloudFrame *p_frame, dou
           "srl_map_insert");
 }
 
+void lioOptimization::removePointsFarFromLocation(voxelHashMap &map, const srl::Vec3 &location, double distance) {
+    if (!map.ctx) throw std::runtime_error("removePointsFarFromLocation: no HIP context (the product has no CPU path)");
+    check(map.ctx, srl_map_remove_far(map.ctx, location.a, distance, nullptr, nullptr), "srl_map_remove_far");
+}
+
 size_t lioOptimization::mapSize(const voxelHashMap &map) {
     if (!map.ctx) throw std::runtime_error("mapSize: no HIP context");
     int64_t np = 0;

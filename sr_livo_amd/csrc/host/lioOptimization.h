@@ -1,6 +1,6 @@
 // lioOptimization.h (host mirror) -- the reference's class surface for the LIO scan-matching path
 // (include/lioOptimization.h:334-357: optimize / buildPlaneResiduals / updateIEKF /
-// computeNeighborhoodDistribution / searchNeighbors / addPointToMap / addPointsToMap / mapSize),
+// computeNeighborhoodDistribution / searchNeighbors / addPointToMap / addPointsToMap / removePointsFarFromLocation / mapSize),
 // forwarding through the C-ABI of include/srlivo_hip.h to the gfx950 kernels.  ROS I/O, sensor
 // decoding and the vision stage of the reference class are out of scope.
 #pragma once
@@ -14,8 +14,9 @@
 #include <string>
 #include <vector>
 
-// When Eigen is on the include path (the reference's own build: CMakeLists.txt:51) the two members whose signatures carry
-// Eigen types -- computeNeighborhoodDistribution and searchNeighbors, include/lioOptimization.h:340-343 -- are ALSO
+// When Eigen is on the include path (the reference's own build: CMakeLists.txt:51) the members whose signatures carry
+// Eigen types -- computeNeighborhoodDistribution and searchNeighbors, include/lioOptimization.h:340-343, and
+// removePointsFarFromLocation, :355 -- are ALSO
 // declared with exactly those types, so call sites written against the reference header compile unchanged.  They convert
 // at the boundary and forward to the srl:: versions (the image this was built in has no Eigen: tests/stub_eigen holds the
 // minimal stand-in the signature test compiles against).  -DSRL_NO_EIGEN switches the block off.
@@ -124,6 +125,14 @@ public:
                        double min_distance_points, int min_num_points, cloudFrame *p_frame);
     void addPointsToMap(voxelHashMap &map, cloudFrame *p_frame, double voxel_size, int max_num_points_in_voxel,
                         double min_distance_points, int min_num_points = 0, bool to_rendering = false);
+    // lioOptimization.cpp:556-572: srl_map_remove_far (the survivors are renumbered in creation order)
+    void removePointsFarFromLocation(voxelHashMap &map, const srl::Vec3 &location, double distance);
+#ifdef SRL_HAVE_EIGEN
+    // the reference's own signature (include/lioOptimization.h:355), so that the node's call at lioOptimization.cpp:1032 compiles as written
+    void removePointsFarFromLocation(voxelHashMap &map, const Eigen::Vector3d &location, double distance) {
+        removePointsFarFromLocation(map, srl::vec3(location[0], location[1], location[2]), distance);
+    }
+#endif
     size_t mapSize(const voxelHashMap &map);
 
     // stateInitialization (lioOptimization.cpp:895-990): pose prior of the next frame from the last two frames of

@@ -218,6 +218,12 @@ int srl_lio_map_size(srl_lio *h, int64_t *num_points) {
     catch (const std::exception &e) { return status_from_exception(h, e); }
     return SRL_OK;
 }
+int srl_lio_remove_points_far_from_location(srl_lio *h, const double location[3], double distance) {
+    if (!h || !location) return SRL_ERR_BAD_ARG;
+    try { h->lio->removePointsFarFromLocation(h->lio->voxel_map, srl::vec3(location[0], location[1], location[2]), distance); }
+    catch (const std::exception &e) { return status_from_exception(h, e); }
+    return SRL_OK;
+}
 
 int srl_lio_probe_checksum_of_committed_frame(srl_lio *h, int stride, double voxel_size, uint64_t *checksum, int32_t *num_voxels) {
     if (!h || !checksum) return SRL_ERR_BAD_ARG;

@@ -198,7 +198,8 @@ int srl_frame_upload(srl_ctx *ctx, const double *raw_xyz, int n);
  *   Outputs (optional): point3D::imu_point and the corrected point3D::raw_point, n x 3 each.  The corrected sweep
  *   stays in HBM.
  * srl_frame_take makes the points index[0..m) of the corrected sweep the resident frame (what srl_frame_upload
- *   would upload) -- the order buildFrame's shuffle / subSampleFrame / shuffle leaves (a host decision). */
+ *   would upload) -- any index list; buildFrame's shuffle / subSampleFrame / shuffle is srl_frame_subsample +
+ *   srl_frame_take_subsampled below (and srl_frame_take with the first shuffle's order when voxel_size <= 0). */
 typedef struct srl_imu_state {
     double timestamp;
     double un_acc[3], un_gyr[3], trans[3];
@@ -211,6 +212,22 @@ int srl_frame_undistort(srl_ctx *ctx, const double *raw_xyz, const double *relat
                         int motion_compensation, const double R_il[9], const double t_il[3], double *imu_point_out,
                         double *raw_out);
 int srl_frame_take(srl_ctx *ctx, const int32_t *index, int m);
+/* buildFrame's subSampleFrame (lioOptimization.cpp:838-846 -> utility.cpp:167-186) on the sweep srl_frame_undistort left in HBM, in place of
+ * the host grouping and srl_frame_take's index list.  The two std::shuffle calls stay with the caller (its own engine and library).
+ * srl_frame_subsample visits the points in visit_order (n = the undistorted count; a permutation of 0..n-1: the first shuffle), keys each
+ *   by its UNCORRECTED point (raw_xyz as srl_frame_undistort received it: point3D::point, cloudProcessing.cpp:143) at sample_size
+ *   (short(p / size) per axis), keeps the first visited point of every voxel and orders the voxels as std::tr1::unordered_map iterates
+ *   them.  *num_kept = m, the voxel count.  The permutation is checked on the device (SRL_ERR_BAD_ARG if it is none); the order is computed
+ *   there as in srl_frame_select_keypoints (srl_debug_frame_order_used reports the path).
+ * srl_frame_take_subsampled makes frame point k = kept[perm[k]] the resident frame (perm: the second shuffle over 0..m-1 -- std::shuffle of
+ *   the kept list equals this gather with perm = std::shuffle(0..m-1) on the same engine; NULL = container order), and downloads on request
+ *   the sweep index (m), the corrected raw_point (m x 3) and imu_point (m x 3) of every frame point.  A perm that is not a permutation
+ *   returns SRL_ERR_BAD_ARG and leaves no resident frame; the sub-sample stays and can be taken again.
+ * Both return SRL_ERR_NO_SWEEP without an undistorted sweep (or, for the take, without a sub-sample of it), SRL_ERR_BAD_ARG for an n or m
+ * that does not match, SRL_ERR_UNSUPPORTED with more than one rank.  srl_frame_undistort may then be called with both outputs NULL. */
+int srl_frame_subsample(srl_ctx *ctx, const int32_t *visit_order, int n, double sample_size, int *num_kept);
+int srl_frame_take_subsampled(srl_ctx *ctx, const int32_t *perm /* m or NULL */, int m, int32_t *index_out /* m or NULL */,
+                              double *raw_out /* m x 3 or NULL */, double *imu_out /* m x 3 or NULL */);
 int srl_frame_size(srl_ctx *ctx, int *n);      /* points of the resident frame (capacity needed for keypoint_index) */
 int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9],
                                const double t_il[3], double sample_voxel_size,

@@ -53,6 +53,10 @@ int srl_lio_map_size(srl_lio *lio, int64_t *num_points);
  * srl_lio_run_measurement does the same with srl_lio_remove_points_far_from_location(lio, result.state + 4, max_distance) after every
  * processed, successful measurement. */
 int srl_lio_remove_points_far_from_location(srl_lio *lio, const double location[3], double distance);
+/* Where lioOptimization::buildFrame sub-samples the cut sweep (subSampleFrame, lioOptimization.cpp:838-846): on = 1 (the default) on the
+ * device (srl_frame_subsample + srl_frame_take_subsampled; the host runs the two shuffles on index arrays and downloads m points), 0 = on the
+ * host over the n-point downloads of srl_frame_undistort and srl_frame_take.  Both give the same frame bit for bit. */
+int srl_lio_set_device_subsample(srl_lio *lio, int on);
 /* srl_map_probe_checksum over the world points the last srl_lio_commit_frame left in HBM (the frame the node inserts next) */
 int srl_lio_probe_checksum_of_committed_frame(srl_lio *lio, int stride, double voxel_size, uint64_t *checksum, int32_t *num_voxels);
 

@@ -138,6 +138,8 @@ def load_library():
         "srl_frame_upload": ([p, p, C.c_int], C.c_int),
         "srl_frame_undistort": ([p, p, p, p, C.c_int, p, C.c_int, C.c_double, C.c_int, dp, dp, p, p], C.c_int),
         "srl_frame_take": ([p, p, C.c_int], C.c_int),
+        "srl_frame_subsample": ([p, p, C.c_int, C.c_double, C.POINTER(C.c_int)], C.c_int),
+        "srl_frame_take_subsampled": ([p, p, C.c_int, p, p, p], C.c_int),
         "srl_frame_size": ([p, C.POINTER(C.c_int)], C.c_int),
         "srl_frame_select_keypoints": ([p, dp, dp, dp, dp, C.c_double, p, C.POINTER(C.c_int)], C.c_int),
         "srl_frame_commit": ([p, dp, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_int, p, C.POINTER(C.c_int)], C.c_int),
@@ -201,6 +203,7 @@ def load_library():
         "srl_lio_add_points_to_map": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
         "srl_lio_map_size": ([p, C.POINTER(C.c_int64)], C.c_int),
         "srl_lio_remove_points_far_from_location": ([p, dp, C.c_double], C.c_int),
+        "srl_lio_set_device_subsample": ([p, C.c_int], C.c_int),
         "srl_lio_probe_checksum_of_committed_frame": ([p, C.c_int, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)], C.c_int),
         "srl_lio_resident_sweep": ([p, p, C.c_int], C.c_int),
         "srl_lio_prefetch_sweep": ([p, p, C.c_int], C.c_int),
@@ -619,14 +622,17 @@ class Context:
         r = _f64(raw_xyz, (-1, 3))
         self._chk(self.lib.srl_frame_upload(self.h, _ptr(r), len(r)), "srl_frame_upload")
 
-    def frame_undistort(self, raw_xyz, relative_time_ms, imu_states, time_frame_begin, mode, R_il=None, t_il=None, imu_point_in=None):
-        """imu_states: (S, 17) array = timestamp, un_acc, un_gyr, trans, quat wxyz, vel.  Returns (imu_point, raw_point)."""
+    def frame_undistort(self, raw_xyz, relative_time_ms, imu_states, time_frame_begin, mode, R_il=None, t_il=None, imu_point_in=None,
+                        want_outputs=True):
+        """imu_states: (S, 17) array = timestamp, un_acc, un_gyr, trans, quat wxyz, vel.  Returns (imu_point, raw_point); (None, None) with
+        want_outputs=False (both outputs NULL: the corrected sweep only stays in HBM)"""
         r = _f64(raw_xyz, (-1, 3)); rel = _f64(relative_time_ms)
         st = _f64(imu_states, (-1, 17))
         R_il = _f64(np.eye(3) if R_il is None else R_il).ravel()
         t_il = _f64(np.zeros(3) if t_il is None else t_il)
         pin = None if imu_point_in is None else _f64(imu_point_in, (-1, 3))
-        imu = np.empty_like(r); out = np.empty_like(r)
+        imu = np.empty_like(r) if want_outputs else None
+        out = np.empty_like(r) if want_outputs else None
         self._chk(self.lib.srl_frame_undistort(self.h, _ptr(r), _ptr(rel), None if pin is None else _ptr(pin), len(r), _ptr(st), len(st),
                                                float(time_frame_begin), int(mode), _dptr(R_il), _dptr(t_il), _ptr(imu), _ptr(out)),
                   "srl_frame_undistort")
@@ -635,6 +641,30 @@ class Context:
     def frame_take(self, index):
         idx = np.ascontiguousarray(index, dtype=np.int32)
         self._chk(self.lib.srl_frame_take(self.h, _ptr(idx), len(idx)), "srl_frame_take")
+
+    def frame_subsample(self, order, sample_size):
+        """srl_frame_subsample: buildFrame's subSampleFrame on the undistorted sweep, visiting the points in `order` (the first shuffle);
+        returns m, the number of voxels kept"""
+        o = np.ascontiguousarray(order, dtype=np.int32)
+        m = C.c_int()
+        self._chk(self.lib.srl_frame_subsample(self.h, _ptr(o), len(o), float(sample_size), C.byref(m)), "srl_frame_subsample")
+        self._kept = m.value
+        return m.value
+
+    def frame_take_subsampled(self, perm=None, m=None, want_index=True, want_raw=False, want_imu=False):
+        """srl_frame_take_subsampled: frame point k = kept[perm[k]] (perm = the second shuffle over 0..m-1; None = container order, m = the
+        last sub-sample's count unless given).  Returns dict(index, raw, imu), None for what was not asked for."""
+        pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        if m is None:
+            m = len(pm) if pm is not None else getattr(self, "_kept", 0)
+        m = int(m)
+        idx = np.empty(m, dtype=np.int32) if want_index else None
+        raw = np.empty((m, 3)) if want_raw else None
+        imu = np.empty((m, 3)) if want_imu else None
+        self._chk(self.lib.srl_frame_take_subsampled(self.h, _ptr(pm), m, _ptr(idx),
+                                                     _ptr(raw), _ptr(imu)),
+                  "srl_frame_take_subsampled")
+        return dict(index=idx, raw=raw, imu=imu)
 
     def frame_size(self):
         n = C.c_int()
@@ -877,6 +907,10 @@ class Lio:
         """lioOptimization::removePointsFarFromLocation on the device map (srl_map_remove_far)"""
         loc = _f64(location).ravel()
         self._chk(self.lib.srl_lio_remove_points_far_from_location(self.h, _dptr(loc), float(distance)), "remove_points_far_from_location")
+
+    def set_device_subsample(self, on):
+        """buildFrame's sub-sample on the device (True, the default) or on the host (srl_lio_set_device_subsample)"""
+        self._chk(self.lib.srl_lio_set_device_subsample(self.h, 1 if on else 0), "srl_lio_set_device_subsample")
 
     def resident_sweep(self, raw_xyz):
         r = _f64(raw_xyz, (-1, 3))

@@ -584,7 +584,10 @@ cloudFrame *lioOptimization::buildFrame(std::vector<point3D> &cut_sweep, state *
 
     // device: distortFrameBy* + transformAllImuPoint over the whole sweep
     const int n = (int)sweep.size();
-    std::vector<double> raw((size_t)n * 3), rel((size_t)n), imu_in((size_t)n * 3), imu_out((size_t)n * 3), raw_out((size_t)n * 3);
+    const double sample_size = index_frame < init_num_frames ? init_voxel_size : voxel_size;
+    const bool on_device = device_subsample && voxel_size > 0;      // (no sub-sample: the frame is the first shuffle's order of all n points)
+    std::vector<double> raw((size_t)n * 3), rel((size_t)n), imu_in((size_t)n * 3), imu_out, raw_out;
+    if (!on_device) { imu_out.resize((size_t)n * 3); raw_out.resize((size_t)n * 3); }
     for (int i = 0; i < n; i++) {
         for (int d = 0; d < 3; d++) { raw[(size_t)i * 3 + d] = sweep[i].raw_point[d]; imu_in[(size_t)i * 3 + d] = sweep[i].imu_point[d]; }
         rel[i] = sweep[i].relative_time;
@@ -600,35 +603,54 @@ cloudFrame *lioOptimization::buildFrame(std::vector<point3D> &cut_sweep, state *
     }
     const int mode = motion_compensation == CONSTANT_VELOCITY ? SRL_MC_CONSTANT_VELOCITY : motion_compensation == IMU ? SRL_MC_IMU : SRL_MC_NONE;
     check(ctx, srl_frame_undistort(ctx, raw.data(), rel.data(), imu_in.data(), n, st.data(), (int)st.size(), time_frame_begin, mode,
-                                   R_imu_lidar.a, t_imu_lidar.a, imu_out.data(), raw_out.data()), "srl_frame_undistort");
+                                   R_imu_lidar.a, t_imu_lidar.a, on_device ? nullptr : imu_out.data(), on_device ? nullptr : raw_out.data()),
+          "srl_frame_undistort");
 
-    // host: the order (indices only).  subSampleFrame keys on point3D::point, which still holds the sensor-frame
-    // point here (cloudProcessing.cpp:143); the engine is shared by both shuffles.
-    const double sample_size = index_frame < init_num_frames ? init_voxel_size : voxel_size;
+    // the order: both shuffles on index arrays with the engine they share.  subSampleFrame keys on point3D::point, which still holds the
+    // sensor-frame point here (cloudProcessing.cpp:143) -- what srl_frame_undistort received as raw_xyz
     std::vector<int> order((size_t)n);
     for (int i = 0; i < n; i++) order[i] = i;
     std::mt19937_64 seed;                                                // boost::mt19937_64 seed;
     std::shuffle(order.begin(), order.end(), seed);
-    if (voxel_size > 0) {
-        std::tr1::unordered_map<voxel, std::vector<int>, std::hash<voxel>> grid;
-        for (int i : order) {
-            const srl::Vec3 &p = sweep[i].point;
-            grid[voxel(static_cast<short>(p[0] / sample_size), static_cast<short>(p[1] / sample_size), static_cast<short>(p[2] / sample_size))].push_back(i);
+    std::vector<point3D> frame;
+    if (on_device) {
+        // grouping, first visited point per voxel and the container's order on the device; the second shuffle of the kept list is the
+        // gather kept[perm[k]] with perm = the same std::shuffle over 0..m-1 (its swaps depend on m and the engine only)
+        const std::vector<int32_t> visit(order.begin(), order.end());
+        int m = 0;
+        check(ctx, srl_frame_subsample(ctx, visit.data(), n, sample_size, &m), "srl_frame_subsample");
+        std::vector<int32_t> perm((size_t)m), index((size_t)m);
+        for (int k = 0; k < m; k++) perm[k] = k;
+        std::shuffle(perm.begin(), perm.end(), seed);
+        std::vector<double> f_raw((size_t)m * 3), f_imu((size_t)m * 3);
+        check(ctx, srl_frame_take_subsampled(ctx, perm.data(), m, index.data(), f_raw.data(), f_imu.data()), "srl_frame_take_subsampled");
+        releaseSweep();
+        frame.resize((size_t)m);
+        for (int k = 0; k < m; k++) {
+            frame[k] = sweep[index[k]];
+            for (int d = 0; d < 3; d++) { frame[k].imu_point[d] = f_imu[(size_t)k * 3 + d]; frame[k].raw_point[d] = f_raw[(size_t)k * 3 + d]; }
         }
-        order.resize(0);
-        for (const auto &kv : grid)
-            if (kv.second.size() > 0) order.push_back(kv.second[0]);
-        std::shuffle(order.begin(), order.end(), seed);
-    }
-    std::vector<int32_t> take(order.begin(), order.end());
-    check(ctx, srl_frame_take(ctx, take.data(), (int)take.size()), "srl_frame_take");
-    releaseSweep();
-
-    std::vector<point3D> frame(order.size());
-    for (size_t k = 0; k < order.size(); k++) {
-        const int i = order[k];
-        frame[k] = sweep[i];
-        for (int d = 0; d < 3; d++) { frame[k].imu_point[d] = imu_out[(size_t)i * 3 + d]; frame[k].raw_point[d] = raw_out[(size_t)i * 3 + d]; }
+    } else {
+        if (voxel_size > 0) {
+            std::tr1::unordered_map<voxel, std::vector<int>, std::hash<voxel>> grid;
+            for (int i : order) {
+                const srl::Vec3 &p = sweep[i].point;
+                grid[voxel(static_cast<short>(p[0] / sample_size), static_cast<short>(p[1] / sample_size), static_cast<short>(p[2] / sample_size))].push_back(i);
+            }
+            order.resize(0);
+            for (const auto &kv : grid)
+                if (kv.second.size() > 0) order.push_back(kv.second[0]);
+            std::shuffle(order.begin(), order.end(), seed);
+        }
+        std::vector<int32_t> take(order.begin(), order.end());
+        check(ctx, srl_frame_take(ctx, take.data(), (int)take.size()), "srl_frame_take");
+        releaseSweep();
+        frame.resize(order.size());
+        for (size_t k = 0; k < order.size(); k++) {
+            const int i = order[k];
+            frame[k] = sweep[i];
+            for (int d = 0; d < 3; d++) { frame[k].imu_point[d] = imu_out[(size_t)i * 3 + d]; frame[k].raw_point[d] = raw_out[(size_t)i * 3 + d]; }
+        }
     }
 
     double dt_offset = 0;

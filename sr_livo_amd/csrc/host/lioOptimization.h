@@ -143,12 +143,16 @@ public:
     int initialization = INIT_IMU;                                      // odometry_options.initialization (both yaml: "imu")
 
     // sweep reconstruction (lioOptimization.cpp:786-893).  The per-point math of distortFrameByConstant/-ByImu and
-    // transformAllImuPoint runs on the device over the whole cut sweep (srl_frame_undistort); the order decisions
-    // (two std::shuffle with one default-seeded mt19937_64, subSampleFrame's tr1 iteration order) stay on the host;
-    // the surviving points become the resident frame (srl_frame_take), so optimizeResident(p_frame, ...) and
-    // commitFrame() need no further upload.  point_frame of the returned frame is filled from the device results.
+    // transformAllImuPoint runs on the device over the whole cut sweep (srl_frame_undistort); the two std::shuffle calls
+    // (one default-seeded mt19937_64) run on the host over index arrays; subSampleFrame's grouping and tr1 iteration
+    // order run on the device (srl_frame_subsample), and the surviving points become the resident frame
+    // (srl_frame_take_subsampled), so optimizeResident(p_frame, ...) and commitFrame() need no further upload.
+    // point_frame of the returned frame is filled from the device results (m points, not the n of the sweep).
+    // device_subsample = false: the grouping on the host over the n-point downloads and srl_frame_take (the same bits;
+    // kept to compare the two in one process, srl_lio_set_device_subsample).
     void makePointTimestamp(std::vector<point3D> &sweep, double time_begin, double time_end);
     cloudFrame *buildFrame(std::vector<point3D> &cut_sweep, state *cur_state, double timestamp_begin, double timestamp_offset);
+    bool device_subsample = true;
     // optimize() on the frame buildFrame left resident in HBM
     optimizeSummary optimizeBuiltFrame(cloudFrame *p_frame, const icpOptions &cur_icp_options, double sample_voxel_size,
                                        std::vector<int> *keypoint_index = nullptr);

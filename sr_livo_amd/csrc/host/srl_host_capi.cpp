@@ -225,6 +225,12 @@ int srl_lio_remove_points_far_from_location(srl_lio *h, const double location[3]
     return SRL_OK;
 }
 
+int srl_lio_set_device_subsample(srl_lio *h, int on) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    h->lio->device_subsample = on != 0;
+    return SRL_OK;
+}
+
 int srl_lio_probe_checksum_of_committed_frame(srl_lio *h, int stride, double voxel_size, uint64_t *checksum, int32_t *num_voxels) {
     if (!h || !checksum) return SRL_ERR_BAD_ARG;
     srl_ctx *ctx = h->lio->context();

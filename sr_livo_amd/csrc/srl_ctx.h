@@ -99,6 +99,13 @@ struct srl_ctx {
     int *d_corr_seg = nullptr;
     int corr_cap = 0;
     int corr_n = -1;
+    // buildFrame's sub-sample of the undistorted sweep (srl_frame_subsample): the kept sweep indices in container order, and the tag words
+    // that check a permutation on the device (zeroed when allocated; a call tags with a value no earlier call of this block used)
+    int *d_sub_kept = nullptr;
+    unsigned *d_sub_seen = nullptr;
+    int sub_cap = 0;
+    int sub_n = -1;                    // voxels kept by the last sub-sample of the CURRENT undistorted sweep (-1: none)
+    unsigned sub_seen_tag = 0;
 
     // srl_debug_frame_timing: per-stage wall time of the frame pipeline (the stream is synchronised at every stage boundary while on)
     bool frame_timing = false;

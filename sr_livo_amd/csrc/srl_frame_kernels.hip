@@ -9,6 +9,9 @@
 //                               keys alone, so the distinct keys are inserted (first-occurrence order) into the same
 //                               container type and read back.  The selected raw points are gathered on the device
 //                               straight into the resident sweep (no keypoint upload).
+//   srl_frame_subsample         buildFrame's subSampleFrame (lioOptimization.cpp:838-846) on the undistorted sweep: the same grouping and
+//   srl_frame_take_subsampled   order chain in the first shuffle's visit order, keyed on the uncorrected points; then the second shuffle
+//                               as a gather into the resident frame
 //   srl_frame_commit            the re-transform loop of optimize() (optimize.cpp:441-445) + addPointsToMap
 //                               (lioOptimization.cpp:520-554) chained on the device.
 #include "srl_ctx.h"
@@ -131,8 +134,12 @@ struct EmitSink {
         host_first[r] = (unsigned)i;
     }
 };
+// bit 30 of a published count word: srl_frame_subsample's visit order was not a permutation (sync[4], set by k_sub_group; 0 for a selection)
+#define SRL_CTRL_BAD_ORDER (1u << 30)
+#define SRL_CTRL_COUNT_MASK 0x3FFFFFFFu
 struct EmitFin {
-    unsigned *sync;                           // [0] workgroups done (reset by the last one), [1] the count (written by the workgroup holding the last tile)
+    unsigned *sync;                           // [0] workgroups done (reset by the last one), [1] the count (written by the workgroup holding the last tile),
+                                              // [4] a bad visit order (k_sub_group)
     unsigned long long *host_ctrl;
     unsigned tag;
     __device__ void operator()(int tile_end) const {
@@ -144,8 +151,11 @@ struct EmitFin {
         if (prev == gridDim.x - 1) {
             __hip_atomic_store(sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned count = __hip_atomic_load(sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned bad = __hip_atomic_load(sync + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (k_sub_group, below)
+            if (bad) __hip_atomic_store(sync + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __threadfence_system();
-            __hip_atomic_store(host_ctrl, ((unsigned long long)tag << 32) | count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host_ctrl, ((unsigned long long)tag << 32) | (bad ? SRL_CTRL_BAD_ORDER : 0u) | count, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 };
@@ -217,8 +227,10 @@ __global__ void k_tr1_bucket(const SrlTr1Sched *S, unsigned *sync, const unsigne
     __hip_atomic_store(sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned over = __hip_atomic_load(sync + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(sync + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(host_ctrl, ((unsigned long long)tag << 32) | ((unsigned long long)(over ? 1u : 0u) << 31) | total, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
+    const unsigned bad = __hip_atomic_load(sync + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bad) __hip_atomic_store(sync + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(host_ctrl, ((unsigned long long)tag << 32) | ((unsigned long long)(over ? 1u : 0u) << 31) | (bad ? SRL_CTRL_BAD_ORDER : 0u) | total,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // T_G(o, me) from the two records; falls back to the general relation below level G - 1 (two voxels sharing their bucket at two levels)
 struct Tr1EraOfSched {
@@ -234,7 +246,8 @@ __device__ __forceinline__ bool tr1_rec_before(const SrlTr1Sched *S, const unsig
     return srl_tr1_before_t(G - 1, me, o, Tr1EraOfSched{S}, SrlTr1BucketOfHash{S, hash});      // rare (one pair in ~n_{G-1})
 }
 // one thread per voxel: position = start of its bucket (scan over the bucket counts) + voxels of the bucket that precede it; writes the
-// ordered index list and gathers the keypoint's raw point into the resident sweep
+// ordered index list and (kGather: keypoint selection) gathers the keypoint's raw point into the resident sweep
+template <bool kGather>
 __global__ void k_tr1_rank(const SrlTr1Sched *S, unsigned *sync, const unsigned long long *hash, const unsigned *first, const unsigned long long *members,
                            const int *bucket_count, const int *bucket_start, const unsigned *bucket_of, const double *raw,
                            double *x, double *y, double *z, int *sel) {
@@ -249,7 +262,8 @@ __global__ void k_tr1_rank(const SrlTr1Sched *S, unsigned *sync, const unsigned 
         const int start = bucket_start[b];
         const unsigned long long *m = members + (size_t)b * SRL_TR1_BUCKET_SLOTS;
         const ulonglong2 r01 = *reinterpret_cast<const ulonglong2 *>(m), r23 = *reinterpret_cast<const ulonglong2 *>(m + 2);
-        const double px = raw[(size_t)fi * 3], py = raw[(size_t)fi * 3 + 1], pz = raw[(size_t)fi * 3 + 2];
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (kGather) { px = raw[(size_t)fi * 3]; py = raw[(size_t)fi * 3 + 1]; pz = raw[(size_t)fi * 3 + 2]; }
         if (c <= SRL_TR1_BUCKET_SLOTS) {            // (an overfull bucket: k_tr1_bucket has told the host, which orders the frame itself)
             int rank = 0;
             if (c > 1) {
@@ -270,9 +284,11 @@ __global__ void k_tr1_rank(const SrlTr1Sched *S, unsigned *sync, const unsigned 
             }
             const int k = start + rank;
             sel[k] = (int)fi;
-            x[k] = px;
-            y[k] = py;
-            z[k] = pz;
+            if (kGather) {
+                x[k] = px;
+                y[k] = py;
+                z[k] = pz;
+            }
         }
     }
 }
@@ -449,6 +465,117 @@ __global__ void k_gather_aos(const double *src, const int *sel, int m, double *d
     dst[(size_t)k * 3 + 2] = src[(size_t)i * 3 + 2];
 }
 
+// ---------------------------------------------------------------------------- buildFrame's sub-sample (lioOptimization.cpp:838-846)
+// subSampleFrame (utility.cpp:167-186) over the sweep in the order of the first shuffle: keyed on point3D::point -- the UNCORRECTED sensor-frame
+// point (cloudProcessing.cpp:143), d_corr_in -- at the sample size, no pose.  Thread j visits point order[j]; the voxel keeps the point of the
+// smallest visit rank j ({~frame counter, j} in the same scratch words keypoint selection lowers), and the chain behind it is the selection's:
+// k_select_mark, the scan over the marks (first-VISIT order), k_tr1_bucket, the scan over the bucket counts, k_tr1_rank.
+// The same pass checks that order is a permutation of 0..n-1: an index out of range is not visited, an index seen twice (its tag word already
+// holds this call's tag) is still grouped; either sets sync[4], which the publisher of the count word folds into SRL_CTRL_BAD_ORDER.
+__global__ void k_sub_group(const int *order, int n, const double *pts, double size, unsigned long long *keyw, unsigned long long *minw, unsigned mask,
+                            unsigned epoch16, unsigned counter32, int *flag, unsigned *seen, unsigned seen_tag, unsigned *bad) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    flag[j] = 0;
+    const int i = order[j];
+    if ((unsigned)i >= (unsigned)n) { __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
+    if (atomicExch(&seen[i], seen_tag) == seen_tag) __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double x = pts[(size_t)i * 3], y = pts[(size_t)i * 3 + 1], z = pts[(size_t)i * 3 + 2];
+    const unsigned long long key = srl_pack_key((short)(int)(x / size), (short)(int)(y / size), (short)(int)(z / size));
+    const unsigned h = srl_epoch_claim(keyw, mask, epoch16, key, srl_hash_key(key));
+    atomicMin(&minw[h], ((unsigned long long)(0xFFFFFFFFu - counter32) << 32) | (unsigned)j);
+}
+// RankSink of the sub-sample: the element a voxel carries is the sweep index of its first visited point, order[j]
+struct SubRankSink {
+    const unsigned long long *key_at;
+    unsigned long long *hash;
+    unsigned *first;
+    const int *order;
+    __device__ void operator()(int j, int is_first, int r) const {
+        if (!is_first) return;
+        short x, y, z;
+        srl_unpack_key(key_at[j], &x, &y, &z);
+        const unsigned long long kP1 = 73856093ull, kP2 = 19349669ull, kP3 = 83492791ull;
+        hash[r] = (unsigned long long)(long long)x * kP1 + (unsigned long long)(long long)y * kP2 + (unsigned long long)(long long)z * kP3;
+        first[r] = (unsigned)order[j];
+    }
+};
+// the second shuffle and the take: frame point k = kept[perm[k]] (perm == NULL: k) -> the resident frame, and on request its sweep index and
+// imu_point; a perm that is not a permutation of 0..m-1 sets *bad (page-locked host word, read behind the stream synchronisation)
+__global__ void k_sub_take(const int *kept, const int *perm, int m, unsigned *seen, unsigned seen_tag, const double *raw, const double *imu,
+                           double *frame_raw, int *index_out, double *imu_out, unsigned *bad) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int p = perm ? perm[k] : k;
+    if ((unsigned)p >= (unsigned)m) { __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return; }
+    if (perm && atomicExch(&seen[p], seen_tag) == seen_tag) __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const int i = kept[p];
+    frame_raw[(size_t)k * 3] = raw[(size_t)i * 3];
+    frame_raw[(size_t)k * 3 + 1] = raw[(size_t)i * 3 + 1];
+    frame_raw[(size_t)k * 3 + 2] = raw[(size_t)i * 3 + 2];
+    if (index_out) index_out[k] = i;
+    if (imu_out) {
+        imu_out[(size_t)k * 3] = imu[(size_t)i * 3];
+        imu_out[(size_t)k * 3 + 1] = imu[(size_t)i * 3 + 1];
+        imu_out[(size_t)k * 3 + 2] = imu[(size_t)i * 3 + 2];
+    }
+}
+
+// the keypoint ORDER on the device applies to n points (frame_order_mode 0, a bucket table that fits one scan launch): the container's growth
+// schedule goes to the device once, *nb_max = bucket count of its level for n elements; 0 = the host replay orders
+int tr1_device_order(srl_ctx *ctx, int n, unsigned *nb_max) {
+    *nb_max = 0;
+    if (ctx->frame_order_mode != 0 || n > SRL_SCAN_MAX) return SRL_OK;
+    if (ctx->tr1_steps < 0) {
+        SrlTr1Sched S;
+        std::memset(&S, 0, sizeof S);
+        const int steps = srl::Tr1Order::export_schedule(SRL_SCAN_MAX, S.first, S.nb, SRL_TR1_MAX_STEPS);
+        if (steps >= 0) {
+            S.steps = steps;
+            HIPCHK(ctx, hipMalloc((void **)&ctx->d_tr1_sched, sizeof S));
+            HIPCHK(ctx, hipMemcpy(ctx->d_tr1_sched, &S, sizeof S, hipMemcpyHostToDevice));
+            std::memcpy(ctx->tr1_first, S.first, sizeof S.first);
+            std::memcpy(ctx->tr1_nb, S.nb, sizeof S.nb);
+            ctx->tr1_steps = steps;
+        } else {
+            ctx->tr1_steps = -2;                                      // a growth policy this table cannot hold: host replay from now on
+        }
+    }
+    if (ctx->tr1_steps < 0) return SRL_OK;
+    int g = 0;
+    while (g < ctx->tr1_steps && ctx->tr1_first[g] <= (unsigned)n) ++g;
+    const unsigned nb = ctx->tr1_nb[g];
+    if (nb > 0 && nb <= (1u << 23)) *nb_max = nb;                   // (srl_scan takes any size; the member lists are 128 B per bucket)
+    return SRL_OK;
+}
+
+// wait for the count word {tag, flags, count} of a frame chain (the stream is looked at every ~1M polls: a fault must not become a hang)
+int wait_frame_word(srl_ctx *ctx, const unsigned long long *h_ctrl, unsigned tag, const char *what, unsigned long long *out) {
+    unsigned long long ctrl = 0, spins = 0;
+    while ((unsigned)((ctrl = __atomic_load_n(h_ctrl, __ATOMIC_ACQUIRE)) >> 32) != tag) {
+        if ((++spins & 0xFFFFF) == 0) {
+            const hipError_t qe = hipStreamQuery(ctx->stream);
+            if (qe != hipSuccess && qe != hipErrorNotReady) { ctx->err = std::string(what) + ": " + hipGetErrorString(qe); return SRL_ERR_HIP; }
+            if (qe == hipSuccess && (unsigned)(__atomic_load_n(h_ctrl, __ATOMIC_ACQUIRE) >> 32) != tag) {
+                ctx->err = std::string(what) + " finished without publishing its voxel list";
+                return SRL_ERR_HIP;
+            }
+        }
+    }
+    *out = ctrl;
+    return SRL_OK;
+}
+
+// a fresh tag for the permutation checks (d_sub_seen: sub_cap words, zeroed when allocated and when the tag wraps)
+int sub_seen_begin(srl_ctx *ctx, unsigned *tag) {
+    if (++ctx->sub_seen_tag == 0) {
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_sub_seen, 0, (size_t)ctx->sub_cap * 4, ctx->stream));
+        ctx->sub_seen_tag = 1;
+    }
+    *tag = ctx->sub_seen_tag;
+    return SRL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -463,6 +590,7 @@ int srl_frame_undistort(srl_ctx *ctx, const double *raw_xyz, const double *relat
         return SRL_ERR_BAD_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->corr_n = -1;
+    ctx->sub_n = -1;
     if (n > ctx->corr_cap) {
         void *bufs[] = {ctx->d_corr_raw, ctx->d_corr_imu, ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_seg};
         for (void *b : bufs) if (b) HIPCHK(ctx, hipFree(b));
@@ -554,6 +682,163 @@ int srl_frame_take(srl_ctx *ctx, const int32_t *index, int m) {
     return SRL_OK;
 }
 
+int srl_frame_subsample(srl_ctx *ctx, const int32_t *visit_order, int n, double sample_size, int *num_kept) {
+    if (num_kept) *num_kept = 0;
+    if (!ctx || n < 0 || (n > 0 && !visit_order) || !(sample_size > 0.0) || !num_kept) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    if (ctx->nranks > 1) { ctx->err = "frame pipeline is single-rank (shard with srl_sweep_upload instead)"; return SRL_ERR_UNSUPPORTED; }
+    if (ctx->corr_n < 0) { ctx->err = "no undistorted sweep (srl_frame_undistort first)"; return SRL_ERR_NO_SWEEP; }
+    ctx->sub_n = -1;
+    if (n != ctx->corr_n) { ctx->err = "visit order: n is not the size of the undistorted sweep"; return SRL_ERR_BAD_ARG; }
+    if ((unsigned)n > SRL_CTRL_COUNT_MASK) { ctx->err = "sweep too large for one sub-sample"; return SRL_ERR_UNSUPPORTED; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    static const bool trace = std::getenv("SRL_FRAME_TIMING") != nullptr;      // stage times on stderr (tools/frame_build_probe.py)
+    const auto tp0 = std::chrono::steady_clock::now();
+    auto tp1 = tp0, tp2 = tp0, tp3 = tp0;
+    ctx->frame_order_used = 0;
+    if (n == 0) { ctx->sub_n = 0; return SRL_OK; }
+    hipStream_t st = ctx->stream;
+    if (n > ctx->sub_cap) {
+        if (ctx->d_sub_kept || ctx->d_sub_seen) HIPCHK(ctx, hipStreamSynchronize(st));       // a take may still read the old blocks
+        if (ctx->d_sub_kept) { HIPCHK(ctx, hipFree(ctx->d_sub_kept)); ctx->d_sub_kept = nullptr; }
+        if (ctx->d_sub_seen) { HIPCHK(ctx, hipFree(ctx->d_sub_seen)); ctx->d_sub_seen = nullptr; }
+        ctx->sub_cap = 0;
+        const int cap = std::max(n, 4096);
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_sub_kept, (size_t)cap * 4));
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_sub_seen, (size_t)cap * 4));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_sub_seen, 0, (size_t)cap * 4, st));
+        ctx->sub_cap = cap;
+        ctx->sub_seen_tag = 0;
+    }
+    unsigned seen_tag = 0;
+    { const int rcs = sub_seen_begin(ctx, &seen_tag); if (rcs) return rcs; }
+    unsigned nb_max = 0;
+    { const int rco = tr1_device_order(ctx, n, &nb_max); if (rco) return rco; }
+    const bool dev_order = nb_max > 0;
+    unsigned cap = 1024;
+    while (cap < 2u * (unsigned)n) cap <<= 1;
+    DevBuf b_order, b_flag, b_keyat, b_hash, b_first, b_bcnt, b_members, b_elem, b_bstart, b_sc;
+    HIPCHK(ctx, b_order.alloc(ctx, (size_t)n * 4));
+    HIPCHK(ctx, b_flag.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_keyat.alloc(ctx, (size_t)n * 8));
+    HIPCHK(ctx, b_sc.alloc(ctx, srl_scan_scratch_ints(std::max(n, (int)nb_max)) * 4));
+    if (dev_order) {
+        HIPCHK(ctx, b_hash.alloc(ctx, (size_t)n * 8)); HIPCHK(ctx, b_first.alloc(ctx, (size_t)n * 4));
+        HIPCHK(ctx, b_bcnt.alloc(ctx, (size_t)nb_max * 4)); HIPCHK(ctx, b_members.alloc(ctx, (size_t)nb_max * SRL_TR1_BUCKET_SLOTS * 8));
+        HIPCHK(ctx, b_elem.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_bstart.alloc(ctx, (size_t)nb_max * 4));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(b_order.p, visit_order, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    // its own epoch of the selection's scratch table: the selection that follows in this frame opens the next one, and its {~counter, ...}
+    // words win every atomicMin against the ones left here
+    int rct = srl_epoch_table_begin(ctx, ctx->sel_table, cap, true);
+    if (rct) return rct;
+    const SrlEpochTable &T = ctx->sel_table;
+    // host exchange block: [0] control word {tag, flags, count} | hashes (8 B) | first visit ranks (4 B) | kept sweep indices (4 B)
+    int rcx = ensure_frame_exchange(ctx, 64 + (size_t)n * 16);
+    if (rcx) return rcx;
+    unsigned long long *h_ctrl = reinterpret_cast<unsigned long long *>(ctx->h_frame_x);
+    unsigned long long *h_hash = reinterpret_cast<unsigned long long *>(ctx->h_frame_x + 64);
+    unsigned *first = reinterpret_cast<unsigned *>(ctx->h_frame_x + 64 + (size_t)n * 8);
+    int *h_kept = reinterpret_cast<int *>(ctx->h_frame_x + 64 + (size_t)n * 12);
+    if (++ctx->frame_tag == 0) ++ctx->frame_tag;
+    const unsigned tag = ctx->frame_tag;
+    __atomic_store_n(h_ctrl, 0ull, __ATOMIC_RELEASE);
+    hipLaunchKernelGGL(k_sub_group, dim3((n + 255) / 256), dim3(256), 0, st, b_order.as<int>(), n, ctx->d_corr_in, sample_size, T.keyw, T.minw, cap - 1,
+                       T.epoch16, T.counter32, b_flag.as<int>(), ctx->d_sub_seen, seen_tag, ctx->d_frame_sync + 4);
+    const unsigned mark_threads = dev_order && nb_max > cap ? nb_max : cap;
+    hipLaunchKernelGGL(k_select_mark, dim3((mark_threads + 255) / 256), dim3(256), 0, st, T.keyw, T.minw, cap, T.epoch16, b_flag.as<int>(),
+                       b_keyat.as<unsigned long long>(), dev_order ? b_bcnt.as<int>() : (int *)nullptr, dev_order ? nb_max : 0u);
+    if (dev_order) {
+        srl_scan(SrlIntArrayIn{b_flag.as<int>()}, SubRankSink{b_keyat.as<unsigned long long>(), b_hash.as<unsigned long long>(), b_first.as<unsigned>(),
+                                                              b_order.as<int>()},
+                 n, b_sc.as<int>(), st, CountFin{ctx->d_frame_sync});
+        hipLaunchKernelGGL(k_tr1_bucket, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
+                           b_bcnt.as<int>(), b_members.as<unsigned long long>(), b_elem.as<unsigned>(), h_ctrl, tag);
+        srl_scan(SrlIntArrayIn{b_bcnt.as<int>()}, SrlIntArraySink{b_bstart.as<int>()}, (int)nb_max, b_sc.as<int>(), st);
+        hipLaunchKernelGGL(k_tr1_rank<false>, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
+                           b_first.as<unsigned>(), b_members.as<unsigned long long>(), b_bcnt.as<int>(), b_bstart.as<int>(), b_elem.as<unsigned>(),
+                           (const double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, ctx->d_sub_kept);
+    } else {
+        srl_scan(SrlIntArrayIn{b_flag.as<int>()}, EmitSink{b_keyat.as<unsigned long long>(), h_hash, first}, n, b_sc.as<int>(), st,
+                 EmitFin{ctx->d_frame_sync, h_ctrl, tag});
+    }
+    HIPCHK(ctx, hipGetLastError());
+    tp1 = std::chrono::steady_clock::now();
+    unsigned long long ctrl = 0;
+    { const int rcw = wait_frame_word(ctx, h_ctrl, tag, "frame sub-sample", &ctrl); if (rcw) return rcw; }
+    tp2 = std::chrono::steady_clock::now();
+    if ((unsigned)ctrl & SRL_CTRL_BAD_ORDER) { ctx->err = "visit order is not a permutation of 0..n-1"; return SRL_ERR_BAD_ARG; }
+    const int m = (int)((unsigned)ctrl & SRL_CTRL_COUNT_MASK);
+    const bool overflow = dev_order && (((unsigned)ctrl >> 31) & 1u);
+    ctx->frame_order_used = dev_order ? (overflow ? 3 : 1) : 2;
+    if (!dev_order || overflow) {
+        // the host replay of the container's order over the m voxels (host/tr1_order.h), as keypoint selection does it; the device path left
+        // first = sweep indices, the host path first = visit ranks
+        if (overflow) {
+            HIPCHK(ctx, hipMemcpyAsync(h_hash, b_hash.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipMemcpyAsync(first, b_first.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+        }
+        std::vector<int> perm((size_t)m);
+        srl::Tr1Order::order(reinterpret_cast<const std::size_t *>(h_hash), m, perm.data());
+        for (int r = 0; r < m; r++) {
+            const unsigned f = first[(size_t)perm[(size_t)r]];
+            h_kept[r] = overflow ? (int)f : visit_order[f];
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_sub_kept, h_kept, (size_t)m * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));      // (the exchange block is the next chain's)
+    }
+    tp3 = std::chrono::steady_clock::now();
+    ctx->sub_n = m;
+    *num_kept = m;
+    if (trace) {
+        auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        std::fprintf(stderr, "[srl_frame_subsample] n %d -> %d (order %d): enqueue %.0f us, wait %.0f us, host order replay %.0f us\n", n, m,
+                     ctx->frame_order_used, us(tp0, tp1), us(tp1, tp2), us(tp2, tp3));
+    }
+    return SRL_OK;
+}
+
+int srl_frame_take_subsampled(srl_ctx *ctx, const int32_t *perm, int m, int32_t *index_out, double *raw_out, double *imu_out) {
+    if (!ctx || m < 0) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    if (ctx->corr_n < 0 || ctx->sub_n < 0) { ctx->err = "no sub-sample of an undistorted sweep (srl_frame_subsample first)"; return SRL_ERR_NO_SWEEP; }
+    if (m != ctx->sub_n) { ctx->err = "m is not the voxel count of the sub-sample"; return SRL_ERR_BAD_ARG; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_frame(ctx, m);
+    if (rc) return rc;
+    ctx->frame_n = m;
+    ctx->frame_world_n = -1;
+    if (m == 0) return SRL_OK;
+    hipStream_t st = ctx->stream;
+    unsigned seen_tag = 0;
+    { const int rcs = sub_seen_begin(ctx, &seen_tag); if (rcs) return rcs; }
+    DevBuf b_perm, b_idx, b_imu;
+    if (perm) {
+        HIPCHK(ctx, b_perm.alloc(ctx, (size_t)m * 4));
+        HIPCHK(ctx, hipMemcpyAsync(b_perm.p, perm, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    }
+    if (index_out) HIPCHK(ctx, b_idx.alloc(ctx, (size_t)m * 4));
+    if (imu_out) HIPCHK(ctx, b_imu.alloc(ctx, (size_t)m * 24));
+    int rcx = ensure_frame_exchange(ctx, 64);
+    if (rcx) return rcx;
+    unsigned *h_bad = reinterpret_cast<unsigned *>(ctx->h_frame_x + 8);      // (word 0 is the count word of the chains)
+    __atomic_store_n(h_bad, 0u, __ATOMIC_RELEASE);
+    hipLaunchKernelGGL(k_sub_take, dim3((m + 255) / 256), dim3(256), 0, st, ctx->d_sub_kept, perm ? b_perm.as<int>() : (const int *)nullptr, m,
+                       ctx->d_sub_seen, seen_tag, ctx->d_corr_raw, ctx->d_corr_imu, ctx->d_frame_raw, index_out ? b_idx.as<int>() : (int *)nullptr,
+                       imu_out ? b_imu.as<double>() : (double *)nullptr, h_bad);
+    HIPCHK(ctx, hipGetLastError());
+    if (index_out) HIPCHK(ctx, hipMemcpyAsync(index_out, b_idx.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    if (raw_out) HIPCHK(ctx, hipMemcpyAsync(raw_out, ctx->d_frame_raw, (size_t)m * 24, hipMemcpyDeviceToHost, st));
+    if (imu_out) HIPCHK(ctx, hipMemcpyAsync(imu_out, b_imu.p, (size_t)m * 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (__atomic_load_n(h_bad, __ATOMIC_ACQUIRE)) {
+        ctx->frame_n = -1;                                   // (the resident frame was partly overwritten)
+        ctx->err = "perm is not a permutation of 0..m-1";
+        return SRL_ERR_BAD_ARG;
+    }
+    return SRL_OK;
+}
+
 int srl_frame_upload(srl_ctx *ctx, const double *raw_xyz, int n) {
     if (!ctx || n < 0 || (n > 0 && !raw_xyz)) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);
@@ -626,30 +911,8 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
         while (cap < 2u * (unsigned)n) cap <<= 1;
         // the keypoint ORDER on the device (see "keypoint ORDER on the device" above) when the bucket table of n voxels fits one scan launch
         unsigned nb_max = 0;
-        bool dev_order = ctx->frame_order_mode == 0 && n <= SRL_SCAN_MAX;
-        if (dev_order) {
-            if (ctx->tr1_steps < 0) {
-                SrlTr1Sched S;
-                std::memset(&S, 0, sizeof S);
-                const int steps = srl::Tr1Order::export_schedule(SRL_SCAN_MAX, S.first, S.nb, SRL_TR1_MAX_STEPS);
-                if (steps >= 0) {
-                    S.steps = steps;
-                    HIPCHK(ctx, hipMalloc((void **)&ctx->d_tr1_sched, sizeof S));
-                    HIPCHK(ctx, hipMemcpy(ctx->d_tr1_sched, &S, sizeof S, hipMemcpyHostToDevice));
-                    std::memcpy(ctx->tr1_first, S.first, sizeof S.first);
-                    std::memcpy(ctx->tr1_nb, S.nb, sizeof S.nb);
-                    ctx->tr1_steps = steps;
-                } else {
-                    ctx->tr1_steps = -2;                                      // a growth policy this table cannot hold: host replay from now on
-                }
-            }
-            if (ctx->tr1_steps >= 0) {
-                int g = 0;
-                while (g < ctx->tr1_steps && ctx->tr1_first[g] <= (unsigned)n) ++g;
-                nb_max = ctx->tr1_nb[g];
-            }
-            dev_order = ctx->tr1_steps >= 0 && nb_max > 0 && nb_max <= (1u << 23);       // (srl_scan takes any size; the member lists are 128 B per bucket)
-        }
+        { const int rco = tr1_device_order(ctx, n, &nb_max); if (rco) return rco; }
+        const bool dev_order = nb_max > 0;
         DevBuf b_flag, b_keyat, b_hash, b_first, b_bcnt, b_members, b_elem, b_bstart, b_sel, b_sc;
         HIPCHK(ctx, b_flag.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_keyat.alloc(ctx, (size_t)n * 8));
         HIPCHK(ctx, b_sc.alloc(ctx, srl_scan_scratch_ints(std::max(n, (int)nb_max)) * 4));      // tile sums of the scans beyond one launch (srl_scan)
@@ -686,7 +949,7 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
             hipLaunchKernelGGL(k_tr1_bucket, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
                                b_bcnt.as<int>(), b_members.as<unsigned long long>(), b_elem.as<unsigned>(), h_ctrl, tag);
             srl_scan(SrlIntArrayIn{b_bcnt.as<int>()}, SrlIntArraySink{b_bstart.as<int>()}, (int)nb_max, b_sc.as<int>(), st);
-            hipLaunchKernelGGL(k_tr1_rank, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
+            hipLaunchKernelGGL(k_tr1_rank<true>, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
                                b_first.as<unsigned>(), b_members.as<unsigned long long>(), b_bcnt.as<int>(), b_bstart.as<int>(), b_elem.as<unsigned>(),
                                ctx->d_frame_raw, sx, sy, sz, b_sel.as<int>());
         } else {
@@ -697,18 +960,8 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
         HIPCHK(ctx, hipGetLastError());
         srl_stage_end(ctx, 1);
         tp1 = std::chrono::steady_clock::now();
-        // wait for the control word (the stream is looked at every ~1M polls: a fault must not become a hang)
-        unsigned long long ctrl = 0, spins = 0;
-        while ((unsigned)((ctrl = __atomic_load_n(h_ctrl, __ATOMIC_ACQUIRE)) >> 32) != tag) {
-            if ((++spins & 0xFFFFF) == 0) {
-                const hipError_t qe = hipStreamQuery(st);
-                if (qe != hipSuccess && qe != hipErrorNotReady) { ctx->err = std::string("keypoint selection: ") + hipGetErrorString(qe); return SRL_ERR_HIP; }
-                if (qe == hipSuccess && (unsigned)(__atomic_load_n(h_ctrl, __ATOMIC_ACQUIRE) >> 32) != tag) {
-                    ctx->err = "keypoint selection finished without publishing its voxel list";
-                    return SRL_ERR_HIP;
-                }
-            }
-        }
+        unsigned long long ctrl = 0;
+        { const int rcw = wait_frame_word(ctx, h_ctrl, tag, "keypoint selection", &ctrl); if (rcw) return rcw; }
         const int S = (int)((unsigned)ctrl & 0x7FFFFFFFu);
         const bool overflow = dev_order && (((unsigned)ctrl >> 31) & 1u);
         srl_stage_end(ctx, 2);

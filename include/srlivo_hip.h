@@ -100,6 +100,24 @@ int srl_map_upload(srl_ctx *ctx, const int16_t *keys_xyz /* V x 3 */, const int3
  * order-dependent insert of world points (AoS n x 3, FP64) into the device-resident map. */
 int srl_map_insert(srl_ctx *ctx, const double *world_xyz, int n, double voxel_size, int cap,
                    double min_distance_points, int min_num_points, int *num_added);
+/* The same insertion, reporting what it stored: what addPointToMap hands to addPointToPcl (lioOptimization.cpp:428-429, 1346-1355) and
+ * addPointsToMap publishes as cloud_world (:552-553).  outcome[i] (n bytes, batch order): 0 = not stored (voxel full, closer than
+ * min_distance_points to a resident, min_num_points not met, or no voxel and min_num_points > 0), 1 = appended to a voxel that existed
+ * when the point's turn came (one created by an EARLIER point of the batch included), 2 = created its voxel.  cloud (capacity n): the
+ * points with outcome 1 in ascending batch index -- voxel creators are stored but not published, as in the reference -- with x, y, z the
+ * FP32 position the map holds and intensity = (float)(50.0 * ((double)z - ref_z)), ref_z = p_frame->p_state->translation.z().
+ * count(outcome != 0) == *num_added.  outcome, cloud, num_cloud and num_added are each optional.  The map ends up exactly as after
+ * srl_map_insert, every n srl_map_insert accepts is accepted (SRL_MAP_INSERT_REPORT_MAX_POINTS), and like it the call cancels an armed
+ * launch, folds a deferred insert in first and voids the neighbourhood bounds.  Always synchronous: it waits for the device once (the
+ * record count) and then moves num_cloud records in one DMA.  NULL ctx or NULL points with n > 0: SRL_ERR_BAD_ARG with both counts
+ * written as 0, before any device is touched; cap != 20: SRL_ERR_UNSUPPORTED; n == 0: SRL_OK, counts 0.  With a communicator the call
+ * acts on this rank's map as srl_map_insert does (the map is replicated: every rank inserts the same batch); not tested on several ranks. */
+typedef struct srl_cloud_point { float x, y, z, intensity; } srl_cloud_point;   /* the payload of pcl::PointXYZI */
+#define SRL_MAP_INSERT_REPORT_MAX_POINTS 2147483647      /* no limit of its own: INT_MAX, as srl_map_insert */
+int srl_map_insert_report(srl_ctx *ctx, const double *world_xyz, int n, double voxel_size, int cap,
+                          double min_distance_points, int min_num_points, double ref_z,
+                          uint8_t *outcome /* n or NULL */, srl_cloud_point *cloud /* capacity n, or NULL */,
+                          int *num_cloud /* or NULL */, int *num_added /* or NULL */);
 /* replaces lioOptimization::mapSize (lioOptimization.cpp:574-581) */
 int srl_map_size(srl_ctx *ctx, int64_t *num_points, int32_t *num_voxels);
 /* copies the device map back in creation order (same layout as srl_map_upload) */
@@ -235,6 +253,12 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
 int srl_frame_commit(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9], const double t_il[3],
                      double voxel_size, int cap, double min_distance_points, int min_num_points,
                      double *world_out /* n x 3 or NULL */, int *num_added /* or NULL */);
+/* srl_frame_commit + the report of srl_map_insert_report on the resident frame (ref_z = t[2]; the re-transform stays fused into the
+ * insertion's first kernel).  Never deferred, whatever is NULL; world_out is bitwise what srl_frame_commit gives. */
+int srl_frame_commit_report(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9], const double t_il[3],
+                            double voxel_size, int cap, double min_distance_points, int min_num_points,
+                            double *world_out /* n x 3 or NULL */, uint8_t *outcome /* n or NULL */,
+                            srl_cloud_point *cloud /* capacity n, or NULL */, int *num_cloud /* or NULL */, int *num_added /* or NULL */);
 /* num_added == NULL (addPointsToMap returns nothing either): the insertion is enqueued behind the re-transform and the call returns as
  * soon as world_out (if asked for) has arrived; the passes of the next sweep are ordered behind the insertion on the context's stream,
  * and the map's totals are brought up to date by the next call that reads them (srl_map_size, srl_map_download, the next insertion). */

@@ -53,6 +53,14 @@ int srl_lio_map_size(srl_lio *lio, int64_t *num_points);
  * srl_lio_run_measurement does the same with srl_lio_remove_points_far_from_location(lio, result.state + 4, max_distance) after every
  * processed, successful measurement. */
 int srl_lio_remove_points_far_from_location(srl_lio *lio, const double location[3], double distance);
+/* points_world (include/lioOptimization.h:262): the cloud addPointsToMap publishes as cloud_world (lioOptimization.cpp:552-553) -- the
+ * points the last insertion of this handle (srl_lio_add_points_to_map, srl_lio_commit_frame, the commit inside srl_lio_run_measurement)
+ * appended to voxels that already existed, see srl_map_insert_report.  Off by default; while on, those insertions go through the
+ * synchronous report calls (a commit with num_added == NULL is then not deferred).  srl_lio_points_world copies the records out: *n is
+ * their number; capacity 0 asks for the number alone, a smaller non-zero capacity is SRL_ERR_BAD_ARG.  The cloud stays until the next
+ * insertion.  A host-only handle has no map: SRL_ERR_NO_DEVICE with *n = 0. */
+int srl_lio_set_collect_points_world(srl_lio *lio, int on);
+int srl_lio_points_world(srl_lio *lio, srl_cloud_point *out, int capacity, int *n);
 /* Where lioOptimization::buildFrame sub-samples the cut sweep (subSampleFrame, lioOptimization.cpp:838-846): on = 1 (the default) on the
  * device (srl_frame_subsample + srl_frame_take_subsampled; the host runs the two shuffles on index arrays and downloads m points), 0 = on the
  * host over the n-point downloads of srl_frame_undistort and srl_frame_take.  Both give the same frame bit for bit. */

@@ -50,6 +50,14 @@ class Frame(C.Structure):
                 ("R_il", C.c_double * 9), ("t_il", C.c_double * 3), ("frame_id", C.c_int32)]
 
 
+class CloudPoint(C.Structure):
+    """srl_cloud_point: one record of cloud_world (the payload of pcl::PointXYZI)"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("intensity", C.c_float)]
+
+
+CLOUD_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])      # cloud.view(CLOUD_POINT_DTYPE)
+
+
 class NormalEq(C.Structure):
     _fields_ = [("HtH", C.c_double * 36), ("Hth", C.c_double * 6), ("loss_sum", C.c_double),
                 ("num_residuals", C.c_int32), ("success", C.c_int32), ("sum_candidates", C.c_int64),
@@ -113,6 +121,8 @@ def load_library():
         "srl_icp_opts_default": ([C.POINTER(IcpOpts)], None),
         "srl_map_upload": ([p, p, p, p, C.c_int, C.c_int], C.c_int),
         "srl_map_insert": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_map_insert_report": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, p, p, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int)], C.c_int),
         "srl_map_size": ([p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)], C.c_int),
         "srl_map_download": ([p, p, p, p, C.c_int], C.c_int),
         "srl_map_remove_far": ([p, dp, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64)], C.c_int),
@@ -142,6 +152,8 @@ def load_library():
         "srl_frame_take_subsampled": ([p, p, C.c_int, p, p, p], C.c_int),
         "srl_frame_size": ([p, C.POINTER(C.c_int)], C.c_int),
         "srl_frame_select_keypoints": ([p, dp, dp, dp, dp, C.c_double, p, C.POINTER(C.c_int)], C.c_int),
+        "srl_frame_commit_report": ([p, dp, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_int, p, p, p, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int)], C.c_int),
         "srl_frame_commit": ([p, dp, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_int, p, C.POINTER(C.c_int)], C.c_int),
         "srl_comm_unique_id": ([p], C.c_int),
         "srl_comm_init_rank": ([p, C.c_int, C.c_int, p], C.c_int),
@@ -203,6 +215,8 @@ def load_library():
         "srl_lio_add_points_to_map": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
         "srl_lio_map_size": ([p, C.POINTER(C.c_int64)], C.c_int),
         "srl_lio_remove_points_far_from_location": ([p, dp, C.c_double], C.c_int),
+        "srl_lio_set_collect_points_world": ([p, C.c_int], C.c_int),
+        "srl_lio_points_world": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_set_device_subsample": ([p, C.c_int], C.c_int),
         "srl_lio_probe_checksum_of_committed_frame": ([p, C.c_int, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)], C.c_int),
         "srl_lio_resident_sweep": ([p, p, C.c_int], C.c_int),
@@ -425,6 +439,19 @@ class Context:
         added = C.c_int()
         self._chk(self.lib.srl_map_insert(self.h, _ptr(w), len(w), voxel_size, cap, min_dist, min_num_points, C.byref(added)), "srl_map_insert")
         return added.value
+
+    def map_insert_report(self, world_xyz, voxel_size=1.0, cap=20, min_dist=0.15, min_num_points=0, ref_z=0.0):
+        """srl_map_insert_report: map_insert that also says what it stored.  Returns (outcome, cloud, num_added): outcome uint8 per point
+        (0 not stored, 1 appended to an existing voxel, 2 created its voxel), cloud (m, 4) float32 rows x, y, z, intensity of the
+        appended points in batch order (cloud_world; intensity = 50 (z - ref_z))."""
+        w = _f64(world_xyz, (-1, 3))
+        n = len(w)
+        outcome = np.zeros(n, dtype=np.uint8)
+        cloud = np.zeros((n, 4), dtype=np.float32)
+        m, added = C.c_int(), C.c_int()
+        self._chk(self.lib.srl_map_insert_report(self.h, _ptr(w), n, voxel_size, cap, min_dist, min_num_points, float(ref_z), _ptr(outcome), _ptr(cloud),
+                                                 C.byref(m), C.byref(added)), "srl_map_insert_report")
+        return outcome, cloud[: m.value].copy(), added.value
 
     def map_size(self):
         npnt, nv = C.c_int64(), C.c_int32()
@@ -719,6 +746,22 @@ class Context:
                   "srl_frame_commit")
         return world, (added.value if want_added else None)
 
+    def frame_commit_report(self, q, t, voxel_size=1.0, cap=20, min_dist=0.15, min_num_points=0, R_il=None, t_il=None, want_world=False):
+        """srl_frame_commit_report: frame_commit with the report of map_insert_report (ref_z = t[2]).  Returns (outcome, cloud, num_added),
+        or (outcome, cloud, num_added, world) with want_world."""
+        R_il = _f64(np.eye(3) if R_il is None else R_il).ravel()
+        t_il = _f64(np.zeros(3) if t_il is None else t_il)
+        n = self.frame_size()
+        world = np.empty((n, 3)) if want_world else None
+        outcome = np.zeros(n, dtype=np.uint8)
+        cloud = np.zeros((n, 4), dtype=np.float32)
+        m, added = C.c_int(), C.c_int()
+        self._chk(self.lib.srl_frame_commit_report(self.h, _dptr(_f64(q)), _dptr(_f64(t)), _dptr(R_il), _dptr(t_il), float(voxel_size), cap,
+                                                   float(min_dist), min_num_points, _ptr(world), _ptr(outcome), _ptr(cloud), C.byref(m),
+                                                   C.byref(added)), "srl_frame_commit_report")
+        out = (outcome, cloud[: m.value].copy(), added.value)
+        return out + (world,) if want_world else out
+
     # --- multi-GPU
     @staticmethod
     def comm_unique_id():
@@ -907,6 +950,20 @@ class Lio:
         """lioOptimization::removePointsFarFromLocation on the device map (srl_map_remove_far)"""
         loc = _f64(location).ravel()
         self._chk(self.lib.srl_lio_remove_points_far_from_location(self.h, _dptr(loc), float(distance)), "remove_points_far_from_location")
+
+    def set_collect_points_world(self, on):
+        """collect lioOptimization::points_world (cloud_world) at every insertion of this object; off by default (the collecting
+        insertions are synchronous, see srl_lio_set_collect_points_world)"""
+        self._chk(self.lib.srl_lio_set_collect_points_world(self.h, 1 if on else 0), "srl_lio_set_collect_points_world")
+
+    def points_world(self):
+        """the cloud the last insertion left: (m, 4) float32 rows x, y, z, intensity (empty while the switch is off)"""
+        m = C.c_int()
+        self._chk(self.lib.srl_lio_points_world(self.h, None, 0, C.byref(m)), "srl_lio_points_world")
+        cloud = np.zeros((m.value, 4), dtype=np.float32)
+        if m.value:
+            self._chk(self.lib.srl_lio_points_world(self.h, _ptr(cloud), m.value, C.byref(m)), "srl_lio_points_world")
+        return cloud
 
     def set_device_subsample(self, on):
         """buildFrame's sub-sample on the device (True, the default) or on the host (srl_lio_set_device_subsample)"""

@@ -484,6 +484,17 @@ void lioOptimization::addPointsToMap(voxelHashMap &map, cloudFrame *p_frame, dou
     const int n = (int)p_frame->point_frame.size();
     std::vector<double> xyz((size_t)n * 3);
     for (int k = 0; k < n; k++) for (int d = 0; d < 3; d++) xyz[(size_t)k * 3 + d] = p_frame->point_frame[k].point[d];
+    points_world.clear();
+    if (collect_points_world) {
+        // addPointToPcl (lioOptimization.cpp:1346-1355) for every point appended to an existing voxel (:428-429)
+        points_world.resize((size_t)n);
+        int m = 0;
+        const int rc = srl_map_insert_report(map.ctx, xyz.data(), n, voxel_size, max_num_points_in_voxel, min_distance_points, min_num_points,
+                                             p_frame->p_state->translation[2], nullptr, points_world.data(), &m, nullptr);
+        points_world.resize(rc == SRL_OK ? (size_t)m : 0);
+        check(map.ctx, rc, "srl_map_insert_report");
+        return;
+    }
     check(map.ctx, srl_map_insert(map.ctx, xyz.data(), n, voxel_size, max_num_points_in_voxel, min_distance_points, min_num_points, nullptr),
           "srl_map_insert");
 }
@@ -732,6 +743,10 @@ optimizeSummary lioOptimization::stateEstimation(cloudFrame *p_frame) {
     std::vector<double> world(download_frame_points ? (size_t)n * 3 : 0);
     last_points_added = commitFrame(&commit_pose, kSizeVoxelMap, max_num_points_in_voxel, min_distance_points, 0,
                                     download_frame_points && n > 0 ? world.data() : nullptr);
+    // addPointToPcl reads p_frame->p_state->translation.z() (lioOptimization.cpp:1352); the first frame is committed with the identity
+    // pose its points were built with, so its records get the frame's own translation here (the same FP64 expression, rounded once)
+    if (collect_points_world && p_frame->frame_id <= 1)
+        for (srl_cloud_point &r : points_world) r.intensity = (float)(50.0 * ((double)r.z - p_frame->p_state->translation[2]));
     if (download_frame_points && p_frame->frame_id > 1)
         for (int k = 0; k < n; k++) p_frame->point_frame[k].point = srl::vec3(world[(size_t)k * 3], world[(size_t)k * 3 + 1], world[(size_t)k * 3 + 2]);
     return optimize_summary;
@@ -864,6 +879,17 @@ int lioOptimization::commitFrame(const state *p_state, double voxel_size, int ma
     if (!ctx) throw std::runtime_error("addPointsToMap: no HIP context (the product has no CPU path)");
     const double qv[4] = {p_state->rotation.w, p_state->rotation.x, p_state->rotation.y, p_state->rotation.z};
     int added = -1;
+    points_world.clear();
+    if (collect_points_world) {
+        int n = 0, m = 0;
+        check(ctx, srl_frame_size(ctx, &n), "srl_frame_size");
+        points_world.resize((size_t)(n > 0 ? n : 0));
+        const int rc = srl_frame_commit_report(ctx, qv, p_state->translation.a, R_imu_lidar.a, t_imu_lidar.a, voxel_size, max_num_points_in_voxel,
+                                               min_distance_points, min_num_points, world_out, nullptr, points_world.data(), &m, &added);
+        points_world.resize(rc == SRL_OK ? (size_t)m : 0);
+        check(ctx, rc, "srl_frame_commit_report");
+        return want_added ? added : -1;
+    }
     check(ctx, srl_frame_commit(ctx, qv, p_state->translation.a, R_imu_lidar.a, t_imu_lidar.a, voxel_size, max_num_points_in_voxel,
                                 min_distance_points, min_num_points, world_out, want_added ? &added : nullptr), "srl_frame_commit");
     return added;

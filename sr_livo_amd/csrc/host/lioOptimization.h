@@ -189,6 +189,14 @@ public:
     std::vector<imuMeas> imu_meas;
     double current_time = -1, last_time_frame = -1, dt_sum = 0;         // lioOptimization.cpp:353-357
     int last_frame_keypoints = 0, last_frame_points = 0, last_points_added = 0;
+    // points_world (include/lioOptimization.h:262; filled by addPointToPcl at lioOptimization.cpp:429, published as cloud_world at :552-553):
+    // the points the last addPointsToMap / commitFrame APPENDED to voxels that already existed, in frame order, as pcl::PointXYZI payloads.
+    // Cleared at the start of both; filled only while the switch is on (srl_map_insert_report / srl_frame_commit_report, which are
+    // synchronous: with the switch off process() keeps its deferred commit).  The reference clears the cloud after publishing it; here
+    // it stays until the next insertion so that the caller can publish it.
+    std::vector<srl_cloud_point> points_world;
+    void setCollectPointsWorld(bool on) { collect_points_world = on; }
+    bool collectPointsWorld() const { return collect_points_world; }
 
     // ---- ours ----
     // pin a sweep in HBM (bench: inputs resident before the timed region): solveIEKF() then runs on it.  updateIEKF()
@@ -240,6 +248,7 @@ private:
     int pending_prefetch_n = -1;
     int pending_prefetch_rc = 0;
     bool sweep_pinned = false;
+    bool collect_points_world = false;
 };
 
 }  // namespace srlivo

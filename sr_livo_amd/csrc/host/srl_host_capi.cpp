@@ -225,6 +225,22 @@ int srl_lio_remove_points_far_from_location(srl_lio *h, const double location[3]
     return SRL_OK;
 }
 
+int srl_lio_set_collect_points_world(srl_lio *h, int on) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    h->lio->setCollectPointsWorld(on != 0);
+    return SRL_OK;
+}
+int srl_lio_points_world(srl_lio *h, srl_cloud_point *out, int capacity, int *n) {
+    if (n) *n = 0;
+    if (!h || !n || capacity < 0 || (capacity > 0 && !out)) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device map, no points_world"; return SRL_ERR_NO_DEVICE; }
+    const std::vector<srl_cloud_point> &pw = h->lio->points_world;
+    *n = (int)pw.size();
+    if ((int)pw.size() > capacity) return capacity == 0 ? SRL_OK : SRL_ERR_BAD_ARG;     // capacity 0: the size query
+    if (!pw.empty()) std::memcpy(out, pw.data(), pw.size() * sizeof(srl_cloud_point));
+    return SRL_OK;
+}
+
 int srl_lio_set_device_subsample(srl_lio *h, int on) {
     if (!h) return SRL_ERR_BAD_ARG;
     h->lio->device_subsample = on != 0;

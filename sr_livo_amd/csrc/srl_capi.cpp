@@ -28,6 +28,8 @@ int srl_map_insert_device(struct srl_ctx *ctx, const double *world_xyz, int n, d
                           double min_distance_points, int min_num_points, int *num_added);
 
 #include "srl_ctx.h"
+int srl_map_insert_report_device(srl_ctx *ctx, const double *world_xyz, int n, double voxel_size, int cap, double min_distance_points, int min_num_points,
+                                 double ref_z, uint8_t *outcome, srl_cloud_point *cloud, int *num_cloud, int *num_added);
 
 namespace {
 
@@ -308,6 +310,16 @@ int srl_map_insert(srl_ctx *ctx, const double *world_xyz, int n, double voxel_si
     SRL_DISARM(ctx);
     if (cap != SRL_VOXEL_CAP) { ctx->err = "max_num_points_in_voxel must be 20"; return SRL_ERR_UNSUPPORTED; }
     return srl_map_insert_device(ctx, world_xyz, n, voxel_size, cap, min_distance_points, min_num_points, num_added);
+}
+
+int srl_map_insert_report(srl_ctx *ctx, const double *world_xyz, int n, double voxel_size, int cap, double min_distance_points, int min_num_points,
+                          double ref_z, uint8_t *outcome, srl_cloud_point *cloud, int *num_cloud, int *num_added) {
+    if (num_cloud) *num_cloud = 0;
+    if (num_added) *num_added = 0;
+    if (!ctx || n < 0 || (n > 0 && !world_xyz)) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    if (cap != SRL_VOXEL_CAP) { ctx->err = "max_num_points_in_voxel must be 20"; return SRL_ERR_UNSUPPORTED; }
+    return srl_map_insert_report_device(ctx, world_xyz, n, voxel_size, cap, min_distance_points, min_num_points, ref_z, outcome, cloud, num_cloud, num_added);
 }
 
 // ------------------------------------------------------------------------------------------ sweep

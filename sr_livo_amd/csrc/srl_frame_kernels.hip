@@ -31,7 +31,8 @@
 
 int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, int n, double voxel_size,
                         double min_distance_points, int min_num_points, int *num_added, bool defer_counters,
-                        const SrlFrameTransform *xf = nullptr, int (*after_first_kernel)(srl_ctx *, void *) = nullptr, void *user = nullptr);
+                        const SrlFrameTransform *xf = nullptr, int (*after_first_kernel)(srl_ctx *, void *) = nullptr, void *user = nullptr,
+                        const SrlInsertReport *report = nullptr);
 
 namespace {
 
@@ -1017,8 +1018,11 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
     return SRL_OK;
 }
 
-int srl_frame_commit(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9], const double t_il[3],
-                     double voxel_size, int cap, double min_distance_points, int min_num_points, double *world_out, int *num_added) {
+}  // extern "C"
+
+namespace {
+int frame_commit_impl(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9], const double t_il[3], double voxel_size, int cap,
+                      double min_distance_points, int min_num_points, double *world_out, int *num_added, const SrlInsertReport *report) {
     if (!ctx || !q || !t || !R_il || !t_il) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);
     if (cap != SRL_VOXEL_CAP) { ctx->err = "max_num_points_in_voxel must be 20"; return SRL_ERR_UNSUPPORTED; }
@@ -1061,11 +1065,26 @@ int srl_frame_commit(srl_ctx *ctx, const double q[4], const double t[3], const d
     }
     // num_added == NULL: the insert is only enqueued (its counters are folded in later, srl_map_settle); the caller's world points are
     // waited for on their own event, which fires long before the insert behind them is done
-    const int rci = srl_map_insert_impl(ctx, ctx->d_frame_world, true, n, voxel_size, min_distance_points, min_num_points, num_added, num_added == nullptr,
-                                        fused ? &xf : nullptr, fused ? +world_ready : nullptr, &dl);
+    const int rci = srl_map_insert_impl(ctx, ctx->d_frame_world, true, n, voxel_size, min_distance_points, min_num_points, num_added,
+                                        num_added == nullptr && !report, fused ? &xf : nullptr, fused ? +world_ready : nullptr, &dl, report);
     if (world_out && rci == SRL_OK) HIPCHK(ctx, hipEventSynchronize(ctx->ev_world));
     if (rci == SRL_OK) ctx->frame_world_n = n;            // d_frame_world = the frame as inserted (srl_map_probe_checksum)
     return rci;
 }
+}  // namespace
 
+extern "C" {
+int srl_frame_commit(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9], const double t_il[3],
+                     double voxel_size, int cap, double min_distance_points, int min_num_points, double *world_out, int *num_added) {
+    return frame_commit_impl(ctx, q, t, R_il, t_il, voxel_size, cap, min_distance_points, min_num_points, world_out, num_added, nullptr);
+}
+int srl_frame_commit_report(srl_ctx *ctx, const double q[4], const double t[3], const double R_il[9], const double t_il[3],
+                            double voxel_size, int cap, double min_distance_points, int min_num_points, double *world_out, uint8_t *outcome,
+                            srl_cloud_point *cloud, int *num_cloud, int *num_added) {
+    if (num_cloud) *num_cloud = 0;
+    if (num_added) *num_added = 0;
+    if (!ctx || !q || !t || !R_il || !t_il) return SRL_ERR_BAD_ARG;
+    const SrlInsertReport rep = {t[2], outcome, cloud, num_cloud};
+    return frame_commit_impl(ctx, q, t, R_il, t_il, voxel_size, cap, min_distance_points, min_num_points, world_out, num_added, &rep);
+}
 }  // extern "C"

@@ -27,6 +27,14 @@ struct SrlFrameTransform {
     double *world;           // where point3D::point goes (AoS); the insertion reads it from there
     SrlXf X;
 };
+// srl_map_insert_report / srl_frame_commit_report: where the insertion's report goes (host pointers, each optional) and translation.z()
+static_assert(sizeof(srl_cloud_point) == 16, "srl_cloud_point is written as one float4");
+struct SrlInsertReport {
+    double ref_z;
+    uint8_t *outcome;            // n bytes: 0 not stored, 1 appended, 2 created its voxel
+    srl_cloud_point *cloud;      // capacity n: the appended points in batch order
+    int *num_cloud;
+};
 
 // (struct SrlEpochTable: srl_ctx.h -- the context owns one for the selection and one for the insertion)
 

@@ -140,6 +140,60 @@ struct CreateSink {
 };
 
 
+// A bulk load sizes the map AFTER the segment scan has looked the touched voxels up (it needs the scan's segment count to do so).  When
+// that growth rebuilds the table, the slot indices the scan found belong to the old one: the segments that found their voxel look it up
+// again in the new table (one thread per segment; segments of new voxels keep -1 and are placed by CreateSink).
+__global__ void k_relookup(const int *seg_start, const unsigned long long *keys_sorted, const int *counters, const SrlMapSlot *table, unsigned mask,
+                           int *seg_slot) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= counters[0] || seg_slot[s] < 0) return;
+    const unsigned long long key = keys_sorted[seg_start[s]];
+    unsigned h = srl_hash_key(key) & mask;
+    int slot = -1;
+    for (unsigned probe = 0; probe <= mask; ++probe) {
+        const unsigned long long k = table[h].key;
+        if (k == key) { slot = (int)h; break; }
+        if (k == SRL_EMPTY_KEY) break;
+        h = (h + 1) & mask;
+    }
+    seg_slot[s] = slot;
+}
+
+// srl_map_insert_report / srl_frame_commit_report: what the insertion decided for every point of the batch (0 not stored, 1 appended to a
+// voxel that existed when its turn came, 2 created its voxel).  k_replay<true> writes the byte of every point it DECIDES straight to
+// outcome[batch index]; a point it never visits (behind the point that filled the voxel; a segment without a voxel when min_num_points > 0)
+// keeps the 0 this wrapper of the segment scan's sink stores for every position -- the kernel in front of the writer, no fill launch.
+struct SegmentSinkReport {
+    SegmentSink base;
+    unsigned char *outcome;
+    __device__ void operator()(int i, int head, int excl) const {
+        outcome[i] = 0;
+        base(i, head, excl);
+    }
+};
+// ... and the cloud (lioOptimization::addPointToPcl, lioOptimization.cpp:1346-1355, called at :429 only): the points with outcome 1 in
+// batch order, as the per-element work of the scan over (outcome == 1).  x, y, z = the FP32 position the slab holds; intensity =
+// 50 * (z - translation.z()) in FP64 (an FP32 z widened, one subtraction, one product: no contraction), rounded once.
+struct OutcomeAppended {
+    const unsigned char *outcome;
+    __device__ int operator()(int i) const { return outcome[i] == 1 ? 1 : 0; }
+};
+struct CloudSink {
+    const double *xyz;
+    double ref_z;
+    float4 *cloud;
+    int *num_cloud;                           // counters[3]
+    int n;
+    __device__ void operator()(int i, int appended, int excl) const {
+        if (appended) {
+            const float fx = (float)xyz[(size_t)i * 3], fy = (float)xyz[(size_t)i * 3 + 1], fz = (float)xyz[(size_t)i * 3 + 2];
+            cloud[excl] = make_float4(fx, fy, fz, (float)(50.0 * ((double)fz - ref_z)));
+        }
+        if (i == n - 1) *num_cloud = excl + appended;
+    }
+};
+
+
 // sequential replay of one voxel's segment (lioOptimization.cpp:409-445), one thread per voxel.  The kernel is latency bound,
 // not work bound: a 1 M-point batch touches 67 k voxels = ONE wave per SIMD, and every point costs its thread two dependent
 // memory round trips (sorted index -> coordinates, ~2 us together from HBM) before 20 compares.  So the incoming points are
@@ -152,10 +206,12 @@ struct CreateSink {
 // waves for a <= 20-wide compare); a hybrid -- this kernel for segments <= 48 points plus one WAVE per longer segment (chunks
 // of 64 points resolved in order with ballots) -- 157 + 131 us and 2.5 + 1.2 ms: the long segments were never the tail (a
 // dense voxel fills to 20 and stops), the per-point latency of the many short ones was.
+// REPORT: the outcome byte of every decided point (see SegmentSinkReport); the instance without it is the kernel as it was.
 #define SRL_REPLAY_BATCH 8
+template <bool REPORT>
 __global__ void __launch_bounds__(128) k_replay(const int *seg_start, const unsigned *sorted_idx, const int *counters, int n, const double *xyz,
                          const int *seg_slot, const unsigned char *is_new, SrlMapSlot *table, unsigned char *slabs,
-                         double voxel_size, double min_distance_points, int min_num_points, int *added_total) {
+                         double voxel_size, double min_distance_points, int min_num_points, int *added_total, unsigned char *outcome) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     const int S = counters[0];
     if (s >= S) return;
@@ -206,6 +262,7 @@ __global__ void __launch_bounds__(128) k_replay(const int *seg_start, const unsi
                 }
                 add = (sq_dist_min > min_d2) && (min_num_points <= 0 || count >= min_num_points);
             }
+            if (REPORT) outcome[idx[b]] = add ? (fresh && count == 0 ? 2 : 1) : 0;
             if (add) {
                 sl->xyz[count][0] = fx; sl->xyz[count][1] = fy; sl->xyz[count][2] = fz;
 #pragma unroll
@@ -448,7 +505,8 @@ int srl_ctx_grow_map(srl_ctx *ctx, unsigned need_slabs, unsigned need_slots) {
 
 int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, int n, double voxel_size,
                         double min_distance_points, int min_num_points, int *num_added, bool defer_counters,
-                        const SrlFrameTransform *xf = nullptr, int (*after_first_kernel)(srl_ctx *, void *) = nullptr, void *user = nullptr);
+                        const SrlFrameTransform *xf = nullptr, int (*after_first_kernel)(srl_ctx *, void *) = nullptr, void *user = nullptr,
+                        const SrlInsertReport *report = nullptr);
 
 // debug / parity hook: the frame path's own stable sort (srl_frame_scratch.h) on caller data
 extern "C" int srl_debug_radix_sort_pairs(srl_ctx *ctx, const uint32_t *keys, int n, int bits, uint32_t *keys_sorted, uint32_t *positions_sorted) {
@@ -476,6 +534,12 @@ int srl_map_insert_device(srl_ctx *ctx, const double *world_xyz, int n, double v
     (void)cap;
     return srl_map_insert_impl(ctx, world_xyz, false, n, voxel_size, min_distance_points, min_num_points, num_added, false);
 }
+int srl_map_insert_report_device(srl_ctx *ctx, const double *world_xyz, int n, double voxel_size, int cap, double min_distance_points, int min_num_points,
+                                 double ref_z, uint8_t *outcome, srl_cloud_point *cloud, int *num_cloud, int *num_added) {
+    (void)cap;
+    const SrlInsertReport rep = {ref_z, outcome, cloud, num_cloud};
+    return srl_map_insert_impl(ctx, world_xyz, false, n, voxel_size, min_distance_points, min_num_points, num_added, false, nullptr, nullptr, nullptr, &rep);
+}
 
 // world_xyz: host pointer, or (on_device) a device pointer that stays valid for the duration of the call.
 //
@@ -489,10 +553,14 @@ int srl_map_insert_device(srl_ctx *ctx, const double *world_xyz, int n, double v
 // defer_counters (frame-sized batches, num_added == NULL): return once everything is enqueued; the counters are folded into the
 // map's totals by srl_map_settle() -- at the next insert, srl_map_size, srl_map_download.  The solve that follows needs none of them
 // and is ordered behind the insert on the stream.
+// report (srl_map_insert_report / srl_frame_commit_report): the same kernels with k_replay<true>, the segment scan zeroing the outcome
+// bytes in front of it, and one more scan behind it that compacts the appended points into 16-byte records (CloudSink).  Never deferred:
+// the record count leaves with the counters, the call waits for them once and then moves `count` records in one DMA.
 int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, int n, double voxel_size,
                         double min_distance_points, int min_num_points, int *num_added, bool defer_counters,
-                        const SrlFrameTransform *xf, int (*after_first_kernel)(srl_ctx *, void *), void *user) {
+                        const SrlFrameTransform *xf, int (*after_first_kernel)(srl_ctx *, void *), void *user, const SrlInsertReport *report) {
     if (num_added) *num_added = 0;
+    if (report && report->num_cloud) *report->num_cloud = 0;
     if (n == 0) return SRL_OK;
     if (!(voxel_size > 0.0)) return SRL_ERR_BAD_ARG;
     ctx->bound_n = 0;                // the map changes: what the last pass learnt about its keypoints' neighbourhoods is void
@@ -520,7 +588,7 @@ int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, i
         }
     }
 
-    DevBuf b_xyz, b_keys2, b_idx, b_idx2, b_prefix, b_start, b_cnt, b_slot, b_isnew, b_first, b_newflag;
+    DevBuf b_xyz, b_keys2, b_idx, b_idx2, b_prefix, b_start, b_cnt, b_slot, b_isnew, b_first, b_newflag, b_outcome, b_cloud;
     const double *d_xyz = world_xyz;
     if (!on_device) {
         HIPCHK(ctx, b_xyz.alloc(ctx, (size_t)n * 3 * sizeof(double)));
@@ -532,11 +600,15 @@ int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, i
     HIPCHK(ctx, b_idx2.alloc(ctx, (size_t)n * 4));
     HIPCHK(ctx, b_prefix.alloc(ctx, (size_t)n * 4));
     HIPCHK(ctx, b_start.alloc(ctx, (size_t)n * 4));
-    HIPCHK(ctx, b_cnt.alloc(ctx, 64));                       // counters: [0] segments, [1] new voxels, [2] points added
+    HIPCHK(ctx, b_cnt.alloc(ctx, 64));                       // counters: [0] segments, [1] new voxels, [2] points added, [3] cloud records (report)
     HIPCHK(ctx, b_slot.alloc(ctx, (size_t)n * 4));
     HIPCHK(ctx, b_isnew.alloc(ctx, (size_t)n));
     HIPCHK(ctx, b_first.alloc(ctx, (size_t)n * 4));
     HIPCHK(ctx, b_newflag.alloc(ctx, (size_t)n * 4));
+    if (report) {
+        HIPCHK(ctx, b_outcome.alloc(ctx, (size_t)n));
+        HIPCHK(ctx, b_cloud.alloc(ctx, (size_t)n * sizeof(srl_cloud_point)));
+    }
     int *cnt = b_cnt.as<int>();
     srl_stage_begin(ctx);
     DevBuf b_sc;
@@ -567,15 +639,20 @@ int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, i
                              bits, st, sc_radix);
         HIPCHK(ctx, hipGetLastError());
         srl_stage_end(ctx, 7);                                    // slots + sort
-        srl_scan(HeadFlag32{b_slot_sorted.as<unsigned>()},
-                 SegmentSink{b_slot_sorted.as<unsigned>(), b_idx2.as<unsigned>(), T.keyw, b_start.as<int>(), b_keys2.as<unsigned long long>(), ctx->d_table,
-                             ctx->table_cap - 1, b_slot.as<int>(), b_isnew.as<unsigned char>(), min_num_points <= 0 ? b_newflag.as<int>() : (int *)nullptr,
-                             b_first.as<int>(), cnt, n}, n, sc_scan, st);
+        const SegmentSink seg_sink{b_slot_sorted.as<unsigned>(), b_idx2.as<unsigned>(), T.keyw, b_start.as<int>(), b_keys2.as<unsigned long long>(), ctx->d_table,
+                                   ctx->table_cap - 1, b_slot.as<int>(), b_isnew.as<unsigned char>(), min_num_points <= 0 ? b_newflag.as<int>() : (int *)nullptr,
+                                   b_first.as<int>(), cnt, n};
+        if (report) srl_scan(HeadFlag32{b_slot_sorted.as<unsigned>()}, SegmentSinkReport{seg_sink, b_outcome.as<unsigned char>()}, n, sc_scan, st);
+        else srl_scan(HeadFlag32{b_slot_sorted.as<unsigned>()}, seg_sink, n, sc_scan, st);
         HIPCHK(ctx, hipGetLastError());
     }
 
     srl_stage_end(ctx, 8);                                    // segments
-    int rcs = ensure_host_scratch(ctx, 64);
+    // the report of a frame-sized batch leaves through the page-locked scratch (a DMA each for the outcome bytes and the records; pageable
+    // destinations are staged by the runtime and cost more than the kernels around them) and is copied to the caller's arrays by the host
+    const bool stage_report = report && frame_sized;
+    const size_t stage_outcome = 64, stage_cloud = 64 + (((size_t)n + 63) / 64) * 64;
+    int rcs = ensure_host_scratch(ctx, stage_report ? stage_cloud + (size_t)n * sizeof(srl_cloud_point) : 64);
     if (rcs) return rcs;
     int *h_cnt = reinterpret_cast<int *>(ctx->h_scratch);
     if (!frame_sized) {
@@ -584,8 +661,14 @@ int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, i
         HIPCHK(ctx, hipStreamSynchronize(st));
         const unsigned need_slabs = (unsigned)ctx->num_voxels + (unsigned)h_cnt[0];
         if (need_slabs > ctx->slab_cap || SRL_TABLE_FACTOR * need_slabs > ctx->table_cap) {
+            const unsigned table_cap_before = ctx->table_cap;
             int rc = srl_ctx_grow_map(ctx, need_slabs, SRL_TABLE_FACTOR * need_slabs);
             if (rc) return rc;
+            if (ctx->table_cap != table_cap_before && ctx->num_voxels > 0 && h_cnt[0] > 0) {
+                hipLaunchKernelGGL(k_relookup, dim3((h_cnt[0] + 255) / 256), dim3(256), 0, st, b_start.as<int>(), b_keys2.as<unsigned long long>(), cnt,
+                                   ctx->d_table, ctx->table_cap - 1, b_slot.as<int>());
+                HIPCHK(ctx, hipGetLastError());
+            }
         }
     }
     const unsigned mask = ctx->table_cap - 1;
@@ -600,16 +683,39 @@ int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, i
         }
     }
     srl_stage_end(ctx, 9);                                    // lookup + creation
-    hipLaunchKernelGGL(k_replay, dim3((n + 127) / 128), dim3(128), 0, st, b_start.as<int>(), b_idx2.as<unsigned>(), cnt, n,
-                       d_xyz, b_slot.as<int>(), b_isnew.as<unsigned char>(), ctx->d_table, ctx->d_slabs, voxel_size,
-                       min_distance_points, min_num_points, cnt + 2);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_insert_cnt, cnt, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (report) {
+        hipLaunchKernelGGL(k_replay<true>, dim3((n + 127) / 128), dim3(128), 0, st, b_start.as<int>(), b_idx2.as<unsigned>(), cnt, n,
+                           d_xyz, b_slot.as<int>(), b_isnew.as<unsigned char>(), ctx->d_table, ctx->d_slabs, voxel_size,
+                           min_distance_points, min_num_points, cnt + 2, b_outcome.as<unsigned char>());
+        HIPCHK(ctx, hipGetLastError());
+        srl_scan(OutcomeAppended{b_outcome.as<unsigned char>()}, CloudSink{d_xyz, report->ref_z, b_cloud.as<float4>(), cnt + 3, n}, n, sc_scan, st);
+        HIPCHK(ctx, hipGetLastError());
+        if (report->outcome)
+            HIPCHK(ctx, hipMemcpyAsync(stage_report ? (void *)(ctx->h_scratch + stage_outcome) : (void *)report->outcome, b_outcome.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    } else {
+        hipLaunchKernelGGL(k_replay<false>, dim3((n + 127) / 128), dim3(128), 0, st, b_start.as<int>(), b_idx2.as<unsigned>(), cnt, n,
+                           d_xyz, b_slot.as<int>(), b_isnew.as<unsigned char>(), ctx->d_table, ctx->d_slabs, voxel_size,
+                           min_distance_points, min_num_points, cnt + 2, (unsigned char *)nullptr);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_insert_cnt, cnt, (report ? 4 : 3) * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipEventRecord(ctx->ev_insert, st));
     ctx->insert_pending = true;
-    if (defer_counters && frame_sized && !num_added && !ctx->frame_timing) return SRL_OK;
+    if (defer_counters && frame_sized && !num_added && !report && !ctx->frame_timing) return SRL_OK;
     { const int rcs = srl_map_settle(ctx); if (rcs) return rcs; }
     srl_stage_end(ctx, 10);                                   // replay + counters
     if (num_added) *num_added = ctx->h_insert_cnt[2];
+    if (report) {
+        // the records: ONE DMA of exactly `count` of them, now that the count is known (the outcome bytes went out in front of the counters)
+        const int m = ctx->h_insert_cnt[3];
+        const bool want_cloud = report->cloud && m > 0;
+        if (want_cloud)
+            HIPCHK(ctx, hipMemcpyAsync(stage_report ? (void *)(ctx->h_scratch + stage_cloud) : (void *)report->cloud, b_cloud.p, (size_t)m * sizeof(srl_cloud_point),
+                                       hipMemcpyDeviceToHost, st));
+        if (stage_report && report->outcome) std::memcpy(report->outcome, ctx->h_scratch + stage_outcome, (size_t)n);     // (landed in front of the counters)
+        if (want_cloud || !stage_report) HIPCHK(ctx, hipStreamSynchronize(st));
+        if (stage_report && want_cloud) std::memcpy(report->cloud, ctx->h_scratch + stage_cloud, (size_t)m * sizeof(srl_cloud_point));
+        if (report->num_cloud) *report->num_cloud = m;
+    }
     return SRL_OK;
 }

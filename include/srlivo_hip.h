@@ -32,7 +32,7 @@ typedef enum srl_status {
     SRL_ERR_NO_DEVICE = -1,     /* no HIP device / HIP runtime failure at create */
     SRL_ERR_HIP = -2,           /* a HIP call failed (see srl_last_error) */
     SRL_ERR_BAD_ARG = -3,
-    SRL_ERR_UNSUPPORTED = -4,   /* option outside the supported envelope (cap != 20, K > 32, nb_voxels > 2) */
+    SRL_ERR_UNSUPPORTED = -4,   /* option outside the supported envelope (cap != 20, K > 32, nb_voxels < 1 or > 2) */
     SRL_ERR_NO_MAP = -5,
     SRL_ERR_NO_SWEEP = -6,
     SRL_ERR_COMM = -7,          /* RCCL failure */

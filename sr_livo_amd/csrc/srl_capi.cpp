@@ -1545,8 +1545,8 @@ int srl_search_neighbors(srl_ctx *ctx, const double *world_xyz, int n, int nb_vo
     if (!ctx || n < 0 || (n > 0 && (!world_xyz || !ids || !num_found))) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);
     if (!ctx->d_table) return SRL_ERR_NO_MAP;
-    if (nb_voxels_visited < 1 || nb_voxels_visited > 2 || max_num_neighbors < 1 || max_num_neighbors > SRL_MAX_NEIGHBORS)
-        return SRL_ERR_UNSUPPORTED;
+    if (nb_voxels_visited < 1 || nb_voxels_visited > 2) { ctx->err = "nb_voxels_visited must be 1 or 2"; return SRL_ERR_UNSUPPORTED; }
+    if (max_num_neighbors < 1 || max_num_neighbors > SRL_MAX_NEIGHBORS) { ctx->err = "max_num_neighbors must be in [1,32]"; return SRL_ERR_UNSUPPORTED; }
     if (n == 0) return SRL_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int K = max_num_neighbors;

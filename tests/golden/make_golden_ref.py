@@ -12,6 +12,8 @@ The inputs are those of golden_small.npz (same scenes), so the two files are rea
   * tests/test_reference_tu.py (CPU): the oracle must reproduce these vectors BITWISE (also on the GPU box, where neither
     /root/reference nor a compiler for it exists);
   * tests/test_gpu_parity.py (GPU): the HIP path against the same vectors.
+golden_ref_tu_ragged.npz (ragged() below) carries its own inputs: the ragged-occupancy scene of tests/ragged_scene.py, read by
+tests/test_ragged_scene.py (CPU) and tests/test_gpu_option_envelope.py (GPU).
 """
 import os
 import sys
@@ -118,7 +120,45 @@ def main():
     path = os.path.join(HERE, "golden_ref_tu.npz")
     save_golden(path, data)
     print("wrote", path, "(+ _part2)", os.path.getsize(path) // 1024, "KiB")
+    ragged()
+
+
+RAGGED_KEYPOINTS = 1024
+# prefix, map ("map": 1.0 m voxels, "map08": 0.8 m voxels), icpOptions that differ from the defaults
+RAGGED_CASES = (("t5n1", "map", dict(threshold_voxel_occupancy=5, voxel_neighborhood=1, max_num_residuals=2**31 - 1)),
+                ("t12n2", "map", dict(threshold_voxel_occupancy=12, voxel_neighborhood=2, max_num_residuals=2**31 - 1)),
+                ("lowinertia", "map08", None))       # None: ragged_scene.LOW_INERTIA
+
+
+def ragged():
+    """golden_ref_tu_ragged.npz (`python tests/golden/make_golden_ref.py ragged` writes this file alone): the reference's accepted
+    residuals on the small ragged-occupancy scene of tests/ragged_scene.py, where threshold_voxel_occupancy changes which voxels
+    searchNeighbors visits -- (thr 5, nb 1), (thr 12, nb 2) and the icpOptions of defaultRobustOutdoorLowInertia on a 0.8 m map.
+    One file: it must stay below the 1 MiB a committed file may take."""
+    import ragged_scene as rs
+    backend = "tsl" if os.path.exists(po.LIB_TSL) else "plain"
+    seed, target, _ = rs.SMALL
+    data = dict(source=pr.load().ref_describe().decode())
+    maps = {}
+    for name, size in (("map", 1.0), ("map08", 0.8)):
+        sc = rs.ragged_scene(po, backend, seed, target, RAGGED_KEYPOINTS, voxel_size=size)
+        data[f"{name}_keys"] = sc["keys"]; data[f"{name}_counts"] = sc["counts"]; data[f"{name}_xyz"] = sc["xyz"]
+        maps[name] = pr.Map(sc["keys"], sc["counts"], sc["xyz"])
+    sw = sc["sweep"]
+    for k in ("raw", "q_pred", "t_pred", "t_last", "vel", "q_gt", "t_gt"):
+        data[k] = sw[k]
+    for prefix, which, kw in RAGGED_CASES:
+        opts = po.default_opts(**(rs.LOW_INERTIA if kw is None else kw))
+        r = one_pass(maps[which], opts, sw["raw"], sw["q_pred"], sw["t_pred"], sw["t_last"], 100, prefix, data)
+        print(prefix, "residuals", r["num_residuals"], "success", r["success"])
+    path = os.path.join(HERE, "golden_ref_tu_ragged.npz")
+    np.savez_compressed(path, **data)
+    assert os.path.getsize(path) < 2**20, os.path.getsize(path)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ragged"]:
+        ragged()
+    else:
+        main()

@@ -113,6 +113,9 @@ def test_voxel_hash_is_the_reference_functor():
                                                   (100, INT_MAX, dict(threshold_voxel_occupancy=5, max_dist_to_plane_icp=0.05)),
                                                   (100, INT_MAX, dict(power_planarity=1.5, weight_alpha=0.5, weight_neighborhood=0.7))])
 def test_build_plane_residuals_bitwise(scene, frame_id, max_res, kw):
+    # threshold_voxel_occupancy = 5 is INERT on small_scene: the map is saturated (no voxel holds fewer than 3 points, 80 % hold 20), the
+    # pass gives the same id rows and candidate sum at thresholds 1, 2, 5 and 12.  The threshold branch is pinned where it bites, on the
+    # ragged-occupancy scene: tests/test_ragged_scene.py::test_ragged_build_plane_residuals_bitwise
     sw = scene["sweep"]
     opts = po.default_opts(max_num_residuals=max_res, **kw)
     a = 0.3

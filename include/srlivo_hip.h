@@ -153,6 +153,67 @@ static inline uint64_t srl_probe_mix(int16_t kx, int16_t ky, int16_t kz, int32_t
 }
 int srl_map_probe_checksum(srl_ctx *ctx, const double *world_xyz, int n, int stride, double voxel_size, uint64_t *checksum);
 
+/* ------------------------------------------------------------------ colour voxel map (construction only)
+ * replaces: the second half of lioOptimization::addPointsToMap (lioOptimization.cpp:520-554) -- addPointToColorMap (:448-518) into
+ * color_voxel_map (lioOptimization.h), with rgb_points_vec (rgbMapTracker.h:40) deduplicated through the grid hashmap_3d_points
+ * (utility.h:94-141) and the list voxels_recent_visited_temp (lioOptimization.h:291).  The consumers of those containers (imageProcessing,
+ * rgbMapTracker, rendering, the publishers) stay with the caller; this is what they need to keep their own rgbPoint objects in step.
+ * For batch point i = 0, 1, ... where i % add_point_step == 0 (:538), with p = (float)world_i per axis (cloudMap.cpp:7):
+ *   k = short(p / size_voxel_map), g = short(p / min_distance_points), FP64 division of the FP32 value, 16-bit wrap included (:453-459);
+ *   stored     <=> the voxel k is new (created, slot 0) or holds fewer than max_num_points_in_voxel points (:470-474, :495-499): no
+ *                  distance test among residents, and min_num_points is the 0 of the reference's call (:539);
+ *   registered <=> stored and g not yet in the grid (:461-462, :476-483, :501-508): point_index = size of the registered list, g enters
+ *                  the grid.  A point a full voxel refuses neither registers nor claims g;
+ *   visited    <=> |time_sweep_end - time_last_process| > 1e-5 and |voxel.last_visited_time - time_sweep_end| > 1e-5 (:487-491, :510-514;
+ *                  a new voxel starts at 0.0): the voxel is stamped with time_sweep_end and listed once, in order of first touch,
+ *                  whether or not the point was stored.
+ * Every order comes from batch indices, none from arrival order: results are bitwise reproducible.  The LiDAR map, the neighbourhood
+ * bounds and the taps are not touched.  Device bytes do not depend on max_num_points_in_voxel: 24 per voxel,
+ * 24 per stored point, 4 per registered point, 16 per slot of the two open-addressing tables. */
+typedef struct srl_color_opts {          /* mapOptions (parameters.h:98-106) */
+    double  size_voxel_map;
+    int32_t max_num_points_in_voxel;     /* 1 ... 255 */
+    double  min_distance_points;         /* cell size of the de-duplication grid */
+    int32_t add_point_step;              /* >= 1 */
+} srl_color_opts;
+/* one stored point: position as stored (FP32), its voxel and slot there, its index in the batch, its index in the registered list or -1 */
+typedef struct srl_color_stored {
+    float    x, y, z;
+    int16_t  kx, ky, kz;
+    uint16_t slot;
+    int32_t  batch_index;
+    int32_t  point_index;
+} srl_color_stored;
+typedef struct srl_color_totals { int32_t stored, created, registered, visited; } srl_color_totals;   /* of one insertion */
+#define SRL_COLOR_MAP_INSERT_MAX_POINTS 1048576          /* the frame pipeline's limit */
+void srl_color_opts_default(srl_color_opts *o);          /* effective values of config/r3live.yaml:71-75: 0.1 / 50 / 0.01 / 1 */
+/* The options hold for the map's life.  SRL_ERR_BAD_ARG: NULL, a size that is not finite or <= 0, a cap outside 1 ... 255, a step < 1, or
+ * a colour map that already exists (destroy it first).  srl_ctx_destroy destroys the map with the context. */
+int srl_color_map_create(srl_ctx *ctx, const srl_color_opts *opts);
+int srl_color_map_destroy(srl_ctx *ctx);
+/* world_xyz: host points (n x 3, FP64), or NULL = the world points the last srl_frame_commit left in HBM (n is ignored; nothing crosses
+ * PCIe on the way in; SRL_ERR_NO_SWEEP when a newer frame has been uploaded since, SRL_ERR_BAD_ARG when no frame was ever committed).
+ * Outputs, each optional: outcome[n] (bit 0 stored, bit 1 created its voxel, bit 2 registered; 0 for a point the step skips or a full voxel
+ * refuses), the stored records in batch order, the visited list (int32 x 3 per voxel, voxelId, cloudMap.h:88) in order, and the totals.
+ * stored_capacity / visited_capacity (records / voxels; checked only where the pointer is given) must be at least the number of
+ * participating points ceil(n / add_point_step), else SRL_ERR_BAD_ARG before anything is done.  Synchronous: one wait for the counts,
+ * then one DMA per requested list.  n == 0: SRL_OK.  NULL ctx, n < 0 or n > SRL_COLOR_MAP_INSERT_MAX_POINTS: SRL_ERR_BAD_ARG; no colour
+ * map: SRL_ERR_NO_MAP; more than one rank: SRL_ERR_UNSUPPORTED -- all before a device is touched.  Cancels an armed launch.
+ * Contract: finite coordinates with |p / size| < 2^31. */
+int srl_color_map_insert(srl_ctx *ctx, const double *world_xyz, int n, double time_sweep_end, double time_last_process,
+                         uint8_t *outcome /* n or NULL */, srl_color_stored *stored /* or NULL */, int stored_capacity,
+                         int32_t *visited_xyz /* or NULL */, int visited_capacity, srl_color_totals *totals /* or NULL */);
+/* grid_cells == registered: a cell enters the grid with the point that registers (kept apart because the two containers are) */
+int srl_color_map_size(srl_ctx *ctx, int64_t *num_points, int32_t *num_voxels, int64_t *num_registered, int64_t *num_grid_cells);
+/* The map in creation order: per voxel its key, count and last_visited_time; the points voxel after voxel in slot order (xyz, and
+ * point_index = index in the registered list or -1), counts[v] of them for voxel v.  Every output optional; max_voxels / max_points are
+ * the capacities (SRL_ERR_BAD_ARG when the map is larger). */
+int srl_color_map_download(srl_ctx *ctx, int16_t *keys_xyz, int32_t *counts, double *last_visited_time, int max_voxels,
+                           float *xyz, int32_t *point_index, int64_t max_points);
+/* rgb_points_vec[first .. first + count): one record per registered point (batch_index = its position in the device's point pool,
+ * i.e. its rank among all stored points; point_index = its index in the list). */
+int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_color_stored *out);
+
 /* ------------------------------------------------------------------ sweep
  * replaces: the `keypoints` vector handed to updateIEKF (optimize.cpp:133; point3D::raw_point,
  * cloudMap.h:40).  AoS n x 3 FP64 in the lidar frame, in keypoint order.  Uploaded once per sweep.

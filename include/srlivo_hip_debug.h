@@ -29,6 +29,10 @@ int srl_debug_set_select_mode(srl_ctx *ctx, int select_mode);
  * positions_sorted (the position 0..n-1 each key came from) as a stable sort by (key & ((1 << bits) - 1)) would leave them. */
 int srl_debug_radix_sort_pairs(srl_ctx *ctx, const uint32_t *keys, int n, int bits, uint32_t *keys_sorted, uint32_t *positions_sorted);
 
+/* How often the colour map (srl_color_map_*) has rebuilt its voxel table / its grid set since it was created: both grow by rebuild
+ * (tests make sure a long run crosses several). */
+int srl_debug_color_map_rebuilds(srl_ctx *ctx, int32_t *voxel_table, int32_t *grid_table);
+
 int srl_debug_set_frame_order_mode(srl_ctx *ctx, int mode);
 int srl_debug_frame_order_used(srl_ctx *ctx, int *used);
 

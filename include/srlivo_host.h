@@ -61,6 +61,22 @@ int srl_lio_remove_points_far_from_location(srl_lio *lio, const double location[
  * insertion.  A host-only handle has no map: SRL_ERR_NO_DEVICE with *n = 0. */
 int srl_lio_set_collect_points_world(srl_lio *lio, int on);
 int srl_lio_points_world(srl_lio *lio, srl_cloud_point *out, int capacity, int *n);
+/* The colour half of addPointsToMap (lioOptimization.cpp:538-539, addPointToColorMap :448-518), opt-in.  srl_lio_set_color_map_options
+ * creates the device colour map (srl_color_map_create; opts NULL = srl_color_opts_default); from then on every insertion of this handle
+ * also runs srl_color_map_insert behind the LiDAR insertion -- the commits on the world points they left in HBM -- and keeps
+ * voxels_recent_visited_temp, voxels_recent_visited and number_of_new_visited_voxel as lioOptimization.cpp:523-550 do.  Without it the
+ * handle behaves exactly as before.  srl_lio_set_color_times: img_pro->time_last_process (imageProcessing.cpp:6: -1e5 until the vision
+ * stage processes a frame), p_frame->time_sweep_end of the frame the next srl_lio_commit_frame inserts (srl_lio_run_measurement takes the
+ * frame's own), and the `to_rendering` flag stateEstimation passes (:1027).  srl_lio_add_points_to_map_at: srl_lio_add_points_to_map
+ * with the frame's time_sweep_end and to_rendering as arguments.  srl_lio_color_visited copies a list out (which = 0:
+ * voxels_recent_visited_temp, 1: voxels_recent_visited; int32 x 3 per voxel; capacity in voxels, 0 asks for the number alone) and
+ * number_of_new_visited_voxel; srl_lio_color_stored the records of the last insertion.  A host-only handle: SRL_ERR_NO_DEVICE. */
+int srl_lio_set_color_map_options(srl_lio *lio, const srl_color_opts *opts);
+int srl_lio_set_color_times(srl_lio *lio, double time_last_process, double commit_time_sweep_end, int to_rendering);
+int srl_lio_add_points_to_map_at(srl_lio *lio, const double *world_xyz, int n, double voxel_size, int max_num_points_in_voxel,
+                                 double min_distance_points, int min_num_points, double time_sweep_end, int to_rendering);
+int srl_lio_color_visited(srl_lio *lio, int which, int32_t *out_xyz, int capacity, int *n, int *number_of_new_visited_voxel);
+int srl_lio_color_stored(srl_lio *lio, srl_color_stored *out, int capacity, int *n);
 /* Where lioOptimization::buildFrame sub-samples the cut sweep (subSampleFrame, lioOptimization.cpp:838-846): on = 1 (the default) on the
  * device (srl_frame_subsample + srl_frame_take_subsampled; the host runs the two shuffles on index arrays and downloads m points), 0 = on the
  * host over the n-point downloads of srl_frame_undistort and srl_frame_take.  Both give the same frame bit for bit. */

@@ -59,6 +59,22 @@ class CloudPoint(C.Structure):
 CLOUD_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])      # cloud.view(CLOUD_POINT_DTYPE)
 
 
+class ColorOpts(C.Structure):
+    """srl_color_opts: mapOptions (parameters.h:98-106)"""
+    _fields_ = [("size_voxel_map", C.c_double), ("max_num_points_in_voxel", C.c_int32), ("min_distance_points", C.c_double),
+                ("add_point_step", C.c_int32)]
+
+
+class ColorTotals(C.Structure):
+    """srl_color_totals: what one srl_color_map_insert did"""
+    _fields_ = [("stored", C.c_int32), ("created", C.c_int32), ("registered", C.c_int32), ("visited", C.c_int32)]
+
+
+# srl_color_stored: records.view(COLOR_STORED_DTYPE)
+COLOR_STORED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("kx", "<i2"), ("ky", "<i2"), ("kz", "<i2"), ("slot", "<u2"),
+                               ("batch_index", "<i4"), ("point_index", "<i4")])
+
+
 class NormalEq(C.Structure):
     _fields_ = [("HtH", C.c_double * 36), ("Hth", C.c_double * 6), ("loss_sum", C.c_double),
                 ("num_residuals", C.c_int32), ("success", C.c_int32), ("sum_candidates", C.c_int64),
@@ -128,6 +144,14 @@ def load_library():
         "srl_map_download": ([p, p, p, p, C.c_int], C.c_int),
         "srl_map_remove_far": ([p, dp, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64)], C.c_int),
         "srl_map_probe_checksum": ([p, p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_uint64)], C.c_int),
+        "srl_color_opts_default": ([C.POINTER(ColorOpts)], None),
+        "srl_color_map_create": ([p, C.POINTER(ColorOpts)], C.c_int),
+        "srl_color_map_destroy": ([p], C.c_int),
+        "srl_color_map_insert": ([p, p, C.c_int, C.c_double, C.c_double, p, p, C.c_int, p, C.c_int, C.POINTER(ColorTotals)], C.c_int),
+        "srl_color_map_size": ([p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+        "srl_color_map_download": ([p, p, p, p, C.c_int, p, p, C.c_int64], C.c_int),
+        "srl_color_registered_download": ([p, C.c_int64, C.c_int, p], C.c_int),
+        "srl_debug_color_map_rebuilds": ([p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "srl_sweep_upload": ([p, p, C.c_int], C.c_int),
         "srl_sweep_shard": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "srl_sweep_prefetch": ([p, p, C.c_int], C.c_int),
@@ -219,6 +243,11 @@ def load_library():
         "srl_lio_set_collect_points_world": ([p, C.c_int], C.c_int),
         "srl_lio_points_world": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_set_device_subsample": ([p, C.c_int], C.c_int),
+        "srl_lio_set_color_map_options": ([p, C.POINTER(ColorOpts)], C.c_int),
+        "srl_lio_set_color_times": ([p, C.c_double, C.c_double, C.c_int], C.c_int),
+        "srl_lio_add_points_to_map_at": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
+        "srl_lio_color_visited": ([p, C.c_int, p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "srl_lio_color_stored": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_probe_checksum_of_committed_frame": ([p, C.c_int, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)], C.c_int),
         "srl_lio_resident_sweep": ([p, p, C.c_int], C.c_int),
         "srl_lio_prefetch_sweep": ([p, p, C.c_int], C.c_int),
@@ -292,6 +321,14 @@ def _f64(a, shape=None):
 def default_opts(**kw):
     o = IcpOpts()
     load_library().srl_icp_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_color_opts(**kw):
+    o = ColorOpts()
+    load_library().srl_color_opts_default(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -485,6 +522,62 @@ class Context:
         loc = _f64(location).ravel()
         self._chk(self.lib.srl_map_remove_far(self.h, _dptr(loc), float(distance), C.byref(nv), C.byref(npnt)), "srl_map_remove_far")
         return nv.value, npnt.value
+
+    def color_map_create(self, opts=None):
+        """srl_color_map_create: the colour voxel map (addPointToColorMap); opts = ColorOpts, None = the yaml values 0.1 / 50 / 0.01 / 1"""
+        o = default_color_opts() if opts is None else opts
+        self._chk(self.lib.srl_color_map_create(self.h, C.byref(o)), "srl_color_map_create")
+
+    def color_map_destroy(self):
+        self._chk(self.lib.srl_color_map_destroy(self.h), "srl_color_map_destroy")
+
+    def color_map_insert(self, world_xyz=None, time_sweep_end=0.0, time_last_process=0.0, n_frame=None, want_outcome=True, want_stored=True,
+                         want_visited=True):
+        """srl_color_map_insert.  world_xyz None = the world points of the last committed frame (n_frame: their number, for the output
+        capacities; default srl_frame_size).  Returns (outcome uint8[n] or None, stored records (COLOR_STORED_DTYPE) or None,
+        visited (m, 3) int32 or None, ColorTotals)."""
+        if world_xyz is None:
+            w, n = None, (self.frame_size() if n_frame is None else int(n_frame))
+        else:
+            w = _f64(world_xyz, (-1, 3))
+            n = len(w)
+        outcome = np.zeros(n, dtype=np.uint8) if want_outcome else None
+        stored = np.zeros(n, dtype=COLOR_STORED_DTYPE) if want_stored else None
+        visited = np.zeros((n, 3), dtype=np.int32) if want_visited else None
+        tot = ColorTotals()
+        self._chk(self.lib.srl_color_map_insert(self.h, _ptr(w), n, float(time_sweep_end), float(time_last_process), _ptr(outcome), _ptr(stored), n,
+                                                _ptr(visited), n, C.byref(tot)), "srl_color_map_insert")
+        return (outcome, None if stored is None else stored[: tot.stored].copy(), None if visited is None else visited[: tot.visited].copy(), tot)
+
+    def color_map_size(self):
+        """(points, voxels, registered, grid cells)"""
+        a, b, c, d = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.srl_color_map_size(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "srl_color_map_size")
+        return a.value, b.value, c.value, d.value
+
+    def color_map_download(self):
+        """(keys (V, 3) int16, counts, last_visited_time, xyz (P, 3) float32 voxel after voxel in slot order, point_index (P))"""
+        npnt, nv, _, _ = self.color_map_size()
+        keys = np.zeros((nv, 3), dtype=np.int16)
+        counts = np.zeros(nv, dtype=np.int32)
+        times = np.zeros(nv, dtype=np.float64)
+        xyz = np.zeros((npnt, 3), dtype=np.float32)
+        pidx = np.zeros(npnt, dtype=np.int32)
+        self._chk(self.lib.srl_color_map_download(self.h, _ptr(keys), _ptr(counts), _ptr(times), nv, _ptr(xyz), _ptr(pidx), npnt), "srl_color_map_download")
+        return keys, counts, times, xyz, pidx
+
+    def color_registered_download(self, first=0, count=None):
+        """the device's rgb_points_vec[first : first + count] as COLOR_STORED_DTYPE records"""
+        if count is None:
+            count = self.color_map_size()[2] - first
+        out = np.zeros(count, dtype=COLOR_STORED_DTYPE)
+        self._chk(self.lib.srl_color_registered_download(self.h, int(first), int(count), _ptr(out)), "srl_color_registered_download")
+        return out
+
+    def color_map_rebuilds(self):
+        a, b = C.c_int32(), C.c_int32()
+        self._chk(self.lib.srl_debug_color_map_rebuilds(self.h, C.byref(a), C.byref(b)), "srl_debug_color_map_rebuilds")
+        return a.value, b.value
 
     def sweep_upload(self, raw_xyz):
         r = _f64(raw_xyz, (-1, 3))
@@ -965,6 +1058,37 @@ class Lio:
         if m.value:
             self._chk(self.lib.srl_lio_points_world(self.h, _ptr(cloud), m.value, C.byref(m)), "srl_lio_points_world")
         return cloud
+
+    def set_color_map_options(self, opts=None):
+        """opt in to the colour half of addPointsToMap (srl_lio_set_color_map_options); opts = ColorOpts, None = the yaml values"""
+        self._chk(self.lib.srl_lio_set_color_map_options(self.h, None if opts is None else C.byref(opts)), "srl_lio_set_color_map_options")
+
+    def set_color_times(self, time_last_process=-1e5, commit_time_sweep_end=0.0, to_rendering=False):
+        self._chk(self.lib.srl_lio_set_color_times(self.h, float(time_last_process), float(commit_time_sweep_end), 1 if to_rendering else 0),
+                  "srl_lio_set_color_times")
+
+    def add_points_to_map_at(self, world_xyz, time_sweep_end, to_rendering=False, voxel_size=1.0, cap=20, min_dist=0.15, min_num_points=0):
+        w = _f64(world_xyz, (-1, 3))
+        self._chk(self.lib.srl_lio_add_points_to_map_at(self.h, _ptr(w), len(w), voxel_size, cap, min_dist, min_num_points, float(time_sweep_end),
+                                                        1 if to_rendering else 0), "srl_lio_add_points_to_map_at")
+
+    def color_visited(self, which=0):
+        """(list (m, 3) int32, number_of_new_visited_voxel); which 0 = voxels_recent_visited_temp, 1 = voxels_recent_visited"""
+        m, new = C.c_int(), C.c_int()
+        self._chk(self.lib.srl_lio_color_visited(self.h, int(which), None, 0, C.byref(m), C.byref(new)), "srl_lio_color_visited")
+        out = np.zeros((m.value, 3), dtype=np.int32)
+        if m.value:
+            self._chk(self.lib.srl_lio_color_visited(self.h, int(which), _ptr(out), m.value, C.byref(m), C.byref(new)), "srl_lio_color_visited")
+        return out, new.value
+
+    def color_stored(self):
+        """the stored records of the last insertion (COLOR_STORED_DTYPE)"""
+        m = C.c_int()
+        self._chk(self.lib.srl_lio_color_stored(self.h, None, 0, C.byref(m)), "srl_lio_color_stored")
+        out = np.zeros(m.value, dtype=COLOR_STORED_DTYPE)
+        if m.value:
+            self._chk(self.lib.srl_lio_color_stored(self.h, _ptr(out), m.value, C.byref(m)), "srl_lio_color_stored")
+        return out
 
     def set_device_subsample(self, on):
         """buildFrame's sub-sample on the device (True, the default) or on the host (srl_lio_set_device_subsample)"""

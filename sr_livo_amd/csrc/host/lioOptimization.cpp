@@ -479,7 +479,6 @@ void lioOptimization::addPointToMap(voxelHashMap &map, const srl::Vec3 &point, d
 
 void lioOptimization::addPointsToMap(voxelHashMap &map, cloudFrame *p_frame, double voxel_size, int max_num_points_in_voxel,
                                      double min_distance_points, int min_num_points, bool to_rendering) {
-    (void)to_rendering;   // colour map / rendering bookkeeping belongs to the vision stage (out of scope)
     if (!map.ctx) throw std::runtime_error("addPointsToMap: no HIP context (the product has no CPU path)");
     const int n = (int)p_frame->point_frame.size();
     std::vector<double> xyz((size_t)n * 3);
@@ -493,10 +492,43 @@ void lioOptimization::addPointsToMap(voxelHashMap &map, cloudFrame *p_frame, dou
                                              p_frame->p_state->translation[2], nullptr, points_world.data(), &m, nullptr);
         points_world.resize(rc == SRL_OK ? (size_t)m : 0);
         check(map.ctx, rc, "srl_map_insert_report");
-        return;
+    } else {
+        check(map.ctx, srl_map_insert(map.ctx, xyz.data(), n, voxel_size, max_num_points_in_voxel, min_distance_points, min_num_points, nullptr),
+              "srl_map_insert");
     }
-    check(map.ctx, srl_map_insert(map.ctx, xyz.data(), n, voxel_size, max_num_points_in_voxel, min_distance_points, min_num_points, nullptr),
-          "srl_map_insert");
+    // :538-539 -- the colour map takes the same points with mapOptions and min_num_points = 0
+    if (color_map_enabled) colorInsert(xyz.data(), n, p_frame->time_sweep_end, to_rendering);
+}
+
+void lioOptimization::setColorMapOptions(const srl_color_opts &o) {
+    srl_ctx *ctx = voxel_map.ctx;
+    if (!ctx) throw std::runtime_error("setColorMapOptions: no HIP context (the product has no CPU path)");
+    check(ctx, srl_color_map_create(ctx, &o), "srl_color_map_create");
+    color_map_enabled = true;
+}
+
+// lioOptimization.cpp:523-550 around the device insertion (world_xyz == nullptr: the points the last srl_frame_commit left in HBM)
+void lioOptimization::colorInsert(const double *world_xyz, int n, double time_sweep_end, bool rendering) {
+    srl_ctx *ctx = voxel_map.ctx;
+    if (rendering) {
+        voxels_recent_visited_temp.clear();
+        std::vector<voxelId>().swap(voxels_recent_visited_temp);
+    }
+    const int number_of_voxels_before_add = (int)voxels_recent_visited_temp.size();
+    color_stored.resize((size_t)(n > 0 ? n : 0));
+    std::vector<int32_t> visited((size_t)(n > 0 ? n : 0) * 3);
+    color_totals = {0, 0, 0, 0};
+    const int rc = n > 0 ? srl_color_map_insert(ctx, world_xyz, n, time_sweep_end, time_last_process, nullptr, color_stored.data(), n, visited.data(), n, &color_totals)
+                         : SRL_OK;
+    color_stored.resize(rc == SRL_OK ? (size_t)color_totals.stored : 0);
+    check(ctx, rc, "srl_color_map_insert");
+    for (int k = 0; k < color_totals.visited; k++) voxels_recent_visited_temp.push_back({visited[(size_t)k * 3], visited[(size_t)k * 3 + 1], visited[(size_t)k * 3 + 2]});
+    if (rendering) {
+        voxels_recent_visited.clear();
+        std::vector<voxelId>().swap(voxels_recent_visited);
+        voxels_recent_visited = voxels_recent_visited_temp;
+        number_of_new_visited_voxel = (int)voxels_recent_visited.size() - number_of_voxels_before_add;
+    }
 }
 
 void lioOptimization::removePointsFarFromLocation(voxelHashMap &map, const srl::Vec3 &location, double distance) {
@@ -741,6 +773,7 @@ optimizeSummary lioOptimization::stateEstimation(cloudFrame *p_frame) {
     // addPointsToMap(voxel_map, p_frame, ...) on the frame resident in HBM
     const int n = (int)p_frame->point_frame.size();
     std::vector<double> world(download_frame_points ? (size_t)n * 3 : 0);
+    commit_time_sweep_end = p_frame->time_sweep_end;
     last_points_added = commitFrame(&commit_pose, kSizeVoxelMap, max_num_points_in_voxel, min_distance_points, 0,
                                     download_frame_points && n > 0 ? world.data() : nullptr);
     // addPointToPcl reads p_frame->p_state->translation.z() (lioOptimization.cpp:1352); the first frame is committed with the identity
@@ -888,10 +921,17 @@ int lioOptimization::commitFrame(const state *p_state, double voxel_size, int ma
                                                min_distance_points, min_num_points, world_out, nullptr, points_world.data(), &m, &added);
         points_world.resize(rc == SRL_OK ? (size_t)m : 0);
         check(ctx, rc, "srl_frame_commit_report");
-        return want_added ? added : -1;
+        if (!want_added) added = -1;
+    } else {
+        check(ctx, srl_frame_commit(ctx, qv, p_state->translation.a, R_imu_lidar.a, t_imu_lidar.a, voxel_size, max_num_points_in_voxel,
+                                    min_distance_points, min_num_points, world_out, want_added ? &added : nullptr), "srl_frame_commit");
     }
-    check(ctx, srl_frame_commit(ctx, qv, p_state->translation.a, R_imu_lidar.a, t_imu_lidar.a, voxel_size, max_num_points_in_voxel,
-                                min_distance_points, min_num_points, world_out, want_added ? &added : nullptr), "srl_frame_commit");
+    if (color_map_enabled) {
+        // the colour insertion reads the world points the commit left in HBM: nothing crosses PCIe on the way in
+        int n = 0;
+        check(ctx, srl_frame_size(ctx, &n), "srl_frame_size");
+        colorInsert(nullptr, n, commit_time_sweep_end, to_rendering);
+    }
     return added;
 }
 

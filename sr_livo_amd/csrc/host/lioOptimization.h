@@ -196,6 +196,23 @@ public:
     // it stays until the next insertion so that the caller can publish it.
     std::vector<srl_cloud_point> points_world;
     void setCollectPointsWorld(bool on) { collect_points_world = on; }
+    // The colour half of addPointsToMap (lioOptimization.cpp:538-539: addPointToColorMap for every add_point_step-th point), opt-in: once
+    // setColorMapOptions has created the device colour map (srl_color_map_create with mapOptions, parameters.h:98-106), addPointsToMap and
+    // commitFrame run srl_color_map_insert behind the LiDAR insertion -- commitFrame on the world points it left in HBM -- and keep the
+    // lists of lioOptimization.cpp:523-550 as the reference does, `to_rendering` included.  color_stored: the records of the last
+    // insertion (which point went to which voxel and slot, and under which index it was registered), for the caller's own rgbPoint
+    // objects.  Without the options: exactly the LiDAR insertion.  The calls are synchronous.
+    struct voxelId { int kx, ky, kz; };                                  // cloudMap.h:88
+    void setColorMapOptions(const srl_color_opts &o);
+    bool colorMapEnabled() const { return color_map_enabled; }
+    double time_last_process = -1e5;                                     // img_pro->time_last_process (imageProcessing.cpp:6; the vision stage's, set by the caller)
+    bool to_rendering = false;                                           // include/lioOptimization.h: what stateEstimation hands to addPointsToMap (:1027)
+    double commit_time_sweep_end = 0.0;                                  // p_frame->time_sweep_end of the frame commitFrame inserts (stateEstimation sets it)
+    std::vector<voxelId> voxels_recent_visited_temp;                     // include/lioOptimization.h:291
+    std::vector<voxelId> voxels_recent_visited;                          // img_pro->map_tracker->voxels_recent_visited (rgbMapTracker.h:38)
+    int number_of_new_visited_voxel = 0;                                 // rgbMapTracker.h:52
+    std::vector<srl_color_stored> color_stored;
+    srl_color_totals color_totals = {0, 0, 0, 0};
     bool collectPointsWorld() const { return collect_points_world; }
 
     // ---- ours ----
@@ -249,6 +266,8 @@ private:
     int pending_prefetch_rc = 0;
     bool sweep_pinned = false;
     bool collect_points_world = false;
+    bool color_map_enabled = false;
+    void colorInsert(const double *world_xyz, int n, double time_sweep_end, bool rendering);
 };
 
 }  // namespace srlivo

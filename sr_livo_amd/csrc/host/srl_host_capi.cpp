@@ -241,6 +241,58 @@ int srl_lio_points_world(srl_lio *h, srl_cloud_point *out, int capacity, int *n)
     return SRL_OK;
 }
 
+int srl_lio_set_color_map_options(srl_lio *h, const srl_color_opts *opts) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }
+    srl_color_opts o;
+    if (opts) o = *opts; else srl_color_opts_default(&o);
+    try { h->lio->setColorMapOptions(o); }
+    catch (const std::exception &e) { return status_from_exception(h, e); }
+    return SRL_OK;
+}
+int srl_lio_set_color_times(srl_lio *h, double time_last_process, double commit_time_sweep_end, int to_rendering) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    h->lio->time_last_process = time_last_process;
+    h->lio->commit_time_sweep_end = commit_time_sweep_end;
+    h->lio->to_rendering = to_rendering != 0;
+    return SRL_OK;
+}
+int srl_lio_add_points_to_map_at(srl_lio *h, const double *world_xyz, int n, double voxel_size, int max_num_points_in_voxel, double min_distance_points,
+                                 int min_num_points, double time_sweep_end, int to_rendering) {
+    if (!h || n < 0 || (n > 0 && !world_xyz)) return SRL_ERR_BAD_ARG;
+    std::vector<point3D> pts((size_t)n);
+    for (int k = 0; k < n; k++) pts[k].point = srl::vec3(world_xyz[(size_t)k * 3], world_xyz[(size_t)k * 3 + 1], world_xyz[(size_t)k * 3 + 2]);
+    state st;
+    cloudFrame frame(pts, &st);
+    frame.time_sweep_end = time_sweep_end;
+    try {
+        h->lio->addPointsToMap(h->lio->voxel_map, &frame, voxel_size, max_num_points_in_voxel, min_distance_points, min_num_points, to_rendering != 0);
+    } catch (const std::exception &e) { return status_from_exception(h, e); }
+    return SRL_OK;
+}
+int srl_lio_color_visited(srl_lio *h, int which, int32_t *out_xyz, int capacity, int *n, int *number_of_new_visited_voxel) {
+    if (n) *n = 0;
+    if (number_of_new_visited_voxel) *number_of_new_visited_voxel = 0;
+    if (!h || !n || which < 0 || which > 1 || capacity < 0 || (capacity > 0 && !out_xyz)) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }
+    const auto &list = which == 0 ? h->lio->voxels_recent_visited_temp : h->lio->voxels_recent_visited;
+    *n = (int)list.size();
+    if (number_of_new_visited_voxel) *number_of_new_visited_voxel = h->lio->number_of_new_visited_voxel;
+    if ((int)list.size() > capacity) return capacity == 0 ? SRL_OK : SRL_ERR_BAD_ARG;
+    for (size_t k = 0; k < list.size(); k++) { out_xyz[k * 3] = list[k].kx; out_xyz[k * 3 + 1] = list[k].ky; out_xyz[k * 3 + 2] = list[k].kz; }
+    return SRL_OK;
+}
+int srl_lio_color_stored(srl_lio *h, srl_color_stored *out, int capacity, int *n) {
+    if (n) *n = 0;
+    if (!h || !n || capacity < 0 || (capacity > 0 && !out)) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }
+    const std::vector<srl_color_stored> &cs = h->lio->color_stored;
+    *n = (int)cs.size();
+    if ((int)cs.size() > capacity) return capacity == 0 ? SRL_OK : SRL_ERR_BAD_ARG;
+    if (!cs.empty()) std::memcpy(out, cs.data(), cs.size() * sizeof(srl_color_stored));
+    return SRL_OK;
+}
+
 int srl_lio_set_device_subsample(srl_lio *h, int on) {
     if (!h) return SRL_ERR_BAD_ARG;
     h->lio->device_subsample = on != 0;

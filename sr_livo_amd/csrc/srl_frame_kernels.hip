@@ -1068,7 +1068,7 @@ int frame_commit_impl(srl_ctx *ctx, const double q[4], const double t[3], const 
     const int rci = srl_map_insert_impl(ctx, ctx->d_frame_world, true, n, voxel_size, min_distance_points, min_num_points, num_added,
                                         num_added == nullptr && !report, fused ? &xf : nullptr, fused ? +world_ready : nullptr, &dl, report);
     if (world_out && rci == SRL_OK) HIPCHK(ctx, hipEventSynchronize(ctx->ev_world));
-    if (rci == SRL_OK) ctx->frame_world_n = n;            // d_frame_world = the frame as inserted (srl_map_probe_checksum)
+    if (rci == SRL_OK) { ctx->frame_world_n = n; ctx->frame_world_seen = true; }     // d_frame_world = the frame as inserted (srl_map_probe_checksum, srl_color_map_insert)
     return rci;
 }
 }  // namespace

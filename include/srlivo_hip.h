@@ -214,6 +214,70 @@ int srl_color_map_download(srl_ctx *ctx, int16_t *keys_xyz, int32_t *counts, dou
  * i.e. its rank among all stored points; point_index = its index in the list). */
 int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_color_stored *out);
 
+/* ------------------------------------------------------------------ colour voxel map: rendering an image into it
+ * replaces: rgbMapTracker::renderPointsInRecentVoxel / threadRenderPointsInVoxel (rgbMapTracker.cpp:176-237): for every point of every
+ * listed voxel cloudFrame::project3dPointInThisImage (lioOptimization.cpp:142-199) with if2dPointsAvailable (:48-60), the sub-pixel colour
+ * cloudFrame::getRgb(u, v, 0) = getSubPixel<cv::Vec3b> (:71-103) and rgbPoint::updateRgb(colour, distance, (15, 15, 15), obs_time)
+ * (cloudMap.cpp:59-100).  The per-point colour state (rgb int16 x 3, cov_rgb FP32 x 3, observe_distance, last_observe_time, N_rgb int16:
+ * cloudMap.h:51-66) lives in HBM beside the point pool, 40 bytes per stored point, allocated at the first srl_color_image_upload; zero
+ * bytes are rgbPoint::reset().  The rest of the vision stage (optical flow, PnP, vioEsikf, vioPhotometric, selectPointsForProjection,
+ * undistortion and equalisation of the image, the publishers) stays with the caller.
+ *
+ * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
+ *   p = (double) stored FP32 position; pc = R_cw p + t_cw with q_cw = q_world_camera.inverse(), R_cw = q_cw.toRotationMatrix(),
+ *   t_cw = -R_cw t_world_camera (refreshPoseForProjection, :201-205: computed on the host); rejected if pc.z < 0.001;
+ *   u = (pc.x fx / pc.z + cx) * 1.0, v = (pc.y fy / pc.z + cy) * 1.0; accepted iff u >= m cols + 1, ceil(u) < (1 - m) cols, v >= m rows + 1,
+ *   ceil(v) < (1 - m) rows with m = fov_margin; d = |p - t_world_camera|;
+ *   colour: r0 = floor(v), c0 = floor(u), fr = v - r0, fc = u - c0; per channel the SATURATING 8-bit sum, left to right, of
+ *   sat8((1-fr)(1-fc) I[r0][c0]), sat8(fr (1-fc) I[r0+1][c0]), sat8((1-fr) fc I[r0][c0+1]), sat8(fr fc I[r0+1][c0+1]) where
+ *   sat8(x) = round to nearest, ties to even, clamped to 0 ... 255 -- OpenCV's `double * Vec3b` and `Vec3b + Vec3b`:
+ *   a sum of four individually rounded bytes, not a rounded bilinear value.  The one neighbour the field-of-view test lets lie past the row or the image (integral u = cols - 1 or v = rows - 1) has
+ *   weight exactly 0 and contributes 0 whatever it holds: it is read from the last column / row instead;
+ *   updateRgb, literally: nothing if observe_distance != 0 and d > 1.2 observe_distance; the first observation (N_rgb == 0) stores the
+ *   colour, cov = 15, d, obs_time, N_rgb = 1; otherwise per channel cov = (float)(cov + 0.1 (obs_time - last_observe_time)), old = cov,
+ *   cov = (float)sqrt(1 / (1 / (cov * cov [FP32]) + 1 / 225)), rgb = (short)(cov * cov [FP32] * (rgb / old^2 + colour / 225)) truncated
+ *   toward zero, then observe_distance = min(observe_distance, d), last_observe_time = obs_time, N_rgb++.
+ * N_rgb is an int16 as in the reference: a point observed more than 32 767 times is outside the contract.  Results are bitwise those of
+ * the reference's loop and reproducible.  The LiDAR map, the neighbourhood bounds and the taps are not touched. */
+typedef struct srl_color_camera {
+    double q_world_camera[4];            /* w, x, y, z (state.h) */
+    double t_world_camera[3];
+    double fx, fy, cx, cy;
+    double fov_margin;                   /* state.cpp:25: 0.005; must be > 0 (at 0 an integral u = cols - 1 reads past the row) */
+} srl_color_camera;
+/* of one render, counted per occurrence of a voxel in the list: points of listed voxels; of those rejected behind the camera, rejected
+ * by the field of view, refused by updateRgb's distance gate, first observations, updates (the reference's render_point_count); and the
+ * list entries whose voxel the map does not hold */
+typedef struct srl_color_render_totals { int64_t listed, behind, outside, gated, first, updated, unknown; } srl_color_render_totals;
+#define SRL_COLOR_IMAGE_MAX_PIXELS 67108864
+/* rgb_image of the frame (cloudFrame::rgb_image: 8-bit, 3 channels, BGR as OpenCV holds it; getRgb returns channels 0, 1, 2 as they lie),
+ * already undistorted and equalised by the caller (imageProcessing.cpp:113-125).  Copied through page-locked staging into a device buffer
+ * that is reused while the size stays the same; the call returns when the staging copy is made, the DMA is ordered in front of the next
+ * render.  The first upload allocates the colour state.  NULL, rows or cols < 2, rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS or
+ * row_stride_bytes < 3 cols: SRL_ERR_BAD_ARG; no colour map: SRL_ERR_NO_MAP; more than one rank: SRL_ERR_UNSUPPORTED -- all before a
+ * device is touched.  Cancels an armed launch. */
+int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows, int cols, int64_t row_stride_bytes);
+/* voxels_xyz: n_voxels x 3 int32, the caller's voxels_recent_visited (the visited output of srl_color_map_insert).  The list may name a
+ * voxel several times (lioOptimization.cpp:523-550: the temp list accumulates while to_rendering is false); the reference renders such
+ * a voxel once per occurrence with the same observation, and so does this call: updateRgb runs `multiplicity` times in a row per point
+ * (at most 65 535 occurrences of one voxel: SRL_ERR_UNSUPPORTED beyond, nothing changed).  A key the map does not hold is counted in
+ * totals->unknown and otherwise ignored (the reference's map[voxel] would create an empty block; lists come from the insertion, so this
+ * does not arise).  The pass visits every stored point of the map once, whatever the list's length.  Synchronous: one wait for the totals.
+ * Return codes, all before a device is touched: NULL ctx, cam or (n_voxels > 0) voxels_xyz, n_voxels < 0, a non-finite camera or obs_time,
+ * fov_margin <= 0: SRL_ERR_BAD_ARG; no colour map: SRL_ERR_NO_MAP; no image uploaded: SRL_ERR_NO_SWEEP; more than one rank:
+ * SRL_ERR_UNSUPPORTED; n_voxels == 0: SRL_OK with zero totals.  Cancels an armed launch. */
+int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, const int32_t *voxels_xyz, int n_voxels, double obs_time,
+                         srl_color_render_totals *totals /* or NULL */);
+/* The colour state in the order srl_color_map_download writes xyz in (voxel after voxel, slot order): rgb int16 x 3 (getRgb(): channels as
+ * the image held them), N_rgb, cov_rgb FP32 x 3, observe_distance, last_observe_time.  Every output optional; max_points is the capacity
+ * (SRL_ERR_BAD_ARG when the map holds more).  A map never rendered gives zeros. */
+int srl_color_map_download_rgb(srl_ctx *ctx, int16_t *rgb, int16_t *n_rgb, float *cov_rgb, double *observe_distance, double *last_observe_time,
+                               int64_t max_points);
+/* ... and of rgb_points_vec[first .. first + count): what the publishers read (getRgb(), N_rgb against pub_point_minimum_views:
+ * lioOptimization.cpp:1228-1230, 1290-1292, 1414-1416).  One gather kernel and one DMA of exactly count records. */
+int srl_color_registered_rgb(srl_ctx *ctx, int64_t first, int count, int16_t *rgb, int16_t *n_rgb, float *cov_rgb, double *observe_distance,
+                             double *last_observe_time);
+
 /* ------------------------------------------------------------------ sweep
  * replaces: the `keypoints` vector handed to updateIEKF (optimize.cpp:133; point3D::raw_point,
  * cloudMap.h:40).  AoS n x 3 FP64 in the lidar frame, in keypoint order.  Uploaded once per sweep.

@@ -77,6 +77,11 @@ int srl_lio_add_points_to_map_at(srl_lio *lio, const double *world_xyz, int n, d
                                  double min_distance_points, int min_num_points, double time_sweep_end, int to_rendering);
 int srl_lio_color_visited(srl_lio *lio, int which, int32_t *out_xyz, int capacity, int *n, int *number_of_new_visited_voxel);
 int srl_lio_color_stored(srl_lio *lio, srl_color_stored *out, int capacity, int *n);
+/* rgbMapTracker::renderPointsInRecentVoxel (rgbMapTracker.cpp:219-237): srl_color_map_render of the image last uploaded with
+ * srl_color_image_upload(srl_lio_ctx(lio), ...) into the points of voxels_recent_visited (the list an insertion with to_rendering set
+ * left; repeats included).  totals (optional) is zeroed first.  NULL lio or camera: SRL_ERR_BAD_ARG; a host-only handle:
+ * SRL_ERR_NO_DEVICE; otherwise the codes of srl_color_map_render. */
+int srl_lio_render_points_in_recent_voxel(srl_lio *lio, const srl_color_camera *camera, double obs_time, srl_color_render_totals *totals);
 /* Where lioOptimization::buildFrame sub-samples the cut sweep (subSampleFrame, lioOptimization.cpp:838-846): on = 1 (the default) on the
  * device (srl_frame_subsample + srl_frame_take_subsampled; the host runs the two shuffles on index arrays and downloads m points), 0 = on the
  * host over the n-point downloads of srl_frame_undistort and srl_frame_take.  Both give the same frame bit for bit. */

@@ -70,6 +70,21 @@ class ColorTotals(C.Structure):
     _fields_ = [("stored", C.c_int32), ("created", C.c_int32), ("registered", C.c_int32), ("visited", C.c_int32)]
 
 
+class ColorCamera(C.Structure):
+    """srl_color_camera: the pose and intrinsics project3dPointInThisImage reads from the frame's state (q as w, x, y, z)"""
+    _fields_ = [("q_world_camera", C.c_double * 4), ("t_world_camera", C.c_double * 3), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("fov_margin", C.c_double)]
+
+
+class ColorRenderTotals(C.Structure):
+    """srl_color_render_totals: what one srl_color_map_render did, per occurrence of a voxel in the list"""
+    _fields_ = [("listed", C.c_int64), ("behind", C.c_int64), ("outside", C.c_int64), ("gated", C.c_int64), ("first", C.c_int64),
+                ("updated", C.c_int64), ("unknown", C.c_int64)]
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, f)) for f, _ in self._fields_)
+
+
 # srl_color_stored: records.view(COLOR_STORED_DTYPE)
 COLOR_STORED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("kx", "<i2"), ("ky", "<i2"), ("kz", "<i2"), ("slot", "<u2"),
                                ("batch_index", "<i4"), ("point_index", "<i4")])
@@ -152,6 +167,10 @@ def load_library():
         "srl_color_map_download": ([p, p, p, p, C.c_int, p, p, C.c_int64], C.c_int),
         "srl_color_registered_download": ([p, C.c_int64, C.c_int, p], C.c_int),
         "srl_debug_color_map_rebuilds": ([p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+        "srl_color_image_upload": ([p, p, C.c_int, C.c_int, C.c_int64], C.c_int),
+        "srl_color_map_render": ([p, C.POINTER(ColorCamera), p, C.c_int, C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
+        "srl_color_map_download_rgb": ([p, p, p, p, p, p, C.c_int64], C.c_int),
+        "srl_color_registered_rgb": ([p, C.c_int64, C.c_int, p, p, p, p, p], C.c_int),
         "srl_sweep_upload": ([p, p, C.c_int], C.c_int),
         "srl_sweep_shard": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "srl_sweep_prefetch": ([p, p, C.c_int], C.c_int),
@@ -248,6 +267,7 @@ def load_library():
         "srl_lio_add_points_to_map_at": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
         "srl_lio_color_visited": ([p, C.c_int, p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "srl_lio_color_stored": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_lio_render_points_in_recent_voxel": ([p, C.POINTER(ColorCamera), C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
         "srl_lio_probe_checksum_of_committed_frame": ([p, C.c_int, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)], C.c_int),
         "srl_lio_resident_sweep": ([p, p, C.c_int], C.c_int),
         "srl_lio_prefetch_sweep": ([p, p, C.c_int], C.c_int),
@@ -572,6 +592,41 @@ class Context:
             count = self.color_map_size()[2] - first
         out = np.zeros(count, dtype=COLOR_STORED_DTYPE)
         self._chk(self.lib.srl_color_registered_download(self.h, int(first), int(count), _ptr(out)), "srl_color_registered_download")
+        return out
+
+    def color_image_upload(self, bgr):
+        """srl_color_image_upload: bgr (rows, cols, 3) uint8, the frame's rgb_image as OpenCV holds it (rows may be strided)"""
+        img = np.asarray(bgr)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.strides[2] != 1 or img.strides[1] != 3:
+            img = np.ascontiguousarray(bgr, dtype=np.uint8)
+        self._keep_image = img
+        self._chk(self.lib.srl_color_image_upload(self.h, _ptr(img), img.shape[0], img.shape[1], img.strides[0]), "srl_color_image_upload")
+
+    def color_map_render(self, camera, voxels_xyz, obs_time):
+        """srl_color_map_render: camera = ColorCamera, voxels_xyz (n, 3) int32 (repeats allowed).  Returns ColorRenderTotals."""
+        v = np.ascontiguousarray(voxels_xyz, dtype=np.int32).reshape(-1, 3)
+        tot = ColorRenderTotals()
+        self._chk(self.lib.srl_color_map_render(self.h, C.byref(camera), _ptr(v) if len(v) else None, len(v), float(obs_time), C.byref(tot)),
+                  "srl_color_map_render")
+        return tot
+
+    @staticmethod
+    def _color_state_arrays(n):
+        return (np.zeros((n, 3), dtype=np.int16), np.zeros(n, dtype=np.int16), np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.float64),
+                np.zeros(n, dtype=np.float64))
+
+    def color_map_download_rgb(self):
+        """(rgb (P, 3) int16, N_rgb, cov_rgb (P, 3) float32, observe_distance, last_observe_time) in the order of color_map_download's xyz"""
+        out = self._color_state_arrays(self.color_map_size()[0])
+        self._chk(self.lib.srl_color_map_download_rgb(self.h, *[_ptr(a) for a in out], len(out[1])), "srl_color_map_download_rgb")
+        return out
+
+    def color_registered_rgb(self, first=0, count=None):
+        """the same fields for the device's rgb_points_vec[first : first + count]"""
+        if count is None:
+            count = self.color_map_size()[2] - first
+        out = self._color_state_arrays(int(count))
+        self._chk(self.lib.srl_color_registered_rgb(self.h, int(first), int(count), *[_ptr(a) for a in out]), "srl_color_registered_rgb")
         return out
 
     def color_map_rebuilds(self):
@@ -1089,6 +1144,14 @@ class Lio:
         if m.value:
             self._chk(self.lib.srl_lio_color_stored(self.h, _ptr(out), m.value, C.byref(m)), "srl_lio_color_stored")
         return out
+
+    def render_points_in_recent_voxel(self, camera, obs_time):
+        """rgbMapTracker::renderPointsInRecentVoxel on voxels_recent_visited (srl_lio_render_points_in_recent_voxel); camera = ColorCamera.
+        Returns ColorRenderTotals."""
+        tot = ColorRenderTotals()
+        self._chk(self.lib.srl_lio_render_points_in_recent_voxel(self.h, C.byref(camera), float(obs_time), C.byref(tot)),
+                  "srl_lio_render_points_in_recent_voxel")
+        return tot
 
     def set_device_subsample(self, on):
         """buildFrame's sub-sample on the device (True, the default) or on the host (srl_lio_set_device_subsample)"""

@@ -531,6 +531,16 @@ void lioOptimization::colorInsert(const double *world_xyz, int n, double time_sw
     }
 }
 
+void lioOptimization::renderPointsInRecentVoxel(const srl_color_camera &camera, double obs_time) {
+    srl_ctx *ctx = voxel_map.ctx;
+    if (!ctx) throw std::runtime_error("renderPointsInRecentVoxel: no HIP context (the product has no CPU path)");
+    std::vector<int32_t> list(voxels_recent_visited.size() * 3);
+    for (size_t k = 0; k < voxels_recent_visited.size(); k++) {
+        list[k * 3] = voxels_recent_visited[k].kx; list[k * 3 + 1] = voxels_recent_visited[k].ky; list[k * 3 + 2] = voxels_recent_visited[k].kz;
+    }
+    check(ctx, srl_color_map_render(ctx, &camera, list.data(), (int)voxels_recent_visited.size(), obs_time, &render_totals), "srl_color_map_render");
+}
+
 void lioOptimization::removePointsFarFromLocation(voxelHashMap &map, const srl::Vec3 &location, double distance) {
     if (!map.ctx) throw std::runtime_error("removePointsFarFromLocation: no HIP context (the product has no CPU path)");
     check(map.ctx, srl_map_remove_far(map.ctx, location.a, distance, nullptr, nullptr), "srl_map_remove_far");

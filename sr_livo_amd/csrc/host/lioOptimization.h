@@ -213,6 +213,11 @@ public:
     int number_of_new_visited_voxel = 0;                                 // rgbMapTracker.h:52
     std::vector<srl_color_stored> color_stored;
     srl_color_totals color_totals = {0, 0, 0, 0};
+    // rgbMapTracker::renderPointsInRecentVoxel (rgbMapTracker.cpp:219-237) on the device colour map (srl_color_map_render): the image the
+    // caller uploaded with srl_color_image_upload is rendered into the points of voxels_recent_visited, the list addPointsToMap filled
+    // under `to_rendering`.  Neither list is changed.  render_totals: what the pass did (updated = the reference's render_point_count).
+    void renderPointsInRecentVoxel(const srl_color_camera &camera, double obs_time);
+    srl_color_render_totals render_totals = {0, 0, 0, 0, 0, 0, 0};
     bool collectPointsWorld() const { return collect_points_world; }
 
     // ---- ours ----

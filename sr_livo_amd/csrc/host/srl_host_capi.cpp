@@ -293,6 +293,16 @@ int srl_lio_color_stored(srl_lio *h, srl_color_stored *out, int capacity, int *n
     return SRL_OK;
 }
 
+int srl_lio_render_points_in_recent_voxel(srl_lio *h, const srl_color_camera *camera, double obs_time, srl_color_render_totals *totals) {
+    if (totals) std::memset(totals, 0, sizeof *totals);
+    if (!h || !camera) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }
+    try { h->lio->renderPointsInRecentVoxel(*camera, obs_time); }
+    catch (const std::exception &e) { return status_from_exception(h, e); }
+    if (totals) *totals = h->lio->render_totals;
+    return SRL_OK;
+}
+
 int srl_lio_set_device_subsample(srl_lio *h, int on) {
     if (!h) return SRL_ERR_BAD_ARG;
     h->lio->device_subsample = on != 0;

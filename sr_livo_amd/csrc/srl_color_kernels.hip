@@ -27,6 +27,7 @@
 // point-pool record 24 B {xyz FP32, voxel, slot, registered index or -1}, registered list 4 B (pool position), and two open-addressing
 // tables of 16-B slots kept at a load <= 0.5: voxel key -> voxel, grid key -> {batch tag, owner}.  Both tables grow by rebuild.
 #include "srl_ctx.h"
+#include "srl_color_map.h"
 #include "srl_frame_scratch.h"
 #include "srl_hash.h"
 
@@ -35,26 +36,8 @@
 #include <cstring>
 #include <vector>
 
-struct SrlColorVoxel { unsigned long long key; double last_visited_time; unsigned count; unsigned pad; };
-struct SrlColorPoint { float x, y, z; int voxel; int slot; int reg; };
-struct SrlColorSlot { unsigned long long key; unsigned voxel; unsigned pad; };
-struct SrlGridCell { unsigned long long key; unsigned born; unsigned owner; };     // born: number of the batch that created the cell
 static_assert(sizeof(SrlColorVoxel) == 24 && sizeof(SrlColorPoint) == 24 && sizeof(SrlColorSlot) == 16 && sizeof(SrlGridCell) == 16, "DESIGN.md section 3");
 static_assert(sizeof(srl_color_stored) == 28, "srl_color_stored is 28 bytes on both sides of the C-ABI");
-
-struct SrlColorMap {
-    srl_color_opts opts;
-    SrlColorVoxel *d_vox = nullptr;    unsigned vox_cap = 0;      // voxel records in creation order
-    SrlColorSlot *d_vtab = nullptr;    unsigned vtab_cap = 0;     // voxel key -> voxel (power of two, >= 2 vox_cap)
-    SrlColorPoint *d_pool = nullptr;   size_t pool_cap = 0;       // stored points, append-only, in insertion order
-    int *d_reg = nullptr;              size_t reg_cap = 0;        // registered list: pool position per point_index
-    SrlGridCell *d_grid = nullptr;     unsigned grid_cap = 0;     // grid set (power of two, >= 2 reg_cap)
-    int num_voxels = 0;
-    long long num_points = 0, num_registered = 0;
-    unsigned batch_seq = 0;
-    int vtab_rebuilds = 0, grid_rebuilds = 0;
-    SrlEpochTable scratch;
-};
 
 namespace {
 
@@ -343,6 +326,7 @@ int color_reserve(srl_ctx *ctx, SrlColorMap *cm, int m) {
         const int rc = color_grow_array(ctx, cm->d_pool, (size_t)cm->num_points, cap);
         if (rc) return rc;
         cm->pool_cap = cap;
+        { const int rs = srl_color_state_reserve(ctx, cm); if (rs) return rs; }      // the colour state lies parallel to the pool
     }
     if (need_reg > cm->reg_cap) {
         const size_t cap = std::max<size_t>(need_reg + need_reg / 2, 4096);
@@ -402,6 +386,7 @@ extern "C" int srl_color_map_destroy(srl_ctx *ctx) {
     if (cm->d_pool) hipFree(cm->d_pool);
     if (cm->d_reg) hipFree(cm->d_reg);
     if (cm->d_grid) hipFree(cm->d_grid);
+    srl_color_render_free(cm);
     srl_epoch_table_free(cm->scratch);
     delete cm;
     ctx->color = nullptr;

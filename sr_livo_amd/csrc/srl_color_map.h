@@ -1,0 +1,46 @@
+// srl_color_map.h -- internal: the colour voxel map's device layout, shared by its construction (srl_color_kernels.hip) and its first
+// consumer, the rendering pass (srl_color_render.hip).  DESIGN.md section 3.
+#pragma once
+#include "srl_ctx.h"
+
+struct SrlColorVoxel { unsigned long long key; double last_visited_time; unsigned count; unsigned pad; };
+struct SrlColorPoint { float x, y, z; int voxel; int slot; int reg; };
+struct SrlColorSlot { unsigned long long key; unsigned voxel; unsigned pad; };
+struct SrlGridCell { unsigned long long key; unsigned born; unsigned owner; };     // born: number of the batch that created the cell
+// what rgbPoint::updateRgb reads and writes (include/cloudMap.h:51-66), one record per pool point in an array PARALLEL to the pool;
+// all-zero bytes = rgbPoint::reset() (cloudMap.cpp:11-19)
+struct SrlColorState { double observe_distance; double last_observe_time; float cov_rgb[3]; short rgb[3]; short n_rgb; };
+static_assert(sizeof(SrlColorState) == 40, "DESIGN.md section 3: 40 bytes of colour state per stored point (36 + padding)");
+
+struct SrlColorMap {
+    srl_color_opts opts;
+    SrlColorVoxel *d_vox = nullptr;    unsigned vox_cap = 0;      // voxel records in creation order
+    SrlColorSlot *d_vtab = nullptr;    unsigned vtab_cap = 0;     // voxel key -> voxel (power of two, >= 2 vox_cap)
+    SrlColorPoint *d_pool = nullptr;   size_t pool_cap = 0;       // stored points, append-only, in insertion order
+    int *d_reg = nullptr;              size_t reg_cap = 0;        // registered list: pool position per point_index
+    SrlGridCell *d_grid = nullptr;     unsigned grid_cap = 0;     // grid set (power of two, >= 2 reg_cap)
+    int num_voxels = 0;
+    long long num_points = 0, num_registered = 0;
+    unsigned batch_seq = 0;
+    int vtab_rebuilds = 0, grid_rebuilds = 0;
+    SrlEpochTable scratch;
+
+    // rendering (srl_color_render.hip); nothing of it exists before the first srl_color_image_upload
+    bool render_on = false;
+    SrlColorState *d_state = nullptr;  size_t state_cap = 0;      // parallel to d_pool; entries >= num_points are zero
+    unsigned *d_mark = nullptr;        unsigned mark_cap = 0;     // per voxel: (render epoch << 16) | occurrences in the list of that render
+    unsigned render_epoch = 0;                                    // 1 ... 65535 (0: the value of a word nobody has marked)
+    unsigned char *d_img = nullptr;    size_t img_cap = 0;        // rows x cols x 3 bytes, rows packed
+    unsigned char *h_img = nullptr;    size_t h_img_cap = 0;      // page-locked staging of the upload
+    int img_rows = 0, img_cols = 0;                               // 0: no image uploaded
+    hipEvent_t img_ev = nullptr;       bool img_pending = false;  // the DMA out of h_img
+    unsigned *d_rpart = nullptr;       size_t rpart_rows = 0;     // per-workgroup counter rows of k_render_points (8 words each)
+    unsigned long long *d_rtot = nullptr;                         // [0..5] totals of the last render, [6] unknown keys and [7] overflowing marks
+                                                                  // (both since allocation: never reset), [8] the workgroup ticket
+    unsigned long long unknown_seen = 0, overflow_seen = 0;       // host copies of [6] and [7] as of the previous render
+};
+
+// the state array follows the pool (x1.5 by copy, zero-filled tail) once rendering is on; called behind every pool growth
+int srl_color_state_reserve(srl_ctx *ctx, SrlColorMap *cm);
+// frees what rendering allocated (srl_color_map_destroy)
+void srl_color_render_free(SrlColorMap *cm);

@@ -1,0 +1,410 @@
+// srl_color_render.hip -- the colour voxel map's first consumer on the device for gfx950: rgbMapTracker::renderPointsInRecentVoxel /
+// threadRenderPointsInVoxel (src/rgbMapTracker.cpp:176-237).  For every point of every listed voxel: project3dPointInThisImage
+// (src/lioOptimization.cpp:142-199, if2dPointsAvailable :48-60), the sub-pixel colour getSubPixel<cv::Vec3b> (:71-97) and
+// rgbPoint::updateRgb (src/cloudMap.cpp:59-100).  Every operation is an IEEE operation in the reference's order (-ffp-contract=off,
+// sums of three as (a0 + a1) + a2), so the state is held to the bar of the rest of this tree: bitwise.
+//
+//   k_render_mark    one thread per list entry: the key is looked up in the map's voxel table and 1 is added to the voxel's mark word,
+//                    (render epoch << 16) | occurrences -- a word of another epoch IS zero occurrences, nothing is cleared per call
+//   k_render_points  one thread per POOL point: 24-byte record, 4-byte mark gather; an unmarked point leaves at once, a marked one runs
+//                    the loop body `occurrences` times and rewrites its 40-byte state record.  The six counters are reduced per workgroup
+//                    into a row of its own; ONE atomic per workgroup (a ticket) finds the last one, which adds the rows up
+// The sweep is linear in the map, not in the list: it needs no per-voxel point index (the layout forbids a cap-sized one).
+//
+// OpenCV's Vec3b arithmetic decides the colour's bits: `double * Vec3b` is a Vec3b of saturate_cast<uchar>(w * pixel)
+// = round to nearest, ties to even (cvRound = lrint), clamped to 0 ... 255; `Vec3b + Vec3b` saturates; the four terms are added left to
+// right; the channels become doubles only then.
+#include "srl_ctx.h"
+#include "srl_color_map.h"
+#include "srl_hash.h"
+#include "host/srl_la.h"
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+struct RenderArgs {
+    double R[9], t_cw[3], t_wc[3];     // q_camera_world.toRotationMatrix(), t_camera_world, t_world_camera
+    double fx, fy, cx, cy;
+    double u_lo, u_hi, v_lo, v_hi;     // m cols + 1, (1 - m) cols, m rows + 1, (1 - m) rows
+    double obs_time;
+    int rows, cols;
+};
+enum { RC_LISTED, RC_BEHIND, RC_OUTSIDE, RC_GATED, RC_FIRST, RC_UPDATED, RC_N };
+#define SRL_RTOT_UNKNOWN 6
+#define SRL_RTOT_OVERFLOW 7
+#define SRL_RTOT_TICKET 8
+#define SRL_RTOT_WORDS 9
+
+__global__ void k_render_mark(const int *voxels_xyz, int n, const SrlColorSlot *vtab, unsigned vmask, unsigned *mark, unsigned epoch, unsigned long long *rtot) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int x = voxels_xyz[(size_t)e * 3], y = voxels_xyz[(size_t)e * 3 + 1], z = voxels_xyz[(size_t)e * 3 + 2];
+    int v = -1;
+    if (x >= -32768 && x <= 32767 && y >= -32768 && y <= 32767 && z >= -32768 && z <= 32767) {      // voxelId holds what a voxel's shorts held
+        const unsigned long long key = srl_pack_key((short)x, (short)y, (short)z);
+        unsigned h = srl_hash_key(key) & vmask;
+        for (unsigned probe = 0; probe <= vmask; ++probe) {
+            const unsigned long long k = vtab[h].key;
+            if (k == key) { v = (int)vtab[h].voxel; break; }
+            if (k == SRL_EMPTY_KEY) break;
+            h = (h + 1) & vmask;
+        }
+    }
+    if (v < 0) { atomicAdd(&rtot[SRL_RTOT_UNKNOWN], 1ull); return; }
+    unsigned old = mark[v];
+    for (;;) {
+        const bool cur = (old >> 16) == epoch;
+        if (cur && (old & 0xFFFFu) == 0xFFFFu) { atomicAdd(&rtot[SRL_RTOT_OVERFLOW], 1ull); return; }
+        const unsigned want = cur ? old + 1u : ((epoch << 16) | 1u);
+        const unsigned prev = atomicCAS(&mark[v], old, want);
+        if (prev == old) return;
+        old = prev;
+    }
+}
+
+// saturate_cast<uchar>(w * pixel): cvRound = round to nearest even, then the clamp (w in [0, 1]: the clamp is there for the letter)
+__device__ __forceinline__ int render_sat8(double w, int pixel) {
+    const int r = (int)rint(w * (double)pixel);
+    return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+__device__ __forceinline__ int render_add8(int a, int b) { const int s = a + b; return s > 255 ? 255 : s; }
+// (short) of a double as the reference's x86-64 build does it: cvttsd2si to 32 bits (the "integer indefinite" 0x80000000 outside the
+// range), low 16 bits
+__device__ __forceinline__ short render_short(double x) {
+    const int t = (x > -2147483649.0 && x < 2147483648.0) ? (int)x : (int)0x80000000u;
+    return (short)t;
+}
+
+__global__ void __launch_bounds__(256) k_render_points(long long P, const SrlColorPoint *pool, const unsigned *mark, unsigned epoch, SrlColorState *state,
+                                                       const unsigned char *img, RenderArgs A, unsigned long long overflow_before, unsigned *rpart,
+                                                       unsigned long long *rtot) {
+    __shared__ unsigned s_part[4][RC_N];
+    __shared__ int s_last;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    unsigned c[RC_N] = {0, 0, 0, 0, 0, 0};
+    // a list that names one voxel more than 65 535 times: the mark kernel has flagged it, nothing is rendered
+    const bool refused = rtot[SRL_RTOT_OVERFLOW] != overflow_before;
+    if (p < P && !refused) {
+        const SrlColorPoint pt = pool[p];
+        const unsigned w = mark[pt.voxel];
+        if ((w >> 16) == epoch) {
+            const unsigned mult = w & 0xFFFFu;
+            c[RC_LISTED] = mult;
+            const double px = (double)pt.x, py = (double)pt.y, pz = (double)pt.z;
+            const double xc = ((A.R[0] * px + A.R[1] * py) + A.R[2] * pz) + A.t_cw[0];
+            const double yc = ((A.R[3] * px + A.R[4] * py) + A.R[5] * pz) + A.t_cw[1];
+            const double zc = ((A.R[6] * px + A.R[7] * py) + A.R[8] * pz) + A.t_cw[2];
+            if (zc < 0.001) {
+                c[RC_BEHIND] = mult;
+            } else {
+                const double u = (xc * A.fx / zc + A.cx) * 1.0, v = (yc * A.fy / zc + A.cy) * 1.0;
+                if (!((u >= A.u_lo) && (ceil(u) < A.u_hi) && (v >= A.v_lo) && (ceil(v) < A.v_hi))) {
+                    c[RC_OUTSIDE] = mult;
+                } else {
+                    const double dx = px - A.t_wc[0], dy = py - A.t_wc[1], dz = pz - A.t_wc[2];
+                    const double d = sqrt((dx * dx + dy * dy) + dz * dz);
+                    // the test above leaves 1 <= floor < cols (rows); the clamps only ever move a neighbour of weight 0
+                    const int r0 = (int)floor(v), c0 = (int)floor(u);
+                    const double fr = v - (double)r0, fc = u - (double)c0;
+                    const int r1 = r0 + 1 < A.rows ? r0 + 1 : A.rows - 1, c1 = c0 + 1 < A.cols ? c0 + 1 : A.cols - 1;
+                    const double w00 = (1.0 - fr) * (1.0 - fc), w10 = fr * (1.0 - fc), w01 = (1.0 - fr) * fc, w11 = fr * fc;
+                    const unsigned char *q00 = img + ((size_t)r0 * A.cols + c0) * 3, *q10 = img + ((size_t)r1 * A.cols + c0) * 3;
+                    const unsigned char *q01 = img + ((size_t)r0 * A.cols + c1) * 3, *q11 = img + ((size_t)r1 * A.cols + c1) * 3;
+                    double col[3];
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+                        col[k] = (double)render_add8(render_add8(render_add8(render_sat8(w00, q00[k]), render_sat8(w10, q10[k])), render_sat8(w01, q01[k])),
+                                                     render_sat8(w11, q11[k]));
+                    SrlColorState s = state[p];
+                    bool changed = false;
+                    for (unsigned it = 0; it < mult; ++it) {
+                        if (s.observe_distance != 0 && (d > s.observe_distance * 1.2)) { ++c[RC_GATED]; continue; }
+                        changed = true;
+                        if (s.n_rgb == 0) {
+                            s.last_observe_time = A.obs_time;
+                            s.observe_distance = d;
+#pragma unroll
+                            for (int k = 0; k < 3; k++) { s.rgb[k] = render_short(round(col[k])); s.cov_rgb[k] = (float)15.0; }
+                            s.n_rgb = 1;
+                            ++c[RC_FIRST];
+                            continue;
+                        }
+#pragma unroll
+                        for (int k = 0; k < 3; k++) {
+                            float cv = (float)((double)s.cov_rgb[k] + 0.1 * (A.obs_time - s.last_observe_time));
+                            const double old_sigma = (double)cv;
+                            cv = (float)sqrt(1.0 / (1.0 / (double)(cv * cv) + 1.0 / (15.0 * 15.0)));
+                            s.cov_rgb[k] = cv;
+                            s.rgb[k] = render_short((double)(cv * cv) * ((double)s.rgb[k] / (old_sigma * old_sigma) + col[k] / (15.0 * 15.0)));
+                        }
+                        if (d < s.observe_distance) s.observe_distance = d;
+                        s.last_observe_time = A.obs_time;
+                        s.n_rgb = (short)(s.n_rgb + 1);
+                        ++c[RC_UPDATED];
+                    }
+                    if (changed) state[p] = s;
+                }
+            }
+        }
+    }
+    // the workgroup's counters: waves, then one row per workgroup, then the ticket
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < RC_N; k++) {
+        unsigned v = c[k];
+        for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_xor(v, dlt);
+        if (lane == 0) s_part[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < RC_N) rpart[(size_t)blockIdx.x * 8 + threadIdx.x] = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(&rtot[SRL_RTOT_TICKET], 1ull) == (unsigned long long)gridDim.x - 1ull ? 1 : 0;
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    // the last workgroup: 32 threads per counter over the rows
+    const int k = threadIdx.x >> 5, part = threadIdx.x & 31;
+    unsigned long long sum = 0;
+    if (k < RC_N)
+        for (unsigned b = part; b < gridDim.x; b += 32) sum += __hip_atomic_load(&rpart[(size_t)b * 8 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int dlt = 16; dlt >= 1; dlt >>= 1) sum += __shfl_xor(sum, dlt);
+    if (k < RC_N && part == 0) rtot[k] = sum;
+    if (threadIdx.x == 0) rtot[SRL_RTOT_TICKET] = 0ull;
+}
+
+// srl_color_registered_rgb
+__global__ void k_render_reg_gather(const int *reg_list, long long first, int count, const SrlColorState *state, SrlColorState *out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    out[t] = state[reg_list[first + t]];
+}
+
+void split_state(const SrlColorState &s, size_t at, int16_t *rgb, int16_t *n_rgb, float *cov, double *dist, double *time) {
+    if (rgb) { rgb[at * 3] = s.rgb[0]; rgb[at * 3 + 1] = s.rgb[1]; rgb[at * 3 + 2] = s.rgb[2]; }
+    if (n_rgb) n_rgb[at] = s.n_rgb;
+    if (cov) { cov[at * 3] = s.cov_rgb[0]; cov[at * 3 + 1] = s.cov_rgb[1]; cov[at * 3 + 2] = s.cov_rgb[2]; }
+    if (dist) dist[at] = s.observe_distance;
+    if (time) time[at] = s.last_observe_time;
+}
+
+}  // namespace
+
+int srl_color_state_reserve(srl_ctx *ctx, SrlColorMap *cm) {
+    if (!cm->render_on || cm->state_cap >= cm->pool_cap) return SRL_OK;
+    SrlColorState *ns = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&ns, cm->pool_cap * sizeof(SrlColorState)));
+    const size_t used = cm->d_state ? (size_t)cm->num_points : 0;
+    if (used > 0) HIPCHK(ctx, hipMemcpyAsync(ns, cm->d_state, used * sizeof(SrlColorState), hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ns + used, 0, (cm->pool_cap - used) * sizeof(SrlColorState), ctx->stream));      // rgbPoint::reset()
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (cm->d_state) HIPCHK(ctx, hipFree(cm->d_state));
+    cm->d_state = ns;
+    cm->state_cap = cm->pool_cap;
+    return SRL_OK;
+}
+
+void srl_color_render_free(SrlColorMap *cm) {
+    if (cm->img_pending && cm->img_ev) hipEventSynchronize(cm->img_ev);
+    if (cm->d_state) hipFree(cm->d_state);
+    if (cm->d_mark) hipFree(cm->d_mark);
+    if (cm->d_img) hipFree(cm->d_img);
+    if (cm->h_img) hipHostFree(cm->h_img);
+    if (cm->img_ev) hipEventDestroy(cm->img_ev);
+    if (cm->d_rpart) hipFree(cm->d_rpart);
+    if (cm->d_rtot) hipFree(cm->d_rtot);
+    cm->d_state = nullptr; cm->d_mark = nullptr; cm->d_img = nullptr; cm->h_img = nullptr; cm->img_ev = nullptr; cm->d_rpart = nullptr; cm->d_rtot = nullptr;
+}
+
+extern "C" int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows, int cols, int64_t row_stride_bytes) {
+    if (!ctx || !bgr || rows < 2 || cols < 2 || (int64_t)rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    SrlColorMap *cm = ctx->color;
+    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
+    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t row_bytes = (size_t)cols * 3, bytes = row_bytes * (size_t)rows;
+    if (!cm->img_ev) HIPCHK(ctx, hipEventCreateWithFlags(&cm->img_ev, hipEventDisableTiming));
+    if (cm->img_pending) { HIPCHK(ctx, hipEventSynchronize(cm->img_ev)); cm->img_pending = false; }      // the staging block is free again
+    if (bytes > cm->h_img_cap) {
+        if (cm->h_img) { HIPCHK(ctx, hipHostFree(cm->h_img)); cm->h_img = nullptr; cm->h_img_cap = 0; }
+        HIPCHK(ctx, hipHostMalloc((void **)&cm->h_img, bytes, hipHostMallocDefault));
+        cm->h_img_cap = bytes;
+    }
+    if (bytes > cm->img_cap) {
+        if (cm->d_img) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(cm->d_img)); cm->d_img = nullptr; cm->img_cap = 0; }
+        HIPCHK(ctx, hipMalloc((void **)&cm->d_img, bytes));
+        cm->img_cap = bytes;
+    }
+    cm->img_rows = 0; cm->img_cols = 0;
+    if (row_stride_bytes == (int64_t)row_bytes) std::memcpy(cm->h_img, bgr, bytes);
+    else for (int r = 0; r < rows; r++) std::memcpy(cm->h_img + (size_t)r * row_bytes, bgr + (size_t)r * (size_t)row_stride_bytes, row_bytes);
+    HIPCHK(ctx, hipMemcpyAsync(cm->d_img, cm->h_img, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(cm->img_ev, ctx->stream));
+    cm->img_pending = true;
+    cm->render_on = true;                 // from here on the colour state exists and follows the pool
+    { const int rc = srl_color_state_reserve(ctx, cm); if (rc) return rc; }
+    cm->img_rows = rows; cm->img_cols = cols;
+    return SRL_OK;
+}
+
+extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, const int32_t *voxels_xyz, int n_voxels, double obs_time,
+                                    srl_color_render_totals *totals) {
+    if (totals) std::memset(totals, 0, sizeof *totals);
+    if (!ctx || !cam || n_voxels < 0 || (n_voxels > 0 && !voxels_xyz)) return SRL_ERR_BAD_ARG;
+    {
+        bool finite = std::isfinite(obs_time) && std::isfinite(cam->fx) && std::isfinite(cam->fy) && std::isfinite(cam->cx) && std::isfinite(cam->cy) &&
+                      std::isfinite(cam->fov_margin);
+        for (int k = 0; k < 4; k++) finite = finite && std::isfinite(cam->q_world_camera[k]);
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(cam->t_world_camera[k]);
+        if (!finite) { ctx->err = "render: camera and observation time must be finite"; return SRL_ERR_BAD_ARG; }
+        if (!(cam->fov_margin > 0.0)) { ctx->err = "render: fov_margin must be > 0 (at 0 an integral u = cols - 1 reads one pixel past the row)"; return SRL_ERR_BAD_ARG; }
+    }
+    SrlColorMap *cm = ctx->color;
+    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
+    if (cm->img_rows == 0) { ctx->err = "no image uploaded (srl_color_image_upload)"; return SRL_ERR_NO_SWEEP; }
+    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    if (n_voxels == 0) return SRL_OK;
+    SRL_DISARM(ctx);                      // a waiting launch holds a workgroup on every compute unit
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+
+    // refreshPoseForProjection (lioOptimization.cpp:201-205) and the bounds of if2dPointsAvailable (:55-56)
+    RenderArgs A;
+    {
+        const srl::Quat q(cam->q_world_camera[0], cam->q_world_camera[1], cam->q_world_camera[2], cam->q_world_camera[3]);
+        const srl::Quat q_cw = q.inverse();
+        const srl::Mat3 R = q_cw.toRotationMatrix();
+        const srl::Vec3 t_wc = srl::vec3(cam->t_world_camera[0], cam->t_world_camera[1], cam->t_world_camera[2]);
+        const srl::Vec3 t_cw = (-R) * t_wc;
+        for (int k = 0; k < 9; k++) A.R[k] = R.a[k];
+        for (int k = 0; k < 3; k++) { A.t_cw[k] = t_cw[k]; A.t_wc[k] = t_wc[k]; }
+        for (int k = 0; k < 12; k++) if (!std::isfinite(k < 9 ? A.R[k] : A.t_cw[k - 9])) { ctx->err = "render: camera pose is not finite"; return SRL_ERR_BAD_ARG; }
+        A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy;
+        const double m = cam->fov_margin;
+        A.rows = cm->img_rows; A.cols = cm->img_cols;
+        A.u_lo = m * A.cols + 1; A.u_hi = (1 - m) * A.cols;
+        A.v_lo = m * A.rows + 1; A.v_hi = (1 - m) * A.rows;
+        A.obs_time = obs_time;
+    }
+    const long long P = cm->num_points;
+    const unsigned nblocks = (unsigned)((P + 255) / 256);
+    if (!cm->d_rtot) {
+        HIPCHK(ctx, hipMalloc((void **)&cm->d_rtot, SRL_RTOT_WORDS * sizeof(unsigned long long)));
+        HIPCHK(ctx, hipMemsetAsync(cm->d_rtot, 0, SRL_RTOT_WORDS * sizeof(unsigned long long), st));
+        cm->unknown_seen = 0; cm->overflow_seen = 0;
+    }
+    if (cm->vtab_cap == 0) {              // a map nothing was ever inserted into: every key is unknown
+        if (totals) totals->unknown = n_voxels;
+        return SRL_OK;
+    }
+    if (cm->mark_cap < cm->vox_cap) {
+        if (cm->d_mark) { HIPCHK(ctx, hipStreamSynchronize(st)); HIPCHK(ctx, hipFree(cm->d_mark)); cm->d_mark = nullptr; cm->mark_cap = 0; }
+        HIPCHK(ctx, hipMalloc((void **)&cm->d_mark, (size_t)cm->vox_cap * sizeof(unsigned)));
+        HIPCHK(ctx, hipMemsetAsync(cm->d_mark, 0, (size_t)cm->vox_cap * sizeof(unsigned), st));
+        cm->mark_cap = cm->vox_cap;
+    }
+    if (++cm->render_epoch > 0xFFFFu) {
+        cm->render_epoch = 1;
+        HIPCHK(ctx, hipMemsetAsync(cm->d_mark, 0, (size_t)cm->mark_cap * sizeof(unsigned), st));
+    }
+    if (nblocks > cm->rpart_rows) {
+        if (cm->d_rpart) { HIPCHK(ctx, hipStreamSynchronize(st)); HIPCHK(ctx, hipFree(cm->d_rpart)); cm->d_rpart = nullptr; cm->rpart_rows = 0; }
+        const size_t rows = (size_t)nblocks + nblocks / 2 + 64;
+        HIPCHK(ctx, hipMalloc((void **)&cm->d_rpart, rows * 8 * sizeof(unsigned)));
+        cm->rpart_rows = rows;
+    }
+    { const int rc = srl_color_state_reserve(ctx, cm); if (rc) return rc; }
+    DevBuf b_list;
+    HIPCHK(ctx, b_list.alloc(ctx, (size_t)n_voxels * 12));
+    { const int rc = ensure_host_scratch(ctx, (size_t)n_voxels * 12 + 128); if (rc) return rc; }
+    std::memcpy(ctx->h_scratch + 128, voxels_xyz, (size_t)n_voxels * 12);
+    HIPCHK(ctx, hipMemcpyAsync(b_list.p, ctx->h_scratch + 128, (size_t)n_voxels * 12, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_render_mark, dim3((n_voxels + 255) / 256), dim3(256), 0, st, b_list.as<int>(), n_voxels, cm->d_vtab, cm->vtab_cap - 1, cm->d_mark,
+                       cm->render_epoch, cm->d_rtot);
+    HIPCHK(ctx, hipGetLastError());
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(k_render_points, dim3(nblocks), dim3(256), 0, st, P, cm->d_pool, cm->d_mark, cm->render_epoch, cm->d_state, cm->d_img, A,
+                           cm->overflow_seen, cm->d_rpart, cm->d_rtot);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->d_rtot, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    cm->img_pending = false;
+    unsigned long long h[8];
+    std::memcpy(h, ctx->h_scratch, sizeof h);
+    const unsigned long long unknown = h[SRL_RTOT_UNKNOWN] - cm->unknown_seen, overflow = h[SRL_RTOT_OVERFLOW] - cm->overflow_seen;
+    cm->unknown_seen = h[SRL_RTOT_UNKNOWN]; cm->overflow_seen = h[SRL_RTOT_OVERFLOW];
+    if (overflow) { ctx->err = "render: the list names one voxel more than 65 535 times (nothing was rendered)"; return SRL_ERR_UNSUPPORTED; }
+    if (totals) {
+        if (nblocks > 0) {
+            totals->listed = (int64_t)h[RC_LISTED]; totals->behind = (int64_t)h[RC_BEHIND]; totals->outside = (int64_t)h[RC_OUTSIDE];
+            totals->gated = (int64_t)h[RC_GATED]; totals->first = (int64_t)h[RC_FIRST]; totals->updated = (int64_t)h[RC_UPDATED];
+        }
+        totals->unknown = (int64_t)unknown;
+    }
+    return SRL_OK;
+}
+
+extern "C" int srl_color_map_download_rgb(srl_ctx *ctx, int16_t *rgb, int16_t *n_rgb, float *cov_rgb, double *observe_distance, double *last_observe_time,
+                                          int64_t max_points) {
+    if (!ctx) return SRL_ERR_BAD_ARG;
+    const SrlColorMap *cm = ctx->color;
+    if (!cm) return SRL_ERR_NO_MAP;
+    const int V = cm->num_voxels;
+    const long long P = cm->num_points;
+    if (max_points < P) return SRL_ERR_BAD_ARG;
+    if (P == 0) return SRL_OK;
+    if (!cm->d_state) {                   // never rendered: every point is as rgbPoint::reset() left it
+        const SrlColorState zero = {};
+        for (long long p = 0; p < P; p++) split_state(zero, (size_t)p, rgb, n_rgb, cov_rgb, observe_distance, last_observe_time);
+        return SRL_OK;
+    }
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<SrlColorVoxel> vox((size_t)V);
+    std::vector<SrlColorPoint> pool((size_t)P);
+    std::vector<SrlColorState> state((size_t)P);
+    HIPCHK(ctx, hipMemcpyAsync(vox.data(), cm->d_vox, (size_t)V * sizeof(SrlColorVoxel), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(pool.data(), cm->d_pool, (size_t)P * sizeof(SrlColorPoint), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(state.data(), cm->d_state, (size_t)P * sizeof(SrlColorState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<long long> first((size_t)V + 1, 0);
+    for (int v = 0; v < V; v++) first[(size_t)v + 1] = first[v] + vox[v].count;
+    if (first[V] != P) { ctx->err = "colour map: voxel counts and point pool disagree"; return SRL_ERR_HIP; }
+    for (long long p = 0; p < P; p++) {
+        const SrlColorPoint &pt = pool[(size_t)p];
+        split_state(state[(size_t)p], (size_t)(first[pt.voxel] + pt.slot), rgb, n_rgb, cov_rgb, observe_distance, last_observe_time);      // voxel after voxel, slot order
+    }
+    return SRL_OK;
+}
+
+extern "C" int srl_color_registered_rgb(srl_ctx *ctx, int64_t first, int count, int16_t *rgb, int16_t *n_rgb, float *cov_rgb, double *observe_distance,
+                                        double *last_observe_time) {
+    if (!ctx || first < 0 || count < 0) return SRL_ERR_BAD_ARG;
+    const SrlColorMap *cm = ctx->color;
+    if (!cm) return SRL_ERR_NO_MAP;
+    if (first + count > cm->num_registered) return SRL_ERR_BAD_ARG;
+    if (count == 0) return SRL_OK;
+    if (!cm->d_state) {
+        const SrlColorState zero = {};
+        for (int t = 0; t < count; t++) split_state(zero, (size_t)t, rgb, n_rgb, cov_rgb, observe_distance, last_observe_time);
+        return SRL_OK;
+    }
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf b_out;
+    HIPCHK(ctx, b_out.alloc(ctx, (size_t)count * sizeof(SrlColorState)));
+    { const int rc = ensure_host_scratch(ctx, (size_t)count * sizeof(SrlColorState)); if (rc) return rc; }
+    hipLaunchKernelGGL(k_render_reg_gather, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, cm->d_reg, (long long)first, count, cm->d_state,
+                       b_out.as<SrlColorState>());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, b_out.p, (size_t)count * sizeof(SrlColorState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const SrlColorState *s = reinterpret_cast<const SrlColorState *>(ctx->h_scratch);
+    for (int t = 0; t < count; t++) split_state(s[t], (size_t)t, rgb, n_rgb, cov_rgb, observe_distance, last_observe_time);
+    return SRL_OK;
+}

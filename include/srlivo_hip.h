@@ -220,8 +220,8 @@ int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_co
  * cloudFrame::getRgb(u, v, 0) = getSubPixel<cv::Vec3b> (:71-103) and rgbPoint::updateRgb(colour, distance, (15, 15, 15), obs_time)
  * (cloudMap.cpp:59-100).  The per-point colour state (rgb int16 x 3, cov_rgb FP32 x 3, observe_distance, last_observe_time, N_rgb int16:
  * cloudMap.h:51-66) lives in HBM beside the point pool, 40 bytes per stored point, allocated at the first srl_color_image_upload; zero
- * bytes are rgbPoint::reset().  The rest of the vision stage (optical flow, PnP, vioEsikf, vioPhotometric, selectPointsForProjection,
- * undistortion and equalisation of the image, the publishers) stays with the caller.
+ * bytes are rgbPoint::reset().  selectPointsForProjection is srl_color_map_select below; the rest of the vision stage (optical flow, PnP,
+ * vioEsikf, vioPhotometric, undistortion and equalisation of the image, the publishers) stays with the caller.
  *
  * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
  *   p = (double) stored FP32 position; pc = R_cw p + t_cw with q_cw = q_world_camera.inverse(), R_cw = q_cw.toRotationMatrix(),
@@ -243,7 +243,7 @@ typedef struct srl_color_camera {
     double q_world_camera[4];            /* w, x, y, z (state.h) */
     double t_world_camera[3];
     double fx, fy, cx, cy;
-    double fov_margin;                   /* state.cpp:25: 0.005; must be > 0 (at 0 an integral u = cols - 1 reads past the row) */
+    double fov_margin;                   /* state.cpp:25: 0.005; the render needs > 0 (at 0 an integral u = cols - 1 reads past the row) */
 } srl_color_camera;
 /* of one render, counted per occurrence of a voxel in the list: points of listed voxels; of those rejected behind the camera, rejected
  * by the field of view, refused by updateRgb's distance gate, first observations, updates (the reference's render_point_count); and the
@@ -277,6 +277,53 @@ int srl_color_map_download_rgb(srl_ctx *ctx, int16_t *rgb, int16_t *n_rgb, float
  * lioOptimization.cpp:1228-1230, 1290-1292, 1414-1416).  One gather kernel and one DMA of exactly count records. */
 int srl_color_registered_rgb(srl_ctx *ctx, int64_t first, int count, int16_t *rgb, int16_t *n_rgb, float *cov_rgb, double *observe_distance,
                              double *last_observe_time);
+
+/* ------------------------------------------------------------------ colour voxel map: selecting points for projection
+ * replaces: rgbMapTracker::selectPointsForProjection (rgbMapTracker.cpp:45-152), as refreshPointsForProjection (:26-43) and the tracker's
+ * own call (imageProcessing.cpp:131) use it.  Candidates points_for_projection[i]: in LIST mode (use_all_points clear and n_voxels > 0)
+ * the last point (points.back(): the highest slot) of every list entry whose voxel the map holds, once per occurrence, in list order --
+ * an entry the map does not hold is counted in totals->unknown and takes no index (the reference's map[voxel] creates an empty block
+ * there); otherwise ALL registered points, rgb_points_vec in order.  For i = 0, skip_step, 2 skip_step, ...:
+ *   p = (double) stored FP32 position; depth = |p - t_world_camera| (the render's d); skipped if depth > maximum_depth, then if
+ *   depth < minimum_depth (a depth equal to a limit stays); project3dPointInThisImage(p, u_f, v_f, nullptr, 1.0) exactly as the render
+ *   carries it; the cell key is the pair of int u = (int)(round(u_f / minimum_dis) * minimum_dis), v likewise: FP64 quotient, rounding
+ *   half away from zero, FP64 product, truncation toward zero (for a non-integral or sub-unit minimum_dis distinct quotients can share a
+ *   key); the cell keeps (float) depth of its last setter, and candidate i takes the cell iff it is empty or (double) stored > depth_i.
+ * The output is the final holder of every cell, ascending in i, with cv::Point2f(u_f, v_f) = two casts to float.  Because the stored
+ * depth is rounded the holder is not simply the nearest candidate: with M the smallest (float) depth of the cell it is the LAST i with
+ * depth_i < (double) M if there is one, otherwise the FIRST i with (float) depth_i == M.  The device evaluates this rule with integer
+ * atomics per cell; results are bitwise those of the reference's sequential loop and reproducible.
+ * No image is needed (image_rows / image_cols are the frame's size: the pass reads no pixel).  fov_margin may be <= 0 here -- the
+ * tracker's own frame uses -0.4 (rgbMapTracker.cpp:157, :164): any finite margin with -4 <= margin < 0.5.
+ * Synchronous: one wait for the totals, then one DMA of exactly totals->selected records.  out == NULL: the totals alone.
+ * capacity < selected: SRL_ERR_BAD_ARG with the totals filled and nothing copied (the call changes nothing in the map: ask again).
+ * Before a device is touched: NULL ctx, cam, opts or (n_voxels > 0) voxels_xyz, n_voxels < 0, capacity < 0, a bad option, rows or cols
+ * < 2, rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS, a non-finite camera, a margin outside [-4, 0.5): SRL_ERR_BAD_ARG; no colour map:
+ * SRL_ERR_NO_MAP; more than one rank: SRL_ERR_UNSUPPORTED.  Cancels an armed launch.  Neither map, nor the colour state, the neighbourhood
+ * bounds or the taps are touched. */
+typedef struct srl_color_select_opts {
+    double minimum_dis;          /* finite, 0 < minimum_dis <= 65536 */
+    int32_t skip_step;           /* >= 1 */
+    int32_t use_all_points;
+    double minimum_depth, maximum_depth;     /* not NaN */
+} srl_color_select_opts;
+/* 10.0, 1, 0, 0.1, 200 (rgbMapTracker.cpp:9-10, :36) */
+void srl_color_select_opts_default(srl_color_select_opts *o);
+typedef struct srl_color_selected {
+    int32_t index;               /* position in points_for_projection */
+    int32_t pool;                /* pool position = batch_index of srl_color_registered_download */
+    int32_t point_index;         /* registered index or -1 */
+    float x, y, z;
+    float u, v;
+} srl_color_selected;
+/* candidates: size of points_for_projection; visited: those with i % skip_step == 0; of those: beyond maximum_depth, nearer than
+ * minimum_depth, behind the camera, outside the field of view; selected: cells = records; unknown: list entries the map does not hold */
+typedef struct srl_color_select_totals {
+    int64_t candidates, visited, far, near, behind, outside, selected, unknown;
+} srl_color_select_totals;
+int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, int image_rows, int image_cols, const int32_t *voxels_xyz, int n_voxels,
+                         const srl_color_select_opts *opts, srl_color_selected *out /* or NULL */, int64_t capacity,
+                         srl_color_select_totals *totals /* or NULL */);
 
 /* ------------------------------------------------------------------ sweep
  * replaces: the `keypoints` vector handed to updateIEKF (optimize.cpp:133; point3D::raw_point,

@@ -82,6 +82,15 @@ int srl_lio_color_stored(srl_lio *lio, srl_color_stored *out, int capacity, int 
  * left; repeats included).  totals (optional) is zeroed first.  NULL lio or camera: SRL_ERR_BAD_ARG; a host-only handle:
  * SRL_ERR_NO_DEVICE; otherwise the codes of srl_color_map_render. */
 int srl_lio_render_points_in_recent_voxel(srl_lio *lio, const srl_color_camera *camera, double obs_time, srl_color_render_totals *totals);
+/* rgbMapTracker::selectPointsForProjection (rgbMapTracker.cpp:45-152): srl_color_map_select over voxels_recent_visited with the object's
+ * minimum_depth_for_projection / maximum_depth_for_projection (0.1, 200).  refresh != 0: refreshPointsForProjection (:26-43) -- the
+ * parameters (10.0, 1, list mode) whatever is passed, SRL_OK with *n = 0 at once when rows or cols is 0, and the result kept by the object
+ * as points_for_projection.  *n = the number of records; capacity 0 asks for the number (and the totals) alone, a smaller capacity than
+ * *n is SRL_ERR_BAD_ARG.  NULL lio, camera or n: SRL_ERR_BAD_ARG; a host-only handle: SRL_ERR_NO_DEVICE; otherwise the codes of
+ * srl_color_map_select. */
+int srl_lio_select_points_for_projection(srl_lio *lio, const srl_color_camera *camera, int rows, int cols, double minimum_dis, int skip_step,
+                                         int use_all_points, int refresh, srl_color_selected *out, int capacity, int *n,
+                                         srl_color_select_totals *totals);
 /* Where lioOptimization::buildFrame sub-samples the cut sweep (subSampleFrame, lioOptimization.cpp:838-846): on = 1 (the default) on the
  * device (srl_frame_subsample + srl_frame_take_subsampled; the host runs the two shuffles on index arrays and downloads m points), 0 = on the
  * host over the n-point downloads of srl_frame_undistort and srl_frame_take.  Both give the same frame bit for bit. */

@@ -15,6 +15,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 SRL_OK = 0
 SRL_ERR_NO_DEVICE = -1
+SRL_ERR_BAD_ARG = -3
 SRL_ERR_UNSUPPORTED = -4
 SRL_ERR_COMM = -7
 SRL_ERR_NAN_PLANARITY = -8
@@ -84,6 +85,25 @@ class ColorRenderTotals(C.Structure):
     def as_tuple(self):
         return tuple(int(getattr(self, f)) for f, _ in self._fields_)
 
+
+class ColorSelectOpts(C.Structure):
+    """srl_color_select_opts: the arguments of selectPointsForProjection and the tracker's two depth limits"""
+    _fields_ = [("minimum_dis", C.c_double), ("skip_step", C.c_int32), ("use_all_points", C.c_int32), ("minimum_depth", C.c_double),
+                ("maximum_depth", C.c_double)]
+
+
+class ColorSelectTotals(C.Structure):
+    """srl_color_select_totals: what one srl_color_map_select did"""
+    _fields_ = [("candidates", C.c_int64), ("visited", C.c_int64), ("far", C.c_int64), ("near", C.c_int64), ("behind", C.c_int64),
+                ("outside", C.c_int64), ("selected", C.c_int64), ("unknown", C.c_int64)]
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, f)) for f, _ in self._fields_)
+
+
+# srl_color_selected: records.view(COLOR_SELECTED_DTYPE)
+COLOR_SELECTED_DTYPE = np.dtype([("index", "<i4"), ("pool", "<i4"), ("point_index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                                 ("u", "<f4"), ("v", "<f4")])
 
 # srl_color_stored: records.view(COLOR_STORED_DTYPE)
 COLOR_STORED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("kx", "<i2"), ("ky", "<i2"), ("kz", "<i2"), ("slot", "<u2"),
@@ -168,6 +188,9 @@ def load_library():
         "srl_color_registered_download": ([p, C.c_int64, C.c_int, p], C.c_int),
         "srl_debug_color_map_rebuilds": ([p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "srl_color_image_upload": ([p, p, C.c_int, C.c_int, C.c_int64], C.c_int),
+        "srl_color_select_opts_default": ([C.POINTER(ColorSelectOpts)], None),
+        "srl_color_map_select": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, C.POINTER(ColorSelectOpts), p, C.c_int64,
+                                  C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_color_map_render": ([p, C.POINTER(ColorCamera), p, C.c_int, C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
         "srl_color_map_download_rgb": ([p, p, p, p, p, p, C.c_int64], C.c_int),
         "srl_color_registered_rgb": ([p, C.c_int64, C.c_int, p, p, p, p, p], C.c_int),
@@ -265,6 +288,8 @@ def load_library():
         "srl_lio_set_color_map_options": ([p, C.POINTER(ColorOpts)], C.c_int),
         "srl_lio_set_color_times": ([p, C.c_double, C.c_double, C.c_int], C.c_int),
         "srl_lio_add_points_to_map_at": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
+        "srl_lio_select_points_for_projection": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, p, C.c_int,
+                                                  C.POINTER(C.c_int), C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_lio_color_visited": ([p, C.c_int, p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "srl_lio_color_stored": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_render_points_in_recent_voxel": ([p, C.POINTER(ColorCamera), C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
@@ -349,6 +374,14 @@ def default_opts(**kw):
 def default_color_opts(**kw):
     o = ColorOpts()
     load_library().srl_color_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_color_select_opts(**kw):
+    o = ColorSelectOpts()
+    load_library().srl_color_select_opts_default(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -609,6 +642,22 @@ class Context:
         self._chk(self.lib.srl_color_map_render(self.h, C.byref(camera), _ptr(v) if len(v) else None, len(v), float(obs_time), C.byref(tot)),
                   "srl_color_map_render")
         return tot
+
+    def color_map_select(self, camera, rows, cols, voxels_xyz=None, opts=None, totals_only=False):
+        """srl_color_map_select: camera = ColorCamera, voxels_xyz (n, 3) int32 or None (all points), opts = ColorSelectOpts (None = 10.0, 1,
+        list mode, 0.1, 200).  Returns (records (COLOR_SELECTED_DTYPE), ColorSelectTotals): the totals are asked for first, then the
+        records at their exact number (the call changes nothing in the map)."""
+        v = np.zeros((0, 3), np.int32) if voxels_xyz is None else np.ascontiguousarray(voxels_xyz, dtype=np.int32).reshape(-1, 3)
+        o = default_color_select_opts() if opts is None else opts
+        tot = ColorSelectTotals()
+        lp = _ptr(v) if len(v) else None
+        self._chk(self.lib.srl_color_map_select(self.h, C.byref(camera), int(rows), int(cols), lp, len(v), C.byref(o), None, 0, C.byref(tot)),
+                  "srl_color_map_select")
+        out = np.zeros(tot.selected, dtype=COLOR_SELECTED_DTYPE)
+        if tot.selected and not totals_only:
+            self._chk(self.lib.srl_color_map_select(self.h, C.byref(camera), int(rows), int(cols), lp, len(v), C.byref(o), _ptr(out), len(out),
+                                                    C.byref(tot)), "srl_color_map_select")
+        return out, tot
 
     @staticmethod
     def _color_state_arrays(n):
@@ -1152,6 +1201,24 @@ class Lio:
         self._chk(self.lib.srl_lio_render_points_in_recent_voxel(self.h, C.byref(camera), float(obs_time), C.byref(tot)),
                   "srl_lio_render_points_in_recent_voxel")
         return tot
+
+    def select_points_for_projection(self, camera, rows, cols, minimum_dis=10.0, skip_step=1, use_all_points=False, refresh=False):
+        """rgbMapTracker::selectPointsForProjection on voxels_recent_visited (srl_lio_select_points_for_projection); refresh=True is
+        refreshPointsForProjection.  Returns (records (COLOR_SELECTED_DTYPE), ColorSelectTotals)."""
+        m, tot = C.c_int(), ColorSelectTotals()
+        args = (C.byref(camera), int(rows), int(cols), float(minimum_dis), int(skip_step), 1 if use_all_points else 0, 1 if refresh else 0)
+        # one call into a buffer sized by what earlier calls selected; only a call that selects more than that is asked again
+        out = np.zeros(max(getattr(self, "_select_capacity", 0), 4096), dtype=COLOR_SELECTED_DTYPE)
+        rc = self.lib.srl_lio_select_points_for_projection(self.h, *args, _ptr(out), len(out), C.byref(m), C.byref(tot))
+        if rc == SRL_ERR_BAD_ARG and m.value > len(out):
+            out = np.zeros(m.value, dtype=COLOR_SELECTED_DTYPE)
+            rc = self.lib.srl_lio_select_points_for_projection(self.h, *args, _ptr(out), len(out), C.byref(m), C.byref(tot))
+        self._chk(rc, "srl_lio_select_points_for_projection")
+        self._select_capacity = max(getattr(self, "_select_capacity", 0), m.value + m.value // 2)
+        return out[:m.value].copy(), tot
+
+    def refresh_points_for_projection(self, camera, rows, cols):
+        return self.select_points_for_projection(camera, rows, cols, refresh=True)
 
     def set_device_subsample(self, on):
         """buildFrame's sub-sample on the device (True, the default) or on the host (srl_lio_set_device_subsample)"""

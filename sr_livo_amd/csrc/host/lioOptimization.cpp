@@ -541,6 +541,34 @@ void lioOptimization::renderPointsInRecentVoxel(const srl_color_camera &camera, 
     check(ctx, srl_color_map_render(ctx, &camera, list.data(), (int)voxels_recent_visited.size(), obs_time, &render_totals), "srl_color_map_render");
 }
 
+std::vector<srl_color_selected> lioOptimization::selectPointsForProjection(const srl_color_camera &camera, int rows, int cols, double minimum_dis, int skip_step,
+                                                                           bool use_all_points) {
+    srl_ctx *ctx = voxel_map.ctx;
+    if (!ctx) throw std::runtime_error("selectPointsForProjection: no HIP context (the product has no CPU path)");
+    std::vector<int32_t> list(voxels_recent_visited.size() * 3);
+    for (size_t k = 0; k < voxels_recent_visited.size(); k++) {
+        list[k * 3] = voxels_recent_visited[k].kx; list[k * 3 + 1] = voxels_recent_visited[k].ky; list[k * 3 + 2] = voxels_recent_visited[k].kz;
+    }
+    const srl_color_select_opts o = {minimum_dis, skip_step, use_all_points ? 1 : 0, minimum_depth_for_projection, maximum_depth_for_projection};
+    // ONE call into a buffer sized by what earlier calls selected; only a call that selects more than that is asked again (it changes
+    // nothing in the map, and its totals name the number)
+    std::vector<srl_color_selected> out(std::max<size_t>(select_capacity, 4096));
+    int rc = srl_color_map_select(ctx, &camera, rows, cols, list.data(), (int)voxels_recent_visited.size(), &o, out.data(), (int64_t)out.size(), &select_totals);
+    if (rc == SRL_ERR_BAD_ARG && select_totals.selected > (int64_t)out.size()) {
+        out.resize((size_t)select_totals.selected);
+        rc = srl_color_map_select(ctx, &camera, rows, cols, list.data(), (int)voxels_recent_visited.size(), &o, out.data(), (int64_t)out.size(), &select_totals);
+    }
+    check(ctx, rc, "srl_color_map_select");
+    select_capacity = std::max(select_capacity, (size_t)select_totals.selected + (size_t)select_totals.selected / 2);
+    out.resize((size_t)select_totals.selected);
+    return out;
+}
+
+void lioOptimization::refreshPointsForProjection(const srl_color_camera &camera, int rows, int cols) {
+    if (cols == 0 || rows == 0) return;                                  // rgbMapTracker.cpp:30
+    points_for_projection = selectPointsForProjection(camera, rows, cols, 10.0, 1);      // :36
+}
+
 void lioOptimization::removePointsFarFromLocation(voxelHashMap &map, const srl::Vec3 &location, double distance) {
     if (!map.ctx) throw std::runtime_error("removePointsFarFromLocation: no HIP context (the product has no CPU path)");
     check(map.ctx, srl_map_remove_far(map.ctx, location.a, distance, nullptr, nullptr), "srl_map_remove_far");

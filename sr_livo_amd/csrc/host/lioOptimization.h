@@ -218,6 +218,18 @@ public:
     // under `to_rendering`.  Neither list is changed.  render_totals: what the pass did (updated = the reference's render_point_count).
     void renderPointsInRecentVoxel(const srl_color_camera &camera, double obs_time);
     srl_color_render_totals render_totals = {0, 0, 0, 0, 0, 0, 0};
+    // rgbMapTracker::selectPointsForProjection (rgbMapTracker.cpp:45-152) on the device colour map (srl_color_map_select) over
+    // voxels_recent_visited: one point per coarse image cell, the nearest by the reference's float depth mask, with its pixel position --
+    // what the optical-flow tracker takes.  refreshPointsForProjection (:26-43): the same with (10.0, 1), nothing when the frame has no
+    // image size, the result kept as points_for_projection (the reference's points_rgb_vec_for_projection).  select_totals: the last call's.
+    double minimum_depth_for_projection = 0.1;                           // rgbMapTracker.cpp:9
+    double maximum_depth_for_projection = 200;                           // rgbMapTracker.cpp:10
+    std::vector<srl_color_selected> selectPointsForProjection(const srl_color_camera &camera, int rows, int cols, double minimum_dis = 10.0, int skip_step = 1,
+                                                              bool use_all_points = false);
+    void refreshPointsForProjection(const srl_color_camera &camera, int rows, int cols);
+    std::vector<srl_color_selected> points_for_projection;
+    srl_color_select_totals select_totals = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t select_capacity = 0;                                          // records the one call per frame has room for: 1.5 x the most selected so far
     bool collectPointsWorld() const { return collect_points_world; }
 
     // ---- ours ----

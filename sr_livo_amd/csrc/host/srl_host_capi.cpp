@@ -303,6 +303,30 @@ int srl_lio_render_points_in_recent_voxel(srl_lio *h, const srl_color_camera *ca
     return SRL_OK;
 }
 
+int srl_lio_select_points_for_projection(srl_lio *h, const srl_color_camera *camera, int rows, int cols, double minimum_dis, int skip_step, int use_all_points,
+                                         int refresh, srl_color_selected *out, int capacity, int *n, srl_color_select_totals *totals) {
+    if (n) *n = 0;
+    if (totals) std::memset(totals, 0, sizeof *totals);
+    if (!h || !camera || !n || capacity < 0 || (capacity > 0 && !out)) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }
+    std::vector<srl_color_selected> mine;
+    const std::vector<srl_color_selected> *rec = &mine;
+    try {
+        if (refresh) {
+            if (rows == 0 || cols == 0) return SRL_OK;                   // refreshPointsForProjection returns at once: nothing is selected, nothing kept
+            h->lio->refreshPointsForProjection(*camera, rows, cols);
+            rec = &h->lio->points_for_projection;
+        } else {
+            mine = h->lio->selectPointsForProjection(*camera, rows, cols, minimum_dis, skip_step, use_all_points != 0);
+        }
+    } catch (const std::exception &e) { return status_from_exception(h, e); }
+    *n = (int)rec->size();
+    if (totals) *totals = h->lio->select_totals;
+    if ((int)rec->size() > capacity) return capacity == 0 ? SRL_OK : SRL_ERR_BAD_ARG;
+    if (!rec->empty()) std::memcpy(out, rec->data(), rec->size() * sizeof(srl_color_selected));
+    return SRL_OK;
+}
+
 int srl_lio_set_device_subsample(srl_lio *h, int on) {
     if (!h) return SRL_ERR_BAD_ARG;
     h->lio->device_subsample = on != 0;

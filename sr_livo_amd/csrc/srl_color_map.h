@@ -1,5 +1,5 @@
-// srl_color_map.h -- internal: the colour voxel map's device layout, shared by its construction (srl_color_kernels.hip) and its first
-// consumer, the rendering pass (srl_color_render.hip).  DESIGN.md section 3.
+// srl_color_map.h -- internal: the colour voxel map's device layout, shared by its construction (srl_color_kernels.hip) and its
+// consumers, the rendering pass (srl_color_render.hip) and the selection for projection (srl_color_select.hip).  DESIGN.md section 3.
 #pragma once
 #include "srl_ctx.h"
 
@@ -38,9 +38,38 @@ struct SrlColorMap {
     unsigned long long *d_rtot = nullptr;                         // [0..5] totals of the last render, [6] unknown keys and [7] overflowing marks
                                                                   // (both since allocation: never reset), [8] the workgroup ticket
     unsigned long long unknown_seen = 0, overflow_seen = 0;       // host copies of [6] and [7] as of the previous render
+
+    // selection for projection (srl_color_select.hip); nothing of it exists before the first srl_color_map_select
+    int *d_tail = nullptr;             unsigned tail_cap = 0;     // per voxel: pool position of its last point (slot == count - 1)
+    long long tail_swept = 0;                                     // pool positions [0, tail_swept) have been swept into d_tail
+    SrlEpochTable sel_cells;                                      // image cell -> slot; minw = {~call counter, float bits of the cell's smallest depth}
+    unsigned long long *d_sel_last = nullptr;                     // per slot {~call counter, ~(last index whose depth lies below the float minimum)}
+    unsigned long long *d_sel_first = nullptr;                    // per slot {~call counter, first index whose depth rounds to the float minimum}
+    unsigned sel_words_cap = 0;
+    unsigned *d_spart = nullptr;       size_t spart_rows = 0;     // per-workgroup counter rows of k_select_cells (4 words each)
+    unsigned long long *d_stot = nullptr;                         // [0..3] far, near, behind, outside of the last selection, [4] the workgroup ticket
 };
+
+#if defined(__HIPCC__)
+#include "srl_hash.h"
+// the voxel an entry (x, y, z) of a caller's list names, or -1 for a key the map does not hold (vmask = vtab_cap - 1)
+__device__ __forceinline__ int srl_color_find_voxel(const SrlColorSlot *vtab, unsigned vmask, int x, int y, int z) {
+    if (!(x >= -32768 && x <= 32767 && y >= -32768 && y <= 32767 && z >= -32768 && z <= 32767)) return -1;      // voxelId holds what a voxel's shorts held
+    const unsigned long long key = srl_pack_key((short)x, (short)y, (short)z);
+    unsigned h = srl_hash_key(key) & vmask;
+    for (unsigned probe = 0; probe <= vmask; ++probe) {
+        const unsigned long long k = vtab[h].key;
+        if (k == key) return (int)vtab[h].voxel;
+        if (k == SRL_EMPTY_KEY) return -1;
+        h = (h + 1) & vmask;
+    }
+    return -1;
+}
+#endif
 
 // the state array follows the pool (x1.5 by copy, zero-filled tail) once rendering is on; called behind every pool growth
 int srl_color_state_reserve(srl_ctx *ctx, SrlColorMap *cm);
 // frees what rendering allocated (srl_color_map_destroy)
 void srl_color_render_free(SrlColorMap *cm);
+// frees what the selection allocated (srl_color_map_destroy)
+void srl_color_select_free(SrlColorMap *cm);

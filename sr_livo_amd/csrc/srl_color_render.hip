@@ -16,6 +16,7 @@
 // right; the channels become doubles only then.
 #include "srl_ctx.h"
 #include "srl_color_map.h"
+#include "srl_color_project.h"
 #include "srl_hash.h"
 #include "host/srl_la.h"
 
@@ -26,9 +27,7 @@
 namespace {
 
 struct RenderArgs {
-    double R[9], t_cw[3], t_wc[3];     // q_camera_world.toRotationMatrix(), t_camera_world, t_world_camera
-    double fx, fy, cx, cy;
-    double u_lo, u_hi, v_lo, v_hi;     // m cols + 1, (1 - m) cols, m rows + 1, (1 - m) rows
+    SrlCamArgs C;                      // the pose, the intrinsics and the bounds of the field of view (srl_color_project.h)
     double obs_time;
     int rows, cols;
 };
@@ -41,18 +40,7 @@ enum { RC_LISTED, RC_BEHIND, RC_OUTSIDE, RC_GATED, RC_FIRST, RC_UPDATED, RC_N };
 __global__ void k_render_mark(const int *voxels_xyz, int n, const SrlColorSlot *vtab, unsigned vmask, unsigned *mark, unsigned epoch, unsigned long long *rtot) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    const int x = voxels_xyz[(size_t)e * 3], y = voxels_xyz[(size_t)e * 3 + 1], z = voxels_xyz[(size_t)e * 3 + 2];
-    int v = -1;
-    if (x >= -32768 && x <= 32767 && y >= -32768 && y <= 32767 && z >= -32768 && z <= 32767) {      // voxelId holds what a voxel's shorts held
-        const unsigned long long key = srl_pack_key((short)x, (short)y, (short)z);
-        unsigned h = srl_hash_key(key) & vmask;
-        for (unsigned probe = 0; probe <= vmask; ++probe) {
-            const unsigned long long k = vtab[h].key;
-            if (k == key) { v = (int)vtab[h].voxel; break; }
-            if (k == SRL_EMPTY_KEY) break;
-            h = (h + 1) & vmask;
-        }
-    }
+    const int v = srl_color_find_voxel(vtab, vmask, voxels_xyz[(size_t)e * 3], voxels_xyz[(size_t)e * 3 + 1], voxels_xyz[(size_t)e * 3 + 2]);
     if (v < 0) { atomicAdd(&rtot[SRL_RTOT_UNKNOWN], 1ull); return; }
     unsigned old = mark[v];
     for (;;) {
@@ -94,18 +82,15 @@ __global__ void __launch_bounds__(256) k_render_points(long long P, const SrlCol
             const unsigned mult = w & 0xFFFFu;
             c[RC_LISTED] = mult;
             const double px = (double)pt.x, py = (double)pt.y, pz = (double)pt.z;
-            const double xc = ((A.R[0] * px + A.R[1] * py) + A.R[2] * pz) + A.t_cw[0];
-            const double yc = ((A.R[3] * px + A.R[4] * py) + A.R[5] * pz) + A.t_cw[1];
-            const double zc = ((A.R[6] * px + A.R[7] * py) + A.R[8] * pz) + A.t_cw[2];
-            if (zc < 0.001) {
+            double u, v;
+            const int outcome = srl_color_project(A.C, px, py, pz, &u, &v);
+            if (outcome == SRL_PROJ_BEHIND) {
                 c[RC_BEHIND] = mult;
             } else {
-                const double u = (xc * A.fx / zc + A.cx) * 1.0, v = (yc * A.fy / zc + A.cy) * 1.0;
-                if (!((u >= A.u_lo) && (ceil(u) < A.u_hi) && (v >= A.v_lo) && (ceil(v) < A.v_hi))) {
+                if (outcome == SRL_PROJ_OUTSIDE) {
                     c[RC_OUTSIDE] = mult;
                 } else {
-                    const double dx = px - A.t_wc[0], dy = py - A.t_wc[1], dz = pz - A.t_wc[2];
-                    const double d = sqrt((dx * dx + dy * dy) + dz * dz);
+                    const double d = srl_color_depth(A.C, px, py, pz);
                     // the test above leaves 1 <= floor < cols (rows); the clamps only ever move a neighbour of weight 0
                     const int r0 = (int)floor(v), c0 = (int)floor(u);
                     const double fr = v - (double)r0, fc = u - (double)c0;
@@ -256,10 +241,7 @@ extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, c
     if (totals) std::memset(totals, 0, sizeof *totals);
     if (!ctx || !cam || n_voxels < 0 || (n_voxels > 0 && !voxels_xyz)) return SRL_ERR_BAD_ARG;
     {
-        bool finite = std::isfinite(obs_time) && std::isfinite(cam->fx) && std::isfinite(cam->fy) && std::isfinite(cam->cx) && std::isfinite(cam->cy) &&
-                      std::isfinite(cam->fov_margin);
-        for (int k = 0; k < 4; k++) finite = finite && std::isfinite(cam->q_world_camera[k]);
-        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(cam->t_world_camera[k]);
+        const bool finite = std::isfinite(obs_time) && srl_color_cam_finite(cam);
         if (!finite) { ctx->err = "render: camera and observation time must be finite"; return SRL_ERR_BAD_ARG; }
         if (!(cam->fov_margin > 0.0)) { ctx->err = "render: fov_margin must be > 0 (at 0 an integral u = cols - 1 reads one pixel past the row)"; return SRL_ERR_BAD_ARG; }
     }
@@ -274,22 +256,8 @@ extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, c
 
     // refreshPoseForProjection (lioOptimization.cpp:201-205) and the bounds of if2dPointsAvailable (:55-56)
     RenderArgs A;
-    {
-        const srl::Quat q(cam->q_world_camera[0], cam->q_world_camera[1], cam->q_world_camera[2], cam->q_world_camera[3]);
-        const srl::Quat q_cw = q.inverse();
-        const srl::Mat3 R = q_cw.toRotationMatrix();
-        const srl::Vec3 t_wc = srl::vec3(cam->t_world_camera[0], cam->t_world_camera[1], cam->t_world_camera[2]);
-        const srl::Vec3 t_cw = (-R) * t_wc;
-        for (int k = 0; k < 9; k++) A.R[k] = R.a[k];
-        for (int k = 0; k < 3; k++) { A.t_cw[k] = t_cw[k]; A.t_wc[k] = t_wc[k]; }
-        for (int k = 0; k < 12; k++) if (!std::isfinite(k < 9 ? A.R[k] : A.t_cw[k - 9])) { ctx->err = "render: camera pose is not finite"; return SRL_ERR_BAD_ARG; }
-        A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy;
-        const double m = cam->fov_margin;
-        A.rows = cm->img_rows; A.cols = cm->img_cols;
-        A.u_lo = m * A.cols + 1; A.u_hi = (1 - m) * A.cols;
-        A.v_lo = m * A.rows + 1; A.v_hi = (1 - m) * A.rows;
-        A.obs_time = obs_time;
-    }
+    A.rows = cm->img_rows; A.cols = cm->img_cols; A.obs_time = obs_time;
+    if (!srl_color_cam_args(cam, A.rows, A.cols, &A.C)) { ctx->err = "render: camera pose is not finite"; return SRL_ERR_BAD_ARG; }
     const long long P = cm->num_points;
     const unsigned nblocks = (unsigned)((P + 255) / 256);
     if (!cm->d_rtot) {

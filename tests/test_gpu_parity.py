@@ -1549,7 +1549,12 @@ def _imu_track(rng, S, t0, dt):
     return st
 
 
-UNDISTORT_TOL = 1e-12     # device sin / cos / acos vs glibc: a few ulp of FP64 on O(10 m) coordinates
+# Device sin / cos / acos against glibc's, in this file's max-norm max|a - b| / max|b|.  tests/undistort_checker.py bounds every point by
+# e <= K = 11 units of 2^-52 * s against the exact model (the oracle itself stays within ORACLE_WORST = 2.57), s = |R_il raw + t_il| + |trans|
+# for imu_point and |imu_point| + |t_end| + |t_il| for raw_point.  Here the points lie in a +-30 m cube: s <= 30 sqrt(3) + 5 < 57 m while
+# max|b| > 28.5 m, so s / max|b| < 2 and device and oracle differ by less than 2 * (11 + 2.57) * 2^-52 = 6.1e-15.  (Measured on an MI355X:
+# the two differ in the last bit at 6 of the 12 923 points of tests/test_gpu_undistort_edges.py and agree bit for bit at the others.)
+UNDISTORT_TOL = 6.1e-15
 
 
 @pytest.mark.parametrize("mode", [capi.MC_CONSTANT_VELOCITY, capi.MC_IMU, capi.MC_NONE])
@@ -1674,8 +1679,8 @@ def test_replay_driver_matches_reference_loop(oracle_lib, oracle_backend, mc):
             assert rel(f["raw_point"], fo["raw"]) < 1e-11 and rel(f["imu_point"], fo["imu_point"]) < 1e-11
             assert rel(f["point"], fo["point"]) < 1e-9
             assert rel(lio.eskf_get_cov(), ref.e.get_cov()) < 1e-8
-            # The final maps are compared BIT for bit below although the device's undistortion agrees with the host's only to ~1e-12
-            # (device sin / cos / acos): that holds as long as no inserted point sits closer to a decision boundary of the insertion than
+            # The final maps are compared BIT for bit below although the device's undistortion is guaranteed to agree with the host's only
+            # to a few 1e-15 (device sin / cos / acos, UNDISTORT_TOL above): that holds as long as no inserted point sits closer to a decision boundary of the insertion than
             # the device / host difference -- (a) a voxel seam of the map (key = short(float(p) / 1.0), lioOptimization.cpp:403-405) and
             # (b) a rounding boundary of the FP32 position that is stored (cloudMap.cpp:7).  Asserted here, per frame, not left to luck.
             pd, ph = np.asarray(f["point"], np.float64), np.asarray(fo["point"], np.float64)

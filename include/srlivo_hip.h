@@ -325,6 +325,44 @@ int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, int image_ro
                          const srl_color_select_opts *opts, srl_color_selected *out /* or NULL */, int64_t capacity,
                          srl_color_select_totals *totals /* or NULL */);
 
+/* ------------------------------------------------------------------ colour voxel map: the coloured cloud
+ * replaces: the loops of lioOptimization::pubColorPoints (lioOptimization.cpp:1210-1241), threadPubColorPoints (:1243-1344) and
+ * saveColorPoints (:1386-1426) over rgb_points_vec: a point is left out iff N_rgb < pub_point_minimum_views (:1221, :1281, :1404), every
+ * other one becomes a pcl::PointXYZRGB.  ROS messages, topics, sleeping and the PCD file stay with the caller.
+ * The call covers rgb_points_vec[first .. first + count); count < 0 = to the end of the list as it is at the call.  The range is walked
+ * ascending, or descending when `reverse` is set (saveColorPoints walks down).  Record k is the k-th kept point of the walk:
+ *   x, y, z = the stored FP32 position (getPosition() followed by the float assignment of :1225-1227 is the identity);
+ *   r = (uint8_t) rgb[2], g = (uint8_t) rgb[1], b = (uint8_t) rgb[0] (:1228-1230), each defined here as the low 8 bits of the int16 --
+ *   the reference's double -> uint8_t for 0 ... 255, where updateRgb keeps colours (a truncated weighted mean of bytes); a = 255;
+ *   point_index[k], when requested, is the registered index of record k.
+ * The record is meant as PCL's PointXYZRGB: the fields x y z rgb packed to 16 bytes, the rgb word holding b, g, r, a from the low byte,
+ * a = 255 as PCL's constructor sets it.  PCL is not part of this tree and the stand-in pcl::PointXYZRGB of oracle/ref_shim is not PCL:
+ * nothing here can confirm that layout, so check it against the PCL you link before you reinterpret the records.
+ * `since` additionally leaves out a point iff last_observe_time < since (counted as stale, among the points that pass the N_rgb test);
+ * -inf is the reference's loops, and the time is read only where since > -inf.
+ * A map never rendered has no colour state and none is allocated by this call: every N_rgb is 0 and every colour 0, so that with
+ * minimum_views <= 0 such a map exports every point black.
+ * Synchronous: one wait for the totals, then one DMA of exactly totals->published records, and a second one of as many indices when
+ * point_index is given.  out == NULL and point_index == NULL: the totals alone.  capacity (records, and indices) < published:
+ * SRL_ERR_BAD_ARG with the totals filled and nothing copied.  The call changes nothing: ask again.  A cloud of up to 1 MiB (records
+ * and indices) leaves through page-locked scratch inside the context; a larger one is copied straight into the caller's arrays.
+ * Before a device is touched: NULL ctx or opts, first < 0, first + count beyond the list, capacity < 0, NaN since: SRL_ERR_BAD_ARG; no
+ * colour map: SRL_ERR_NO_MAP; more than one rank: SRL_ERR_UNSUPPORTED; a range of more than 2^27 points (what one scan handles) is
+ * REFUSED with SRL_ERR_UNSUPPORTED, not split: export it in pieces; an empty range: SRL_OK with zero totals.  Cancels an armed launch.
+ * Neither map, nor the colour state, the neighbourhood bounds or the taps are touched; scratch comes from the context's pool. */
+typedef struct srl_color_cloud_point { float x, y, z; uint8_t b, g, r, a; } srl_color_cloud_point;   /* 16 B */
+typedef struct srl_color_cloud_opts {
+    int32_t minimum_views;          /* pub_point_minimum_views: a point is left out iff N_rgb < minimum_views (so <= 0 keeps all) */
+    int32_t reverse;                /* 0: ascending registered index; != 0: descending (saveColorPoints) */
+    double  since;                  /* additionally left out iff last_observe_time < since; -inf = the reference's loops; NaN refused */
+} srl_color_cloud_opts;
+void srl_color_cloud_opts_default(srl_color_cloud_opts *o);   /* 1 (config/r3live.yaml:76; the class default, parameters.h:106, is 3), 0, -inf */
+/* scanned = published + below_views + stale */
+typedef struct srl_color_cloud_totals { int64_t scanned, published, below_views, stale; } srl_color_cloud_totals;
+int srl_color_map_export_cloud(srl_ctx *ctx, int64_t first, int64_t count, const srl_color_cloud_opts *opts,
+                               srl_color_cloud_point *out /* or NULL */, int32_t *point_index /* or NULL */, int64_t capacity,
+                               srl_color_cloud_totals *totals /* or NULL */);
+
 /* ------------------------------------------------------------------ sweep
  * replaces: the `keypoints` vector handed to updateIEKF (optimize.cpp:133; point3D::raw_point,
  * cloudMap.h:40).  AoS n x 3 FP64 in the lidar frame, in keypoint order.  Uploaded once per sweep.

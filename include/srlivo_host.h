@@ -91,6 +91,30 @@ int srl_lio_render_points_in_recent_voxel(srl_lio *lio, const srl_color_camera *
 int srl_lio_select_points_for_projection(srl_lio *lio, const srl_color_camera *camera, int rows, int cols, double minimum_dis, int skip_step,
                                          int use_all_points, int refresh, srl_color_selected *out, int capacity, int *n,
                                          srl_color_select_totals *totals);
+/* The coloured cloud of the publishers (srl_color_map_export_cloud with since = -inf).  which = 0: pubColorPoints
+ * (lioOptimization.cpp:1210-1241) and the cloud threadPubColorPoints cuts into topics (:1243-1344): the whole registered list, ascending.
+ * which = 1: saveColorPoints (:1386-1426), whose loop is `for (i = size - 1; i > 0; i--)` (:1398): descending, and index 0 is never
+ * saved -- the range [1, size) reversed.  *n = the number of records; out and point_index (optional) take them; capacity 0 asks for the
+ * number and the totals alone, a smaller capacity than *n is SRL_ERR_BAD_ARG with both filled.  NULL lio or n, which outside 0 ... 1,
+ * capacity < 0 or capacity > 0 without out: SRL_ERR_BAD_ARG; a host-only handle: SRL_ERR_NO_DEVICE, never a host loop; otherwise the codes
+ * of srl_color_map_export_cloud. */
+int srl_lio_color_cloud(srl_lio *lio, int which, int minimum_views, srl_color_cloud_point *out, int32_t *point_index, int64_t capacity,
+                        int64_t *n, srl_color_cloud_totals *totals);
+/* The same cloud without a copy of the caller's: *points (and *point_index, when with_point_index is set) point into buffers the object
+ * keeps -- *n records, valid until the next srl_lio_color_cloud_view of this handle or its destruction.  The buffers hold the largest
+ * cloud so far and half as much again and are not touched between calls: one device call per cloud, a second one only for a cloud
+ * larger than the buffers.  Errors of the device call arrive as SRL_ERR_HIP with the message of srl_lio_last_error. */
+int srl_lio_color_cloud_view(srl_lio *lio, int which, int minimum_views, int with_point_index, const srl_color_cloud_point **points,
+                             const int32_t **point_index, int64_t *n, srl_color_cloud_totals *totals);
+/* threadPubColorPoints' topic schedule (:1262-1342) as a function of the number of published points, with the two ints the thread carries
+ * from round to round kept by the object: number_of_points_per_topic = 1000 and sleep_time_after_pub = 10 (microseconds) at the start.
+ * One round: published / number_of_points_per_topic full topics, then one remainder topic that is always sent, also when it is empty
+ * (:1319-1336); if the number of topics sent is >= 45 both ints are multiplied by 1.5 and truncated (:1338-1342) for the NEXT round.
+ * sizes[0 .. *n_topics) are the topic sizes in order: the caller slices the one cloud srl_lio_color_cloud(which = 0) gave.  A capacity
+ * below *n_topics leaves the carried state as it was (0: SRL_OK, the number alone; else SRL_ERR_BAD_ARG).  Pure host logic: works on a
+ * host-only handle.  srl_lio_color_topic_state reads the carried ints (each output optional). */
+int srl_lio_color_topic_sizes(srl_lio *lio, int64_t published, int32_t *sizes, int capacity, int *n_topics);
+int srl_lio_color_topic_state(srl_lio *lio, int *number_of_points_per_topic, int *sleep_time_after_pub);
 /* Where lioOptimization::buildFrame sub-samples the cut sweep (subSampleFrame, lioOptimization.cpp:838-846): on = 1 (the default) on the
  * device (srl_frame_subsample + srl_frame_take_subsampled; the host runs the two shuffles on index arrays and downloads m points), 0 = on the
  * host over the n-point downloads of srl_frame_undistort and srl_frame_take.  Both give the same frame bit for bit. */

@@ -105,6 +105,22 @@ class ColorSelectTotals(C.Structure):
 COLOR_SELECTED_DTYPE = np.dtype([("index", "<i4"), ("pool", "<i4"), ("point_index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                                  ("u", "<f4"), ("v", "<f4")])
 
+class ColorCloudOpts(C.Structure):
+    """srl_color_cloud_opts: pub_point_minimum_views, the direction of the walk and the optional observation-time cut"""
+    _fields_ = [("minimum_views", C.c_int32), ("reverse", C.c_int32), ("since", C.c_double)]
+
+
+class ColorCloudTotals(C.Structure):
+    """srl_color_cloud_totals: what one srl_color_map_export_cloud did (scanned = published + below_views + stale)"""
+    _fields_ = [("scanned", C.c_int64), ("published", C.c_int64), ("below_views", C.c_int64), ("stale", C.c_int64)]
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, f)) for f, _ in self._fields_)
+
+
+# srl_color_cloud_point: records.view(COLOR_CLOUD_DTYPE) -- x y z and the rgb word (b, g, r, a from the low byte)
+COLOR_CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])
+
 # srl_color_stored: records.view(COLOR_STORED_DTYPE)
 COLOR_STORED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("kx", "<i2"), ("ky", "<i2"), ("kz", "<i2"), ("slot", "<u2"),
                                ("batch_index", "<i4"), ("point_index", "<i4")])
@@ -192,6 +208,8 @@ def load_library():
         "srl_color_map_select": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, C.POINTER(ColorSelectOpts), p, C.c_int64,
                                   C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_color_map_render": ([p, C.POINTER(ColorCamera), p, C.c_int, C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
+        "srl_color_cloud_opts_default": ([C.POINTER(ColorCloudOpts)], None),
+        "srl_color_map_export_cloud": ([p, C.c_int64, C.c_int64, C.POINTER(ColorCloudOpts), p, p, C.c_int64, C.POINTER(ColorCloudTotals)], C.c_int),
         "srl_color_map_download_rgb": ([p, p, p, p, p, p, C.c_int64], C.c_int),
         "srl_color_registered_rgb": ([p, C.c_int64, C.c_int, p, p, p, p, p], C.c_int),
         "srl_sweep_upload": ([p, p, C.c_int], C.c_int),
@@ -288,6 +306,11 @@ def load_library():
         "srl_lio_set_color_map_options": ([p, C.POINTER(ColorOpts)], C.c_int),
         "srl_lio_set_color_times": ([p, C.c_double, C.c_double, C.c_int], C.c_int),
         "srl_lio_add_points_to_map_at": ([p, p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int], C.c_int),
+        "srl_lio_color_cloud": ([p, C.c_int, C.c_int, p, p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(ColorCloudTotals)], C.c_int),
+        "srl_lio_color_cloud_view": ([p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                      C.POINTER(ColorCloudTotals)], C.c_int),
+        "srl_lio_color_topic_sizes": ([p, C.c_int64, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_lio_color_topic_state": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "srl_lio_select_points_for_projection": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, p, C.c_int,
                                                   C.POINTER(C.c_int), C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_lio_color_visited": ([p, C.c_int, p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
@@ -382,6 +405,14 @@ def default_color_opts(**kw):
 def default_color_select_opts(**kw):
     o = ColorSelectOpts()
     load_library().srl_color_select_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_color_cloud_opts(**kw):
+    o = ColorCloudOpts()
+    load_library().srl_color_cloud_opts_default(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -658,6 +689,20 @@ class Context:
             self._chk(self.lib.srl_color_map_select(self.h, C.byref(camera), int(rows), int(cols), lp, len(v), C.byref(o), _ptr(out), len(out),
                                                     C.byref(tot)), "srl_color_map_select")
         return out, tot
+
+    def color_map_export_cloud(self, first=0, count=-1, opts=None, with_index=True, totals_only=False):
+        """srl_color_map_export_cloud over rgb_points_vec[first : first + count] (count < 0: to the end); opts = ColorCloudOpts (None =
+        1 view, ascending, no time cut).  Returns (records (COLOR_CLOUD_DTYPE), point_index or None, ColorCloudTotals): the totals are
+        asked for first, then the records at their exact number (the call changes nothing)."""
+        o = default_color_cloud_opts() if opts is None else opts
+        tot = ColorCloudTotals()
+        self._chk(self.lib.srl_color_map_export_cloud(self.h, int(first), int(count), C.byref(o), None, None, 0, C.byref(tot)), "srl_color_map_export_cloud")
+        out = np.zeros(tot.published, dtype=COLOR_CLOUD_DTYPE)
+        idx = np.zeros(tot.published, dtype=np.int32) if with_index else None
+        if tot.published and not totals_only:
+            self._chk(self.lib.srl_color_map_export_cloud(self.h, int(first), int(count), C.byref(o), _ptr(out), _ptr(idx), len(out), C.byref(tot)),
+                      "srl_color_map_export_cloud")
+        return out, idx, tot
 
     @staticmethod
     def _color_state_arrays(n):
@@ -1219,6 +1264,53 @@ class Lio:
 
     def refresh_points_for_projection(self, camera, rows, cols):
         return self.select_points_for_projection(camera, rows, cols, refresh=True)
+
+    def color_cloud(self, which=0, minimum_views=1, with_index=True):
+        """the publishers' coloured cloud (srl_lio_color_cloud): which = 0 pubColorPoints / threadPubColorPoints (the whole registered
+        list, ascending), 1 saveColorPoints (descending, index 0 never saved).  Returns (records (COLOR_CLOUD_DTYPE), point_index or
+        None, ColorCloudTotals)."""
+        m, tot = C.c_int64(), ColorCloudTotals()
+        # one call into a buffer sized by what earlier calls published; only a call that publishes more than that is asked again
+        cap = max(getattr(self, "_cloud_capacity", 0), 4096)
+        out = np.zeros(cap, dtype=COLOR_CLOUD_DTYPE)
+        idx = np.zeros(cap, dtype=np.int32) if with_index else None
+        rc = self.lib.srl_lio_color_cloud(self.h, int(which), int(minimum_views), _ptr(out), _ptr(idx), cap, C.byref(m), C.byref(tot))
+        if rc == SRL_ERR_BAD_ARG and m.value > cap:
+            cap = m.value
+            out = np.zeros(cap, dtype=COLOR_CLOUD_DTYPE)
+            idx = np.zeros(cap, dtype=np.int32) if with_index else None
+            rc = self.lib.srl_lio_color_cloud(self.h, int(which), int(minimum_views), _ptr(out), _ptr(idx), cap, C.byref(m), C.byref(tot))
+        self._chk(rc, "srl_lio_color_cloud")
+        self._cloud_capacity = max(getattr(self, "_cloud_capacity", 0), m.value + m.value // 2)
+        return out[:m.value].copy(), (idx[:m.value].copy() if with_index else None), tot
+
+    def color_cloud_view(self, which=0, minimum_views=1, with_index=True):
+        """the same through the object's own buffers (srl_lio_color_cloud_view: the mirror's pubColorPoints / saveColorPoints); the arrays
+        returned here are copies of the view"""
+        pts, idx, m, tot = C.c_void_p(), C.c_void_p(), C.c_int64(), ColorCloudTotals()
+        self._chk(self.lib.srl_lio_color_cloud_view(self.h, int(which), int(minimum_views), 1 if with_index else 0, C.byref(pts), C.byref(idx),
+                                                    C.byref(m), C.byref(tot)), "srl_lio_color_cloud_view")
+        n = m.value
+        rec = np.frombuffer((C.c_char * (n * 16)).from_address(pts.value), dtype=COLOR_CLOUD_DTYPE).copy() if n else np.zeros(0, COLOR_CLOUD_DTYPE)
+        index = None
+        if with_index:
+            index = np.frombuffer((C.c_char * (n * 4)).from_address(idx.value), dtype=np.int32).copy() if n else np.zeros(0, np.int32)
+        return rec, index, tot
+
+    def color_topic_sizes(self, published):
+        """one round of threadPubColorPoints' topic schedule for `published` points (srl_lio_color_topic_sizes): the topic sizes in order;
+        the object carries number_of_points_per_topic and sleep_time_after_pub to the next round"""
+        m = C.c_int()
+        self._chk(self.lib.srl_lio_color_topic_sizes(self.h, int(published), None, 0, C.byref(m)), "srl_lio_color_topic_sizes")
+        sizes = np.zeros(m.value, dtype=np.int32)
+        self._chk(self.lib.srl_lio_color_topic_sizes(self.h, int(published), _ptr(sizes), len(sizes), C.byref(m)), "srl_lio_color_topic_sizes")
+        return sizes
+
+    def color_topic_state(self):
+        """(number_of_points_per_topic, sleep_time_after_pub) as the next round will use them"""
+        a, b = C.c_int(), C.c_int()
+        self._chk(self.lib.srl_lio_color_topic_state(self.h, C.byref(a), C.byref(b)), "srl_lio_color_topic_state")
+        return a.value, b.value
 
     def set_device_subsample(self, on):
         """buildFrame's sub-sample on the device (True, the default) or on the host (srl_lio_set_device_subsample)"""

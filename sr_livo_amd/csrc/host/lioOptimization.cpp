@@ -569,6 +569,65 @@ void lioOptimization::refreshPointsForProjection(const srl_color_camera &camera,
     points_for_projection = selectPointsForProjection(camera, rows, cols, 10.0, 1);      // :36
 }
 
+int lioOptimization::colorCloud(int which, int minimum_views, srl_color_cloud_point *out, int32_t *point_index, int64_t capacity) {
+    srl_ctx *ctx = voxel_map.ctx;
+    cloud_totals = {0, 0, 0, 0};
+    if (!ctx) throw std::runtime_error("colorCloud: no HIP context (the product has no CPU path)");
+    srl_color_cloud_opts o;
+    srl_color_cloud_opts_default(&o);
+    o.minimum_views = minimum_views;
+    int64_t first = 0, count = -1;                                       // pubColorPoints: for (i = 0; i < size; i++) (:1217, :1275)
+    if (which == 1) {
+        // saveColorPoints: for (long i = point_size - 1; i > 0; i--) (:1398): index 0 is never reached
+        int64_t size = 0;
+        const int rc = srl_color_map_size(ctx, nullptr, nullptr, &size, nullptr);
+        if (rc != SRL_OK) return rc;
+        o.reverse = 1;
+        first = size > 0 ? 1 : 0;
+    }
+    return srl_color_map_export_cloud(ctx, first, count, &o, out, point_index, capacity, &cloud_totals);
+}
+
+namespace {
+lioOptimization::colorCloudView color_cloud_into(lioOptimization &lio, int which, int minimum_views, bool with_index, const char *what) {
+    // ONE call into the object's buffers; only a call that publishes more than they hold is asked again (it changes nothing, and its
+    // totals name the number)
+    std::vector<srl_color_cloud_point> &out = lio.color_cloud;
+    std::vector<int32_t> &idx = lio.color_cloud_index;
+    if (out.size() < 4096) out.resize(4096);
+    if (with_index && idx.size() < out.size()) idx.resize(out.size());
+    int rc = lio.colorCloud(which, minimum_views, out.data(), with_index ? idx.data() : nullptr, (int64_t)out.size());
+    if (rc == SRL_ERR_BAD_ARG && lio.cloud_totals.published > (int64_t)out.size()) {
+        const size_t need = (size_t)lio.cloud_totals.published;
+        out.clear(); out.resize(need + need / 2);                        // (cleared first: nothing of the old buffer is worth copying)
+        if (with_index) { idx.clear(); idx.resize(out.size()); }
+        rc = lio.colorCloud(which, minimum_views, out.data(), with_index ? idx.data() : nullptr, (int64_t)out.size());
+    }
+    check(lio.context(), rc, what);
+    return {out.data(), with_index ? idx.data() : nullptr, (size_t)lio.cloud_totals.published};
+}
+}  // namespace
+
+lioOptimization::colorCloudView lioOptimization::pubColorPoints(int minimum_views, bool with_point_index) {
+    return color_cloud_into(*this, 0, minimum_views, with_point_index, "pubColorPoints");
+}
+
+lioOptimization::colorCloudView lioOptimization::saveColorPoints(int minimum_views, bool with_point_index) {
+    return color_cloud_into(*this, 1, minimum_views, with_point_index, "saveColorPoints");
+}
+
+std::vector<int32_t> lioOptimization::colorTopicSizes(int64_t published) {
+    if (published < 0) throw std::runtime_error("colorTopicSizes: a negative number of points");
+    const int n = number_of_points_per_topic;
+    std::vector<int32_t> sizes((size_t)(published / n), (int32_t)n);     // pub_index_size == number_of_points_per_topic (:1297)
+    sizes.push_back((int32_t)(published % n));                           // points_rgb_vec.resize(pub_index_size), always published (:1319-1336)
+    if (sizes.size() >= 45) {                                            // cur_topic_index >= 45 (:1338)
+        number_of_points_per_topic = (int)(number_of_points_per_topic * 1.5);
+        sleep_time_after_pub = (int)(sleep_time_after_pub * 1.5);
+    }
+    return sizes;
+}
+
 void lioOptimization::removePointsFarFromLocation(voxelHashMap &map, const srl::Vec3 &location, double distance) {
     if (!map.ctx) throw std::runtime_error("removePointsFarFromLocation: no HIP context (the product has no CPU path)");
     check(map.ctx, srl_map_remove_far(map.ctx, location.a, distance, nullptr, nullptr), "srl_map_remove_far");

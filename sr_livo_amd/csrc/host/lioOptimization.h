@@ -230,6 +230,29 @@ public:
     std::vector<srl_color_selected> points_for_projection;
     srl_color_select_totals select_totals = {0, 0, 0, 0, 0, 0, 0, 0};
     size_t select_capacity = 0;                                          // records the one call per frame has room for: 1.5 x the most selected so far
+    // The publishers' coloured cloud on the device colour map (srl_color_map_export_cloud): a point is left out iff N_rgb < minimum_views
+    // (map_options.pub_point_minimum_views).  pubColorPoints (lioOptimization.cpp:1210-1241; the same cloud threadPubColorPoints cuts into
+    // topics, :1243-1344): the whole registered list, ascending.  saveColorPoints (:1386-1426): its loop is `for (i = size - 1; i > 0; i--)`
+    // (:1398) -- descending, index 0 never saved: the range [1, size) reversed.  point_index (optional) receives the registered index of
+    // every record.  ROS messages, topics, sleeping and the PCD file stay with the caller.  cloud_totals: the last call's.  Both return a
+    // view of the object's own buffers, valid until the next of these calls.  The buffers keep the size of the largest cloud so far and
+    // half as much again (one device call per cloud; only a call that publishes more than that is asked a second time) and are not
+    // touched between calls, so that a publisher that runs every frame pays for the records it receives and for nothing else.
+    struct colorCloudView { const srl_color_cloud_point *points; const int32_t *point_index /* or nullptr */; size_t size; };
+    colorCloudView pubColorPoints(int minimum_views, bool with_point_index = false);
+    colorCloudView saveColorPoints(int minimum_views, bool with_point_index = false);
+    std::vector<srl_color_cloud_point> color_cloud;                      // the buffers: records [0, cloud_totals.published) are the last cloud
+    std::vector<int32_t> color_cloud_index;
+    // the call beneath both, into the caller's arrays (which = 0 pub, 1 save); returns the status of srl_color_map_export_cloud
+    int colorCloud(int which, int minimum_views, srl_color_cloud_point *out, int32_t *point_index, int64_t capacity);
+    srl_color_cloud_totals cloud_totals = {0, 0, 0, 0};
+    // threadPubColorPoints' topic schedule (:1262-1342) as a pure function with the state the thread carries from round to round: for P
+    // published points P / number_of_points_per_topic full topics, then one remainder topic that is always sent, also when it is empty;
+    // if the topics sent in the round are >= 45 both ints are multiplied by 1.5 and truncated (:1338-1342).  Returns the topic sizes.
+    int number_of_points_per_topic = 1000;                               // :1247
+    int sleep_time_after_pub = 10;                                       // :1246
+    int64_t colorTopicCount(int64_t published) const { return published / number_of_points_per_topic + 1; }
+    std::vector<int32_t> colorTopicSizes(int64_t published);
     bool collectPointsWorld() const { return collect_points_world; }
 
     // ---- ours ----

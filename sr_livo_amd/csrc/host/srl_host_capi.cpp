@@ -327,6 +327,57 @@ int srl_lio_select_points_for_projection(srl_lio *h, const srl_color_camera *cam
     return SRL_OK;
 }
 
+int srl_lio_color_cloud(srl_lio *h, int which, int minimum_views, srl_color_cloud_point *out, int32_t *point_index, int64_t capacity, int64_t *n,
+                        srl_color_cloud_totals *totals) {
+    if (n) *n = 0;
+    if (totals) std::memset(totals, 0, sizeof *totals);
+    if (!h || !n || which < 0 || which > 1 || capacity < 0 || (capacity > 0 && !out)) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }      // never a host loop
+    int rc;
+    try { rc = h->lio->colorCloud(which, minimum_views, capacity > 0 ? out : nullptr, capacity > 0 ? point_index : nullptr, capacity); }
+    catch (const std::exception &e) { return status_from_exception(h, e); }
+    *n = h->lio->cloud_totals.published;
+    if (totals) *totals = h->lio->cloud_totals;
+    if (rc != SRL_OK) h->err = srl_last_error(h->lio->context());
+    return rc;
+}
+
+int srl_lio_color_cloud_view(srl_lio *h, int which, int minimum_views, int with_point_index, const srl_color_cloud_point **points,
+                             const int32_t **point_index, int64_t *n, srl_color_cloud_totals *totals) {
+    if (n) *n = 0;
+    if (points) *points = nullptr;
+    if (point_index) *point_index = nullptr;
+    if (totals) std::memset(totals, 0, sizeof *totals);
+    if (!h || !n || !points || which < 0 || which > 1 || (with_point_index && !point_index)) return SRL_ERR_BAD_ARG;
+    if (!h->lio->context()) { h->err = "host-only handle: no device, no colour map"; return SRL_ERR_NO_DEVICE; }
+    try {
+        const lioOptimization::colorCloudView v = which == 0 ? h->lio->pubColorPoints(minimum_views, with_point_index != 0)
+                                                             : h->lio->saveColorPoints(minimum_views, with_point_index != 0);
+        *points = v.points; *n = (int64_t)v.size;
+        if (point_index) *point_index = v.point_index;
+    } catch (const std::exception &e) { return status_from_exception(h, e); }
+    if (totals) *totals = h->lio->cloud_totals;
+    return SRL_OK;
+}
+
+int srl_lio_color_topic_sizes(srl_lio *h, int64_t published, int32_t *sizes, int capacity, int *n_topics) {
+    if (n_topics) *n_topics = 0;
+    if (!h || !n_topics || published < 0 || capacity < 0 || (capacity > 0 && !sizes)) return SRL_ERR_BAD_ARG;
+    const int64_t topics = h->lio->colorTopicCount(published);
+    if (topics > 0x7FFFFFFF) return SRL_ERR_BAD_ARG;
+    *n_topics = (int)topics;
+    if (topics > capacity) return capacity == 0 ? SRL_OK : SRL_ERR_BAD_ARG;      // the carried state stays as it was
+    const std::vector<int32_t> s = h->lio->colorTopicSizes(published);
+    std::memcpy(sizes, s.data(), s.size() * sizeof(int32_t));
+    return SRL_OK;
+}
+int srl_lio_color_topic_state(srl_lio *h, int *number_of_points_per_topic, int *sleep_time_after_pub) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    if (number_of_points_per_topic) *number_of_points_per_topic = h->lio->number_of_points_per_topic;
+    if (sleep_time_after_pub) *sleep_time_after_pub = h->lio->sleep_time_after_pub;
+    return SRL_OK;
+}
+
 int srl_lio_set_device_subsample(srl_lio *h, int on) {
     if (!h) return SRL_ERR_BAD_ARG;
     h->lio->device_subsample = on != 0;

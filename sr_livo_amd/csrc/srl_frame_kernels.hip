@@ -2,16 +2,19 @@
 // from keypoint selection to map insertion.
 //   srl_frame_upload            p_frame->point_frame raw points -> HBM (once per sweep)
 //   srl_frame_select_keypoints  gridSampling / subSampleFrame (src/utility.cpp:167-201): the device transforms the
-//                               frame with the prior pose, keys every point at the sampling voxel size, sorts
-//                               (key, index) stably and run-length encodes -> first point of every voxel; the
-//                               host only replays the ORDER: the reference emits keypoints in
-//                               std::tr1::unordered_map iteration order, which depends on the sequence of distinct
-//                               keys alone, so the distinct keys are inserted (first-occurrence order) into the same
-//                               container type and read back.  The selected raw points are gathered on the device
+//                               frame with the prior pose and keys every point at the sampling voxel size (k_select_group);
+//                               the grid-sampling chain below keeps the first point of every voxel and emits the voxels in
+//                               std::tr1::unordered_map iteration order.  The selected raw points are gathered on the device
 //                               straight into the resident sweep (no keypoint upload).
-//   srl_frame_subsample         buildFrame's subSampleFrame (lioOptimization.cpp:838-846) on the undistorted sweep: the same grouping and
-//   srl_frame_take_subsampled   order chain in the first shuffle's visit order, keyed on the uncorrected points; then the second shuffle
-//                               as a gather into the resident frame
+//   srl_frame_subsample         buildFrame's subSampleFrame (lioOptimization.cpp:838-846) on the undistorted sweep: the same chain
+//   srl_frame_take_subsampled   behind k_sub_group (the first shuffle's visit order, keyed on the uncorrected points); then the
+//                               second shuffle as a gather into the resident frame
+//   the grid-sampling chain     (GridChain: one host sequence for both) group kernel: voxel -> slot of an epoch-tagged scratch table,
+//                               atomicMin of the element index (no sort) -> k_select_mark -> scan over the marks (first-occurrence
+//                               rank; {std::hash<voxel>, first element} by rank) -> the container's iteration order on the device:
+//                               k_tr1_bucket, scan over the bucket counts, k_tr1_rank.  The host waits for one tagged word
+//                               {tag, overflow, bad order, count}; it replays the order itself (host/tr1_order.h) for frames
+//                               beyond SRL_SCAN_MAX points, an overfull bucket, or on request (frame_order_mode).
 //   srl_frame_commit            the re-transform loop of optimize() (optimize.cpp:441-445) + addPointsToMap
 //                               (lioOptimization.cpp:520-554) chained on the device.
 #include "srl_ctx.h"
@@ -26,7 +29,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <tr1/unordered_map>
 #include <vector>
 
 int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, int n, double voxel_size,
@@ -38,69 +40,39 @@ namespace {
 
 using Xf = SrlXf;
 
-// point = R(q) * (R_il * raw + t_il) + t (utility.cpp:314-318), key = short(point / size) (utility.cpp:171-173)
-__global__ void k_frame_keys(const double *raw, int n, const Xf X, double size, double *world, unsigned long long *keys, unsigned *idx) {
+// the re-transform of optimize() (optimize.cpp:441-445) as a kernel of its own: point = transformPoint(raw)
+__global__ void k_frame_world(const double *raw, int n, const Xf X, double *world) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double rx = raw[(size_t)i * 3], ry = raw[(size_t)i * 3 + 1], rz = raw[(size_t)i * 3 + 2];
-    const double ix = (X.R_il[0] * rx + X.R_il[1] * ry) + X.R_il[2] * rz + X.t_il[0];
-    const double iy = (X.R_il[3] * rx + X.R_il[4] * ry) + X.R_il[5] * rz + X.t_il[1];
-    const double iz = (X.R_il[6] * rx + X.R_il[7] * ry) + X.R_il[8] * rz + X.t_il[2];
-    const double wx = (X.R[0] * ix + X.R[1] * iy) + X.R[2] * iz + X.t[0];
-    const double wy = (X.R[3] * ix + X.R[4] * iy) + X.R[5] * iz + X.t[1];
-    const double wz = (X.R[6] * ix + X.R[7] * iy) + X.R[8] * iz + X.t[2];
-    if (world) { world[(size_t)i * 3] = wx; world[(size_t)i * 3 + 1] = wy; world[(size_t)i * 3 + 2] = wz; }
-    if (keys) {
-        keys[i] = srl_pack_key((short)(int)(wx / size), (short)(int)(wy / size), (short)(int)(wz / size));
-        idx[i] = (unsigned)i;
-    }
+    double wx, wy, wz;
+    srl_transform_point(X, raw[(size_t)i * 3], raw[(size_t)i * 3 + 1], raw[(size_t)i * 3 + 2], wx, wy, wz);
+    world[(size_t)i * 3] = wx; world[(size_t)i * 3 + 1] = wy; world[(size_t)i * 3 + 2] = wz;
 }
 
-__global__ void k_first_index(const int *seg_start, const unsigned *sorted_idx, int S, unsigned *first_idx) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < S) first_idx[s] = sorted_idx[seg_start[s]];
-}
-
-// run heads of the (key, index)-sorted frame: one {voxel key, index of its first point} pair per occupied voxel, in no
-// particular order (the host re-orders by first index anyway); out[0] of `count` = number of pairs
-__global__ void k_run_heads(const unsigned long long *keys_sorted, const unsigned *idx_sorted, int n, unsigned long long *out_key,
-                            unsigned *out_first, int *count) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool head = i < n && (i == 0 || keys_sorted[i] != keys_sorted[i - 1]);
-    // wave-aggregated append: one atomic per wave
-    const unsigned long long m = __ballot(head);
-    if (m == 0ull) return;
-    const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0));
-    const int leader = (int)__builtin_ctzll(m);
-    int base = 0;
-    if (lane == leader) base = atomicAdd(count, (int)__popcll(m));
-    base = __shfl(base, leader);
-    if (head) {
-        const int p = base + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        out_key[p] = keys_sorted[i];
-        out_first[p] = idx_sorted[i];
-    }
+// what a group kernel of the grid-sampling chain is given: the scratch table's words and epoch, and the marks it clears
+struct GroupArgs {
+    unsigned long long *keyw, *minw;
+    unsigned mask, epoch16, counter32;
+    int *flag;
+};
+// element e lies in the voxel `key` (short(p / size) per axis, utility.cpp:171-173): claim the voxel's slot and keep its smallest element --
+// {~frame counter, e}, only ever lowered: a word of an earlier chain loses against any of this one
+__device__ __forceinline__ void group_min(const GroupArgs &G, double x, double y, double z, double size, unsigned e) {
+    const unsigned long long key = srl_pack_key((short)(int)(x / size), (short)(int)(y / size), (short)(int)(z / size));
+    const unsigned h = srl_epoch_claim(G.keyw, G.mask, G.epoch16, key, srl_hash_key(key));
+    atomicMin(&G.minw[h], ((unsigned long long)(0xFFFFFFFFu - G.counter32) << 32) | e);
 }
 
 // gridSampling keeps the FIRST point of every sampling voxel (utility.cpp:175-183): group the points by voxel key in a scratch hash
 // table (open addressing, keys claimed by compare-and-swap) and keep the smallest point index per key (atomicMin) -- no sort: the
-// order of the voxels is decided on the host anyway (std::tr1::unordered_map iteration order), from the first indices.
-__global__ void k_select_group(const double *raw, int n, const Xf X, double size, unsigned long long *keyw, unsigned long long *minw, unsigned mask,
-                               unsigned epoch16, unsigned counter32, int *flag) {
+// order of the voxels is decided behind this kernel (std::tr1::unordered_map iteration order), from the first indices.
+__global__ void k_select_group(const double *raw, int n, const Xf X, double size, const GroupArgs G) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    flag[i] = 0;                           // (k_select_mark, the next kernel, sets the marks: no fill in front of this one)
-    const double rx = raw[(size_t)i * 3], ry = raw[(size_t)i * 3 + 1], rz = raw[(size_t)i * 3 + 2];
-    const double ix = (X.R_il[0] * rx + X.R_il[1] * ry) + X.R_il[2] * rz + X.t_il[0];
-    const double iy = (X.R_il[3] * rx + X.R_il[4] * ry) + X.R_il[5] * rz + X.t_il[1];
-    const double iz = (X.R_il[6] * rx + X.R_il[7] * ry) + X.R_il[8] * rz + X.t_il[2];
-    const double wx = (X.R[0] * ix + X.R[1] * iy) + X.R[2] * iz + X.t[0];
-    const double wy = (X.R[3] * ix + X.R[4] * iy) + X.R[5] * iz + X.t[1];
-    const double wz = (X.R[6] * ix + X.R[7] * iy) + X.R[8] * iz + X.t[2];
-    const unsigned long long key = srl_pack_key((short)(int)(wx / size), (short)(int)(wy / size), (short)(int)(wz / size));
-    const unsigned h = srl_epoch_claim(keyw, mask, epoch16, key, srl_hash_key(key));
-    // smallest point index of the voxel: {~frame counter, index}, only ever lowered -- a word of an earlier frame loses against any of this one
-    atomicMin(&minw[h], ((unsigned long long)(0xFFFFFFFFu - counter32) << 32) | (unsigned)i);
+    G.flag[i] = 0;                         // (k_select_mark, the next kernel, sets the marks: no fill in front of this one)
+    double wx, wy, wz;
+    srl_transform_point(X, raw[(size_t)i * 3], raw[(size_t)i * 3 + 1], raw[(size_t)i * 3 + 2], wx, wy, wz);
+    group_min(G, wx, wy, wz, size, (unsigned)i);
 }
 // ... then the voxels in FIRST-OCCURRENCE order (the order subSampleFrame's loop creates them in, utility.cpp:175-183 -- what the
 // host's replay of the container's iteration order starts from): every occupied slot marks the index of its first point, an
@@ -116,26 +88,32 @@ __global__ void k_select_mark(const unsigned long long *keyw, const unsigned lon
     flag[f] = 1;
     key_at[f] = k & SRL_KEY48_MASK;
 }
-// The voxels leave the device HERE: {std::hash<voxel> (cloudMap.h:173-184, what the host's replay of the container needs), index of the
-// first point} by rank, stored straight into page-locked host memory; the last block to finish publishes {tag, count} in one 8-byte
-// word the host waits on.  No copy command, no stream synchronisation (a D2H copy + hipStreamSynchronize cost ~25 us per frame).
-
-// ... the same hand-over as the per-element work (EmitSink) and the "tile done" step (EmitFin) of the one-launch scan over the marks
-// (frames up to SRL_SCAN_SMALL_MAX points): no rank array, no launch of its own
-struct EmitSink {
+// std::hash<voxel> (cloudMap.h:173-184) of a packed voxel key, in the reference's size_t arithmetic: what the container's order depends on
+__device__ __forceinline__ unsigned long long tr1_voxel_hash(unsigned long long key) {
+    short x, y, z;
+    srl_unpack_key(key, &x, &y, &z);
+    return (unsigned long long)(long long)x * 73856093ull + (unsigned long long)(long long)y * 19349669ull + (unsigned long long)(long long)z * 83492791ull;
+}
+// per-element work of the scan over the marks: {std::hash<voxel>, the element the voxel carries} by first-occurrence rank.  The element is
+// the index of the voxel's first point, or order[that index] (the sub-sample: the sweep index of the first VISITED point).
+// Device ordering: both arrays stay on the device and CountFin leaves the count in sync[1].
+// Host replay: the voxels leave the device HERE, stored straight into page-locked host memory, and EmitFin -- the "tile done" step of the same
+// scan -- has the last block to finish publish {tag, bad order, count} in one 8-byte word the host waits on.  No rank array, no launch of its
+// own, no copy command, no stream synchronisation (a D2H copy + hipStreamSynchronize cost ~25 us per frame).
+struct RankSink {
     const unsigned long long *key_at;
-    unsigned long long *host_hash;
-    unsigned *host_first;
+    unsigned long long *hash;
+    unsigned *first;
+    const int *order;                         // may be null
     __device__ void operator()(int i, int is_first, int r) const {
         if (!is_first) return;
-        short x, y, z;
-        srl_unpack_key(key_at[i], &x, &y, &z);
-        const unsigned long long kP1 = 73856093ull, kP2 = 19349669ull, kP3 = 83492791ull;
-        host_hash[r] = (unsigned long long)(long long)x * kP1 + (unsigned long long)(long long)y * kP2 + (unsigned long long)(long long)z * kP3;
-        host_first[r] = (unsigned)i;
+        hash[r] = tr1_voxel_hash(key_at[i]);
+        first[r] = order ? (unsigned)order[i] : (unsigned)i;
     }
 };
-// bit 30 of a published count word: srl_frame_subsample's visit order was not a permutation (sync[4], set by k_sub_group; 0 for a selection)
+// the published count word: {tag (high half), overflow (an overfull bucket, k_tr1_bucket), bad order, count}.  Bad order: srl_frame_subsample's
+// visit order was not a permutation (sync[4], set by k_sub_group; never by a selection)
+#define SRL_CTRL_OVERFLOW (1u << 31)
 #define SRL_CTRL_BAD_ORDER (1u << 30)
 #define SRL_CTRL_COUNT_MASK 0x3FFFFFFFu
 struct EmitFin {
@@ -169,20 +147,6 @@ struct EmitFin {
 // handful of voxels sharing its bucket (k_tr1_rank, which also gathers the keypoint's raw point into the resident sweep).  One thread
 // per VOXEL, not per bucket: a lane that ranked all pairs of a 6-voxel bucket held the kernel for 40 us.  A bucket with more than
 // SRL_TR1_BUCKET_SLOTS voxels (adversarial keys) sends the frame to the host replay.
-// the ranks stay on the device: {std::hash<voxel>, first point} by first-occurrence rank; the count goes to sync[1]
-struct RankSink {
-    const unsigned long long *key_at;
-    unsigned long long *hash;
-    unsigned *first;
-    __device__ void operator()(int i, int is_first, int r) const {
-        if (!is_first) return;
-        short x, y, z;
-        srl_unpack_key(key_at[i], &x, &y, &z);
-        const unsigned long long kP1 = 73856093ull, kP2 = 19349669ull, kP3 = 83492791ull;       // size_t arithmetic of the reference's hash (cloudMap.h:173-184)
-        hash[r] = (unsigned long long)(long long)x * kP1 + (unsigned long long)(long long)y * kP2 + (unsigned long long)(long long)z * kP3;
-        first[r] = (unsigned)i;
-    }
-};
 struct CountFin {
     unsigned *sync;
     __device__ void operator()(int tile_end) const {
@@ -230,7 +194,7 @@ __global__ void k_tr1_bucket(const SrlTr1Sched *S, unsigned *sync, const unsigne
     __hip_atomic_store(sync + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned bad = __hip_atomic_load(sync + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (bad) __hip_atomic_store(sync + 4, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(host_ctrl, ((unsigned long long)tag << 32) | ((unsigned long long)(over ? 1u : 0u) << 31) | (bad ? SRL_CTRL_BAD_ORDER : 0u) | total,
+    __hip_atomic_store(host_ctrl, ((unsigned long long)tag << 32) | (over ? SRL_CTRL_OVERFLOW : 0u) | (bad ? SRL_CTRL_BAD_ORDER : 0u) | total,
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // T_G(o, me) from the two records; falls back to the general relation below level G - 1 (two voxels sharing their bucket at two levels)
@@ -302,17 +266,6 @@ __global__ void k_gather_soa(const double *raw, const int *sel, int m, double *x
     y[k] = raw[(size_t)i * 3 + 1];
     z[k] = raw[(size_t)i * 3 + 2];
 }
-
-struct vkey {
-    short x, y, z;
-    bool operator==(const vkey &o) const { return x == o.x && y == o.y && z == o.z; }
-};
-struct vkey_hash {     // std::hash<voxel> (cloudMap.h:173-184)
-    std::size_t operator()(const vkey &v) const {
-        const size_t kP1 = 73856093, kP2 = 19349669, kP3 = 83492791;
-        return v.x * kP1 + v.y * kP2 + v.z * kP3;
-    }
-};
 
 void fill_xf(Xf &X, const double q[4], const double t[3], const double R_il[9], const double t_il[3]) {
     const srl::Mat3 R = srl::Quat(q[0], q[1], q[2], q[3]).toRotationMatrix();     // q as is (utility.cpp:317)
@@ -475,38 +428,18 @@ __global__ void k_gather_aos(const double *src, const int *sel, int m, double *d
 // ---------------------------------------------------------------------------- buildFrame's sub-sample (lioOptimization.cpp:838-846)
 // subSampleFrame (utility.cpp:167-186) over the sweep in the order of the first shuffle: keyed on point3D::point -- the UNCORRECTED sensor-frame
 // point (cloudProcessing.cpp:143), d_corr_in -- at the sample size, no pose.  Thread j visits point order[j]; the voxel keeps the point of the
-// smallest visit rank j ({~frame counter, j} in the same scratch words keypoint selection lowers), and the chain behind it is the selection's:
-// k_select_mark, the scan over the marks (first-VISIT order), k_tr1_bucket, the scan over the bucket counts, k_tr1_rank.
+// smallest visit rank j ({~frame counter, j} in the same scratch words keypoint selection lowers); the voxel then carries order[min j] (RankSink).
 // The same pass checks that order is a permutation of 0..n-1: an index out of range is not visited, an index seen twice (its tag word already
 // holds this call's tag) is still grouped; either sets sync[4], which the publisher of the count word folds into SRL_CTRL_BAD_ORDER.
-__global__ void k_sub_group(const int *order, int n, const double *pts, double size, unsigned long long *keyw, unsigned long long *minw, unsigned mask,
-                            unsigned epoch16, unsigned counter32, int *flag, unsigned *seen, unsigned seen_tag, unsigned *bad) {
+__global__ void k_sub_group(const int *order, int n, const double *pts, double size, const GroupArgs G, unsigned *seen, unsigned seen_tag, unsigned *bad) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    flag[j] = 0;
+    G.flag[j] = 0;
     const int i = order[j];
     if ((unsigned)i >= (unsigned)n) { __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
     if (atomicExch(&seen[i], seen_tag) == seen_tag) __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double x = pts[(size_t)i * 3], y = pts[(size_t)i * 3 + 1], z = pts[(size_t)i * 3 + 2];
-    const unsigned long long key = srl_pack_key((short)(int)(x / size), (short)(int)(y / size), (short)(int)(z / size));
-    const unsigned h = srl_epoch_claim(keyw, mask, epoch16, key, srl_hash_key(key));
-    atomicMin(&minw[h], ((unsigned long long)(0xFFFFFFFFu - counter32) << 32) | (unsigned)j);
+    group_min(G, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2], size, (unsigned)j);
 }
-// RankSink of the sub-sample: the element a voxel carries is the sweep index of its first visited point, order[j]
-struct SubRankSink {
-    const unsigned long long *key_at;
-    unsigned long long *hash;
-    unsigned *first;
-    const int *order;
-    __device__ void operator()(int j, int is_first, int r) const {
-        if (!is_first) return;
-        short x, y, z;
-        srl_unpack_key(key_at[j], &x, &y, &z);
-        const unsigned long long kP1 = 73856093ull, kP2 = 19349669ull, kP3 = 83492791ull;
-        hash[r] = (unsigned long long)(long long)x * kP1 + (unsigned long long)(long long)y * kP2 + (unsigned long long)(long long)z * kP3;
-        first[r] = (unsigned)order[j];
-    }
-};
 // the second shuffle and the take: frame point k = kept[perm[k]] (perm == NULL: k) -> the resident frame, and on request its sweep index and
 // imu_point; a perm that is not a permutation of 0..m-1 sets *bad (page-locked host word, read behind the stream synchronisation)
 __global__ void k_sub_take(const int *kept, const int *perm, int m, unsigned *seen, unsigned seen_tag, const double *raw, const double *imu,
@@ -570,6 +503,117 @@ int wait_frame_word(srl_ctx *ctx, const unsigned long long *h_ctrl, unsigned tag
         }
     }
     *out = ctrl;
+    return SRL_OK;
+}
+
+// ---------------------------------------------------------------------------- the grid-sampling chain, host side
+// ONE sequence for keypoint selection and the sweep sub-sample: enqueue (the caller's group kernel goes in as a callable), wait, order.
+struct GridChain {
+    // inputs
+    const int *order = nullptr;                 // device: the element a voxel carries is order[its first index] instead of the index (RankSink)
+    int *d_list = nullptr;                      // device ordering: where the ordered list goes (null: scratch of the chain's own)
+    const double *gather_raw = nullptr;         // device ordering: k_tr1_rank also gathers point list[k] of gather_raw into gx / gy / gz[k]
+    double *gx = nullptr, *gy = nullptr, *gz = nullptr;
+    // grid_chain_enqueue
+    unsigned nb_max = 0, tag = 0;
+    bool dev_order = false;
+    DevBuf b_flag, b_keyat, b_hash, b_first, b_bcnt, b_members, b_elem, b_bstart, b_list, b_sc;
+    // the host exchange block: [0] count word | hashes (8 B) | elements (4 B) | ordered list (4 B)
+    unsigned long long *h_ctrl = nullptr, *h_hash = nullptr;
+    unsigned *h_first = nullptr;
+    int *h_list = nullptr;
+    // grid_chain_wait
+    int m = 0;                                  // voxels
+    bool overflow = false, bad_order = false;
+    // grid_chain_order
+    bool list_on_host = false;                  // the ordered list is h_list (host replay), else d_list
+};
+
+template <class Group>
+int grid_chain_enqueue(srl_ctx *ctx, GridChain &C, int n, Group &&launch_group) {
+    hipStream_t st = ctx->stream;
+    // group by sampling voxel in a scratch table of >= 2 n slots (epoch-tagged: never cleared between frames, srl_frame_scratch.h)
+    unsigned cap = 1024;
+    while (cap < 2u * (unsigned)n) cap <<= 1;
+    // the ORDER on the device (see "keypoint ORDER on the device" above) when the bucket table of n voxels fits the scans
+    { const int rco = tr1_device_order(ctx, n, &C.nb_max); if (rco) return rco; }
+    const unsigned nb_max = C.nb_max;
+    const bool dev_order = C.dev_order = nb_max > 0;
+    HIPCHK(ctx, C.b_flag.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, C.b_keyat.alloc(ctx, (size_t)n * 8));
+    HIPCHK(ctx, C.b_sc.alloc(ctx, srl_scan_scratch_ints(std::max(n, (int)nb_max)) * 4));      // tile sums of the scans beyond one launch (srl_scan)
+    if (dev_order) {
+        HIPCHK(ctx, C.b_hash.alloc(ctx, (size_t)n * 8)); HIPCHK(ctx, C.b_first.alloc(ctx, (size_t)n * 4));
+        HIPCHK(ctx, C.b_bcnt.alloc(ctx, (size_t)nb_max * 4)); HIPCHK(ctx, C.b_members.alloc(ctx, (size_t)nb_max * SRL_TR1_BUCKET_SLOTS * 8));
+        HIPCHK(ctx, C.b_elem.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, C.b_bstart.alloc(ctx, (size_t)nb_max * 4));
+        if (!C.d_list) { HIPCHK(ctx, C.b_list.alloc(ctx, (size_t)n * 4)); C.d_list = C.b_list.as<int>(); }
+    }
+    // one epoch of the selection's scratch table per chain: the sub-sample and the selection of a frame share it, the chain that follows opens
+    // the next epoch and its {~counter, ...} words win every atomicMin against the ones left here
+    int rct = srl_epoch_table_begin(ctx, ctx->sel_table, cap, true);
+    if (rct) return rct;
+    const SrlEpochTable &T = ctx->sel_table;
+    int rcx = ensure_frame_exchange(ctx, 64 + (size_t)n * 16);
+    if (rcx) return rcx;
+    C.h_ctrl = reinterpret_cast<unsigned long long *>(ctx->h_frame_x);
+    C.h_hash = reinterpret_cast<unsigned long long *>(ctx->h_frame_x + 64);
+    C.h_first = reinterpret_cast<unsigned *>(ctx->h_frame_x + 64 + (size_t)n * 8);
+    C.h_list = reinterpret_cast<int *>(ctx->h_frame_x + 64 + (size_t)n * 12);
+    if (++ctx->frame_tag == 0) ++ctx->frame_tag;
+    C.tag = ctx->frame_tag;
+    __atomic_store_n(C.h_ctrl, 0ull, __ATOMIC_RELEASE);
+    int *flag = C.b_flag.as<int>();
+    unsigned long long *key_at = C.b_keyat.as<unsigned long long>();
+    launch_group(GroupArgs{T.keyw, T.minw, cap - 1, T.epoch16, T.counter32, flag});
+    const unsigned mark_threads = dev_order && nb_max > cap ? nb_max : cap;
+    hipLaunchKernelGGL(k_select_mark, dim3((mark_threads + 255) / 256), dim3(256), 0, st, T.keyw, T.minw, cap, T.epoch16, flag, key_at,
+                       dev_order ? C.b_bcnt.as<int>() : (int *)nullptr, dev_order ? nb_max : 0u);
+    if (dev_order) {
+        // ranks (first-occurrence order) -> bucket of every voxel at the table's final size, {tag, overflow, bad order, count} to the host ->
+        // scan over the bucket counts -> per voxel: rank inside its bucket, ordered list, gather of the raw point on request
+        unsigned long long *hash = C.b_hash.as<unsigned long long>(), *members = C.b_members.as<unsigned long long>();
+        unsigned *first = C.b_first.as<unsigned>(), *elem = C.b_elem.as<unsigned>();
+        int *bcnt = C.b_bcnt.as<int>(), *bstart = C.b_bstart.as<int>();
+        srl_scan(SrlIntArrayIn{flag}, RankSink{key_at, hash, first, C.order}, n, C.b_sc.as<int>(), st, CountFin{ctx->d_frame_sync});
+        hipLaunchKernelGGL(k_tr1_bucket, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, hash, bcnt, members, elem, C.h_ctrl, C.tag);
+        srl_scan(SrlIntArrayIn{bcnt}, SrlIntArraySink{bstart}, (int)nb_max, C.b_sc.as<int>(), st);
+        auto rank = C.gather_raw ? k_tr1_rank<true> : k_tr1_rank<false>;
+        hipLaunchKernelGGL(rank, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, hash, first, members, bcnt, bstart, elem,
+                           C.gather_raw, C.gx, C.gy, C.gz, C.d_list);
+    } else {
+        // ranks, hand-over to the host and the completion word in the scan's own pass
+        srl_scan(SrlIntArrayIn{flag}, RankSink{key_at, C.h_hash, C.h_first, C.order}, n, C.b_sc.as<int>(), st, EmitFin{ctx->d_frame_sync, C.h_ctrl, C.tag});
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return SRL_OK;
+}
+
+// the count word: how many voxels, and what the device had to say about them
+int grid_chain_wait(srl_ctx *ctx, GridChain &C, const char *what) {
+    unsigned long long ctrl = 0;
+    { const int rcw = wait_frame_word(ctx, C.h_ctrl, C.tag, what, &ctrl); if (rcw) return rcw; }
+    C.m = (int)((unsigned)ctrl & SRL_CTRL_COUNT_MASK);
+    C.overflow = C.dev_order && ((unsigned)ctrl & SRL_CTRL_OVERFLOW);
+    C.bad_order = ((unsigned)ctrl & SRL_CTRL_BAD_ORDER) != 0;
+    return SRL_OK;
+}
+
+// who orders (frame_order_used: 1 the device, 2 the host, 3 the host behind an overfull bucket), and the host's part of it: the voxels arrive in
+// FIRST-OCCURRENCE order (= the order subSampleFrame's loop creates them in); the iteration order of its std::tr1::unordered_map comes from
+// replaying the container's bucket moves on flat arrays (host/tr1_order.h) for the m distinct voxels (not the n points)
+int grid_chain_order(srl_ctx *ctx, GridChain &C) {
+    ctx->frame_order_used = C.dev_order ? (C.overflow ? 3 : 1) : 2;
+    C.list_on_host = !C.dev_order || C.overflow;
+    if (!C.list_on_host) return SRL_OK;
+    if (C.overflow) {
+        // a bucket with more voxels than the device ranks in place: fetch {hash, element} and order on the host like larger frames
+        HIPCHK(ctx, hipMemcpyAsync(C.h_hash, C.b_hash.p, (size_t)C.m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(C.h_first, C.b_first.p, (size_t)C.m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    static_assert(sizeof(std::size_t) == sizeof(unsigned long long), "hashes are exchanged as 64-bit words");
+    std::vector<int> perm((size_t)C.m);
+    srl::Tr1Order::order(reinterpret_cast<const std::size_t *>(C.h_hash), C.m, perm.data());
+    for (int r = 0; r < C.m; r++) C.h_list[r] = (int)C.h_first[(size_t)perm[(size_t)r]];
     return SRL_OK;
 }
 
@@ -719,79 +763,25 @@ int srl_frame_subsample(srl_ctx *ctx, const int32_t *visit_order, int n, double 
     }
     unsigned seen_tag = 0;
     { const int rcs = sub_seen_begin(ctx, &seen_tag); if (rcs) return rcs; }
-    unsigned nb_max = 0;
-    { const int rco = tr1_device_order(ctx, n, &nb_max); if (rco) return rco; }
-    const bool dev_order = nb_max > 0;
-    unsigned cap = 1024;
-    while (cap < 2u * (unsigned)n) cap <<= 1;
-    DevBuf b_order, b_flag, b_keyat, b_hash, b_first, b_bcnt, b_members, b_elem, b_bstart, b_sc;
+    DevBuf b_order;
     HIPCHK(ctx, b_order.alloc(ctx, (size_t)n * 4));
-    HIPCHK(ctx, b_flag.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_keyat.alloc(ctx, (size_t)n * 8));
-    HIPCHK(ctx, b_sc.alloc(ctx, srl_scan_scratch_ints(std::max(n, (int)nb_max)) * 4));
-    if (dev_order) {
-        HIPCHK(ctx, b_hash.alloc(ctx, (size_t)n * 8)); HIPCHK(ctx, b_first.alloc(ctx, (size_t)n * 4));
-        HIPCHK(ctx, b_bcnt.alloc(ctx, (size_t)nb_max * 4)); HIPCHK(ctx, b_members.alloc(ctx, (size_t)nb_max * SRL_TR1_BUCKET_SLOTS * 8));
-        HIPCHK(ctx, b_elem.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_bstart.alloc(ctx, (size_t)nb_max * 4));
-    }
     HIPCHK(ctx, hipMemcpyAsync(b_order.p, visit_order, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    // its own epoch of the selection's scratch table: the selection that follows in this frame opens the next one, and its {~counter, ...}
-    // words win every atomicMin against the ones left here
-    int rct = srl_epoch_table_begin(ctx, ctx->sel_table, cap, true);
-    if (rct) return rct;
-    const SrlEpochTable &T = ctx->sel_table;
-    // host exchange block: [0] control word {tag, flags, count} | hashes (8 B) | first visit ranks (4 B) | kept sweep indices (4 B)
-    int rcx = ensure_frame_exchange(ctx, 64 + (size_t)n * 16);
-    if (rcx) return rcx;
-    unsigned long long *h_ctrl = reinterpret_cast<unsigned long long *>(ctx->h_frame_x);
-    unsigned long long *h_hash = reinterpret_cast<unsigned long long *>(ctx->h_frame_x + 64);
-    unsigned *first = reinterpret_cast<unsigned *>(ctx->h_frame_x + 64 + (size_t)n * 8);
-    int *h_kept = reinterpret_cast<int *>(ctx->h_frame_x + 64 + (size_t)n * 12);
-    if (++ctx->frame_tag == 0) ++ctx->frame_tag;
-    const unsigned tag = ctx->frame_tag;
-    __atomic_store_n(h_ctrl, 0ull, __ATOMIC_RELEASE);
-    hipLaunchKernelGGL(k_sub_group, dim3((n + 255) / 256), dim3(256), 0, st, b_order.as<int>(), n, ctx->d_corr_in, sample_size, T.keyw, T.minw, cap - 1,
-                       T.epoch16, T.counter32, b_flag.as<int>(), ctx->d_sub_seen, seen_tag, ctx->d_frame_sync + 4);
-    const unsigned mark_threads = dev_order && nb_max > cap ? nb_max : cap;
-    hipLaunchKernelGGL(k_select_mark, dim3((mark_threads + 255) / 256), dim3(256), 0, st, T.keyw, T.minw, cap, T.epoch16, b_flag.as<int>(),
-                       b_keyat.as<unsigned long long>(), dev_order ? b_bcnt.as<int>() : (int *)nullptr, dev_order ? nb_max : 0u);
-    if (dev_order) {
-        srl_scan(SrlIntArrayIn{b_flag.as<int>()}, SubRankSink{b_keyat.as<unsigned long long>(), b_hash.as<unsigned long long>(), b_first.as<unsigned>(),
-                                                              b_order.as<int>()},
-                 n, b_sc.as<int>(), st, CountFin{ctx->d_frame_sync});
-        hipLaunchKernelGGL(k_tr1_bucket, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
-                           b_bcnt.as<int>(), b_members.as<unsigned long long>(), b_elem.as<unsigned>(), h_ctrl, tag);
-        srl_scan(SrlIntArrayIn{b_bcnt.as<int>()}, SrlIntArraySink{b_bstart.as<int>()}, (int)nb_max, b_sc.as<int>(), st);
-        hipLaunchKernelGGL(k_tr1_rank<false>, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
-                           b_first.as<unsigned>(), b_members.as<unsigned long long>(), b_bcnt.as<int>(), b_bstart.as<int>(), b_elem.as<unsigned>(),
-                           (const double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, ctx->d_sub_kept);
-    } else {
-        srl_scan(SrlIntArrayIn{b_flag.as<int>()}, EmitSink{b_keyat.as<unsigned long long>(), h_hash, first}, n, b_sc.as<int>(), st,
-                 EmitFin{ctx->d_frame_sync, h_ctrl, tag});
-    }
-    HIPCHK(ctx, hipGetLastError());
+    GridChain C;
+    C.order = b_order.as<int>();
+    C.d_list = ctx->d_sub_kept;
+    const int rce = grid_chain_enqueue(ctx, C, n, [&](const GroupArgs &G) {
+        hipLaunchKernelGGL(k_sub_group, dim3((n + 255) / 256), dim3(256), 0, st, C.order, n, ctx->d_corr_in, sample_size, G, ctx->d_sub_seen, seen_tag,
+                           ctx->d_frame_sync + 4);
+    });
+    if (rce) return rce;
     tp1 = std::chrono::steady_clock::now();
-    unsigned long long ctrl = 0;
-    { const int rcw = wait_frame_word(ctx, h_ctrl, tag, "frame sub-sample", &ctrl); if (rcw) return rcw; }
+    { const int rcw = grid_chain_wait(ctx, C, "frame sub-sample"); if (rcw) return rcw; }
     tp2 = std::chrono::steady_clock::now();
-    if ((unsigned)ctrl & SRL_CTRL_BAD_ORDER) { ctx->err = "visit order is not a permutation of 0..n-1"; return SRL_ERR_BAD_ARG; }
-    const int m = (int)((unsigned)ctrl & SRL_CTRL_COUNT_MASK);
-    const bool overflow = dev_order && (((unsigned)ctrl >> 31) & 1u);
-    ctx->frame_order_used = dev_order ? (overflow ? 3 : 1) : 2;
-    if (!dev_order || overflow) {
-        // the host replay of the container's order over the m voxels (host/tr1_order.h), as keypoint selection does it; the device path left
-        // first = sweep indices, the host path first = visit ranks
-        if (overflow) {
-            HIPCHK(ctx, hipMemcpyAsync(h_hash, b_hash.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipMemcpyAsync(first, b_first.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-        }
-        std::vector<int> perm((size_t)m);
-        srl::Tr1Order::order(reinterpret_cast<const std::size_t *>(h_hash), m, perm.data());
-        for (int r = 0; r < m; r++) {
-            const unsigned f = first[(size_t)perm[(size_t)r]];
-            h_kept[r] = overflow ? (int)f : visit_order[f];
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_sub_kept, h_kept, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    if (C.bad_order) { ctx->err = "visit order is not a permutation of 0..n-1"; return SRL_ERR_BAD_ARG; }
+    const int m = C.m;
+    { const int rco = grid_chain_order(ctx, C); if (rco) return rco; }
+    if (C.list_on_host) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_sub_kept, C.h_list, (size_t)m * 4, hipMemcpyHostToDevice, st));
         HIPCHK(ctx, hipStreamSynchronize(st));      // (the exchange block is the next chain's)
     }
     tp3 = std::chrono::steady_clock::now();
@@ -913,100 +903,41 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
         if (rc) return rc;
         Xf X;
         fill_xf(X, q, t, R_il, t_il);
-        // group by sampling voxel in a scratch table of >= 2 n slots (epoch-tagged: never cleared between frames, srl_frame_scratch.h)
-        unsigned cap = 1024;
-        while (cap < 2u * (unsigned)n) cap <<= 1;
-        // the keypoint ORDER on the device (see "keypoint ORDER on the device" above) when the bucket table of n voxels fits one scan launch
-        unsigned nb_max = 0;
-        { const int rco = tr1_device_order(ctx, n, &nb_max); if (rco) return rco; }
-        const bool dev_order = nb_max > 0;
-        DevBuf b_flag, b_keyat, b_hash, b_first, b_bcnt, b_members, b_elem, b_bstart, b_sel, b_sc;
-        HIPCHK(ctx, b_flag.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_keyat.alloc(ctx, (size_t)n * 8));
-        HIPCHK(ctx, b_sc.alloc(ctx, srl_scan_scratch_ints(std::max(n, (int)nb_max)) * 4));      // tile sums of the scans beyond one launch (srl_scan)
-        if (dev_order) {
-            HIPCHK(ctx, b_hash.alloc(ctx, (size_t)n * 8)); HIPCHK(ctx, b_first.alloc(ctx, (size_t)n * 4));
-            HIPCHK(ctx, b_bcnt.alloc(ctx, (size_t)nb_max * 4)); HIPCHK(ctx, b_members.alloc(ctx, (size_t)nb_max * SRL_TR1_BUCKET_SLOTS * 8));
-            HIPCHK(ctx, b_elem.alloc(ctx, (size_t)n * 4)); HIPCHK(ctx, b_bstart.alloc(ctx, (size_t)nb_max * 4));
-            HIPCHK(ctx, b_sel.alloc(ctx, (size_t)n * 4));
-        }
-        int rct = srl_epoch_table_begin(ctx, ctx->sel_table, cap, true);
-        if (rct) return rct;
-        const SrlEpochTable &T = ctx->sel_table;
-        // host exchange block: [0] control word {tag, count} | hashes (8 B) | first indices (4 B) | ordered index list (4 B)
-        int rcx = ensure_frame_exchange(ctx, 64 + (size_t)n * 16);
-        if (rcx) return rcx;
-        unsigned long long *h_ctrl = reinterpret_cast<unsigned long long *>(ctx->h_frame_x);
-        unsigned long long *h_hash = reinterpret_cast<unsigned long long *>(ctx->h_frame_x + 64);
-        unsigned *first = reinterpret_cast<unsigned *>(ctx->h_frame_x + 64 + (size_t)n * 8);
-        int *h_sel = reinterpret_cast<int *>(ctx->h_frame_x + 64 + (size_t)n * 12);
-        if (++ctx->frame_tag == 0) ++ctx->frame_tag;
-        const unsigned tag = ctx->frame_tag;
-        __atomic_store_n(h_ctrl, 0ull, __ATOMIC_RELEASE);
+        // the keypoints' raw points become the resident sweep: gathered by the chain's last kernel, or behind the host's replay
         double *sx = ctx->d_raw, *sy = ctx->d_raw + ctx->sweep_cap, *sz = ctx->d_raw + 2 * (size_t)ctx->sweep_cap;
-        hipLaunchKernelGGL(k_select_group, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_frame_raw, n, X, sample_voxel_size, T.keyw, T.minw, cap - 1, T.epoch16,
-                           T.counter32, b_flag.as<int>());
-        const unsigned mark_threads = dev_order && nb_max > cap ? nb_max : cap;
-        hipLaunchKernelGGL(k_select_mark, dim3((mark_threads + 255) / 256), dim3(256), 0, st, T.keyw, T.minw, cap, T.epoch16, b_flag.as<int>(),
-                           b_keyat.as<unsigned long long>(), dev_order ? b_bcnt.as<int>() : (int *)nullptr, dev_order ? nb_max : 0u);
-        if (dev_order) {
-            // ranks (first-occurrence order) -> bucket of every voxel at the table's final size, {tag, overflow, count} to the host -> scan
-            // over the bucket counts -> per voxel: rank inside its bucket, ordered index list, gather of the raw point
-            srl_scan(SrlIntArrayIn{b_flag.as<int>()}, RankSink{b_keyat.as<unsigned long long>(), b_hash.as<unsigned long long>(), b_first.as<unsigned>()}, n,
-                     b_sc.as<int>(), st, CountFin{ctx->d_frame_sync});
-            hipLaunchKernelGGL(k_tr1_bucket, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
-                               b_bcnt.as<int>(), b_members.as<unsigned long long>(), b_elem.as<unsigned>(), h_ctrl, tag);
-            srl_scan(SrlIntArrayIn{b_bcnt.as<int>()}, SrlIntArraySink{b_bstart.as<int>()}, (int)nb_max, b_sc.as<int>(), st);
-            hipLaunchKernelGGL(k_tr1_rank<true>, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_tr1_sched, ctx->d_frame_sync, b_hash.as<unsigned long long>(),
-                               b_first.as<unsigned>(), b_members.as<unsigned long long>(), b_bcnt.as<int>(), b_bstart.as<int>(), b_elem.as<unsigned>(),
-                               ctx->d_frame_raw, sx, sy, sz, b_sel.as<int>());
-        } else {
-            // ranks, hand-over to the host and the completion word in the scan's own pass
-            srl_scan(SrlIntArrayIn{b_flag.as<int>()}, EmitSink{b_keyat.as<unsigned long long>(), h_hash, first}, n, b_sc.as<int>(), st,
-                     EmitFin{ctx->d_frame_sync, h_ctrl, tag});
-        }
-        HIPCHK(ctx, hipGetLastError());
+        GridChain C;
+        C.gather_raw = ctx->d_frame_raw; C.gx = sx; C.gy = sy; C.gz = sz;
+        rc = grid_chain_enqueue(ctx, C, n, [&](const GroupArgs &G) {
+            hipLaunchKernelGGL(k_select_group, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_frame_raw, n, X, sample_voxel_size, G);
+        });
+        if (rc) return rc;
         srl_stage_end(ctx, 1);
         tp1 = std::chrono::steady_clock::now();
-        unsigned long long ctrl = 0;
-        { const int rcw = wait_frame_word(ctx, h_ctrl, tag, "keypoint selection", &ctrl); if (rcw) return rcw; }
-        const int S = (int)((unsigned)ctrl & 0x7FFFFFFFu);
-        const bool overflow = dev_order && (((unsigned)ctrl >> 31) & 1u);
+        rc = grid_chain_wait(ctx, C, "keypoint selection");      // (bad_order: no selection sets it)
+        if (rc) return rc;
         srl_stage_end(ctx, 2);
         tp2 = std::chrono::steady_clock::now();
-        m = S;
-        ctx->frame_order_used = dev_order ? (overflow ? 3 : 1) : 2;
-        if (!dev_order || overflow) {
-            if (overflow) {
-                // a bucket with more voxels than the device ranks in place: fetch {hash, first index} and order on the host like larger frames
-                HIPCHK(ctx, hipMemcpyAsync(h_hash, b_hash.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipMemcpyAsync(first, b_first.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipStreamSynchronize(st));
-            }
-            // the voxels arrive in FIRST-OCCURRENCE order (= the order subSampleFrame's loop creates them): ordered on the device.
-            // Iteration order of the std::tr1::unordered_map of subSampleFrame, by replaying its bucket moves on flat arrays
-            // (host/tr1_order.h) for the S distinct voxels (not the N points)
-            static_assert(sizeof(std::size_t) == sizeof(unsigned long long), "hashes are exchanged as 64-bit words");
-            std::vector<int> perm((size_t)S);
-            srl::Tr1Order::order(reinterpret_cast<const std::size_t *>(h_hash), S, perm.data());
+        m = C.m;
+        rc = grid_chain_order(ctx, C);
+        if (rc) return rc;
+        srl_stage_end(ctx, 3);
+        if (C.list_on_host) {
             // the gather reads the ordered index list straight out of the exchange block (its own region: nothing is written there before
             // the next frame's list, and that is produced behind a wait on a later kernel of this stream)
-            for (int r = 0; r < S; r++) h_sel[r] = (int)first[(size_t)perm[(size_t)r]];
-            srl_stage_end(ctx, 3);
             tp3 = std::chrono::steady_clock::now();
             if (m > 0) {
-                hipLaunchKernelGGL(k_gather_soa, dim3((m + 255) / 256), dim3(256), 0, st, ctx->d_frame_raw, h_sel, m, sx, sy, sz);
+                hipLaunchKernelGGL(k_gather_soa, dim3((m + 255) / 256), dim3(256), 0, st, ctx->d_frame_raw, C.h_list, m, sx, sy, sz);
                 HIPCHK(ctx, hipGetLastError());
             }
         } else {
-            srl_stage_end(ctx, 3);
             tp3 = tp2;
             if (keypoint_index && m > 0) {
                 // the ordered index list is wanted on the host (tests, tools; the host mirror passes NULL): one copy behind the chain
-                HIPCHK(ctx, hipMemcpyAsync(h_sel, b_sel.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(ctx, hipMemcpyAsync(C.h_list, C.d_list, (size_t)m * 4, hipMemcpyDeviceToHost, st));
                 HIPCHK(ctx, hipStreamSynchronize(st));
             }
         }
-        if (keypoint_index) std::memcpy(keypoint_index, h_sel, (size_t)m * 4);
+        if (keypoint_index) std::memcpy(keypoint_index, C.h_list, (size_t)m * 4);
     } else {
         srl_stage_end(ctx, 3);
     }
@@ -1061,8 +992,7 @@ int frame_commit_impl(srl_ctx *ctx, const double q[4], const double t[3], const 
     // less on a chain whose cost is its launches); otherwise a kernel of its own, as stage 5 of srl_debug_frame_timing.
     const bool fused = n <= SRL_SCAN_MAX && !ctx->frame_timing;
     if (!fused) {
-        hipLaunchKernelGGL(k_frame_keys, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_frame_raw, n, xf.X, 1.0, ctx->d_frame_world,
-                           (unsigned long long *)nullptr, (unsigned *)nullptr);
+        hipLaunchKernelGGL(k_frame_world, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_frame_raw, n, xf.X, ctx->d_frame_world);
         HIPCHK(ctx, hipGetLastError());
         srl_stage_end(ctx, 5);
         const int rcw = world_ready(ctx, &dl);

@@ -21,6 +21,15 @@
 
 // transformPoint's operands (utility.cpp:314-318): point = R(q) * (R_il * raw + t_il) + t
 struct SrlXf { double R[9], t[3], R_il[9], t_il[3]; };
+// ... in the operation order that decides voxel keys bit for bit: (a x + b y) + c z + t per row, twice
+__device__ __forceinline__ void srl_transform_point(const SrlXf &X, double rx, double ry, double rz, double &wx, double &wy, double &wz) {
+    const double ix = (X.R_il[0] * rx + X.R_il[1] * ry) + X.R_il[2] * rz + X.t_il[0];
+    const double iy = (X.R_il[3] * rx + X.R_il[4] * ry) + X.R_il[5] * rz + X.t_il[1];
+    const double iz = (X.R_il[6] * rx + X.R_il[7] * ry) + X.R_il[8] * rz + X.t_il[2];
+    wx = (X.R[0] * ix + X.R[1] * iy) + X.R[2] * iz + X.t[0];
+    wy = (X.R[3] * ix + X.R[4] * iy) + X.R[5] * iz + X.t[1];
+    wz = (X.R[6] * ix + X.R[7] * iy) + X.R[8] * iz + X.t[2];
+}
 // srl_frame_commit hands the re-transform of the frame (optimize.cpp:441-445) to the first kernel of the insertion behind it
 struct SrlFrameTransform {
     const double *raw;       // the resident frame's raw points (AoS)

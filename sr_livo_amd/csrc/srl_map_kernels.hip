@@ -27,8 +27,7 @@ namespace {
 // addressing, compare-and-swap; one slot per distinct key), and the stable radix sort runs over log2(slots) bits: 2 passes for a
 // 24k-point frame instead of 6.  Which segment comes first is irrelevant downstream (creation order = first-point rank, replay =
 // per segment).
-// XF: the points are first re-transformed (optimize.cpp:441-445: point = R(q) * (R_il * raw + t_il) + t, the operation order of
-// k_frame_keys / transformPoint) and stored where the rest of the insertion -- and the download of point3D::point -- reads them
+// XF: the points are first re-transformed (optimize.cpp:441-445: transformPoint, srl_transform_point) and stored where the rest of the insertion -- and the download of point3D::point -- reads them
 template <bool XF>
 __global__ void k_point_slots(const double *xyz, int n, double voxel_size, unsigned long long *keyw, unsigned mask, unsigned epoch16, unsigned *slot_out,
                               unsigned *idx, int *new_flag, const SrlFrameTransform T) {
@@ -36,14 +35,7 @@ __global__ void k_point_slots(const double *xyz, int n, double voxel_size, unsig
     if (i >= n) return;
     double wx, wy, wz;
     if (XF) {
-        const SrlXf &X = T.X;
-        const double rx = T.raw[(size_t)i * 3], ry = T.raw[(size_t)i * 3 + 1], rz = T.raw[(size_t)i * 3 + 2];
-        const double ix = (X.R_il[0] * rx + X.R_il[1] * ry) + X.R_il[2] * rz + X.t_il[0];
-        const double iy = (X.R_il[3] * rx + X.R_il[4] * ry) + X.R_il[5] * rz + X.t_il[1];
-        const double iz = (X.R_il[6] * rx + X.R_il[7] * ry) + X.R_il[8] * rz + X.t_il[2];
-        wx = (X.R[0] * ix + X.R[1] * iy) + X.R[2] * iz + X.t[0];
-        wy = (X.R[3] * ix + X.R[4] * iy) + X.R[5] * iz + X.t[1];
-        wz = (X.R[6] * ix + X.R[7] * iy) + X.R[8] * iz + X.t[2];
+        srl_transform_point(T.X, T.raw[(size_t)i * 3], T.raw[(size_t)i * 3 + 1], T.raw[(size_t)i * 3 + 2], wx, wy, wz);
         T.world[(size_t)i * 3] = wx; T.world[(size_t)i * 3 + 1] = wy; T.world[(size_t)i * 3 + 2] = wz;
     } else {
         wx = xyz[(size_t)i * 3]; wy = xyz[(size_t)i * 3 + 1]; wz = xyz[(size_t)i * 3 + 2];

@@ -660,7 +660,7 @@ int srl_debug_block_times(srl_ctx *ctx, double *out, int max_blocks, int *nblock
     const int nb = std::min(max_blocks, ctx->last_nblocks);
     std::vector<double> tmp((size_t)nb * SRL_PART_STRIDE);
     HIPCHK(ctx, hipMemcpy(tmp.data(), ctx->d_partials, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int b = 0; b < nb; b++) for (int k = 0; k < 3; k++) out[(size_t)b * 3 + k] = tmp[(size_t)b * SRL_PART_STRIDE + 28 + k];
+    for (int b = 0; b < nb; b++) for (int k = 0; k < 3; k++) out[(size_t)b * 3 + k] = tmp[(size_t)b * SRL_PART_STRIDE + SRL_ROW_SUMS + k];
     *nblocks = nb;
     return SRL_OK;
 }

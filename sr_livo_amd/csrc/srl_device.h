@@ -40,6 +40,53 @@
 #define SRL_FUSED_MAX_GROUPS (SRL_FUSED_MAX_BLOCKS / SRL_FUSED_GROUP)   // "super row" (stored behind the rows); the grid's last workgroup adds the super rows
 #define SRL_FUSED_CUT_MAX_KPB 64   // fused ordered cut: the finisher re-reads one workgroup's records, one granule per thread
 
+// ---- the row of the final reduction (a wave's, a workgroup's, a group's and the grid's sums all have this layout): 28 sums -- the
+// upper triangle of H^T H row by row, H^T h, the loss -- and, in a published row, four counters carried as doubles
+enum : int {
+    SRL_ROW_HTH = 0,            // [0, 21): H^T H(ia, ib), ia <= ib < 6, row by row
+    SRL_ROW_HTH_V = 21,         // [21, 27): H^T h
+    SRL_ROW_LOSS = 27,
+    SRL_ROW_SUMS = 28,          // components that are sums of floating-point terms (the summation order is part of the result)
+    SRL_ROW_ACCEPTED = 28,      // accepted residuals
+    SRL_ROW_SUM_PK = 29,        // candidates visited
+    SRL_ROW_NAN = 30,           // 1 + index inside the workgroup of its first NaN-planarity keypoint, 0 = none
+    SRL_ROW_FALLBACK = 31,      // keypoints off the fast path
+};
+static_assert(SRL_ROW_FALLBACK + 1 == SRL_PART_STRIDE, "a row is SRL_PART_STRIDE doubles");
+#define SRL_ROW_TIMEOUT_MARK 0x7117ll   // SrlDevOut::pad when a workgroup's row never reached the finisher
+struct SrlRowPair { int ia, ib; };
+// component c < SRL_ROW_HTH_V of the triangle -> (ia, ib)
+__host__ __device__ constexpr SrlRowPair srl_row_tri_pair(int c) {
+    int r = 0;
+    while (c >= 6 - r) { c -= 6 - r; ++r; }
+    return SrlRowPair{r, r + c};
+}
+// ... and back: (i0, i1) in either order -> component
+__host__ __device__ constexpr int srl_row_tri_comp(int i0, int i1) {
+    const int ia = i0 < i1 ? i0 : i1, ib = i0 < i1 ? i1 : i0;
+    return SRL_ROW_HTH + ia * 6 - (ia * (ia - 1)) / 2 + (ib - ia);
+}
+// Sum c < SRL_ROW_SUMS = the sum over the keypoints of operand ia x operand ib of the keypoint's
+//   phase-2 row {J0..J5, h, distance}         (srl_row_pair): H^T h = (i, 6), loss = (7, 7);
+//   record      {J0..J5, distance, weight}    (srl_rec_pair): H^T h = J_i x (distance x weight), i.e. (i, 6) with the weight on the
+//                                             second operand (record_term, srl_kernels.hip), loss = (6, 6).
+__host__ __device__ constexpr SrlRowPair srl_row_pair(int c) {
+    return c < SRL_ROW_HTH_V ? srl_row_tri_pair(c) : (c < SRL_ROW_LOSS ? SrlRowPair{c - SRL_ROW_HTH_V, 6} : SrlRowPair{7, 7});
+}
+__host__ __device__ constexpr SrlRowPair srl_rec_pair(int c) {
+    return c < SRL_ROW_HTH_V ? srl_row_tri_pair(c) : (c < SRL_ROW_LOSS ? SrlRowPair{c - SRL_ROW_HTH_V, 6} : SrlRowPair{6, 6});
+}
+constexpr bool srl_row_layout_ok() {
+    int c = 0;
+    for (int ia = 0; ia < 6; ++ia)
+        for (int ib = ia; ib < 6; ++ib, ++c) {          // the upper triangle row by row
+            const SrlRowPair p = srl_row_tri_pair(c);
+            if (p.ia != ia || p.ib != ib || srl_row_tri_comp(ia, ib) != c || srl_row_tri_comp(ib, ia) != c) return false;
+        }
+    return c == SRL_ROW_HTH_V;
+}
+static_assert(srl_row_layout_ok(), "component -> (ia, ib) -> component is the identity and walks the upper triangle row by row");
+
 struct SrlMapSlot {
     unsigned long long key;
     unsigned slab;

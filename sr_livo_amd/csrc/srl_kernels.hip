@@ -1128,6 +1128,80 @@ __device__ __forceinline__ v4u32 row_load(__amdgpu_buffer_rsrc_t rs, int block, 
     return __builtin_amdgcn_raw_buffer_load_b128(rs, (block * SRL_ROW_GRANULES + 2 * comp) * 8, 0, (int)0x80000010);
 }
 #endif
+// the payload halves of two tagged granules -> the double they carry
+__device__ __forceinline__ double granule_double(unsigned lo, unsigned hi) {
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+#define SRL_ROW_SPIN_BOUND (1u << 18)         // polls of a finisher for a tagged row, record or mask (~0.3 s: something died; do not hang the GPU)
+#if defined(__HIP_DEVICE_COMPILE__)
+// The bounded poll-and-sum of a finisher: component `comp` of the rows first, first + NPART, ... < end that `want` names, added to `acc`
+// in ascending order, INF rows per memory round trip (a round is repeated until every tag carries this launch's epoch).  Row `own` is
+// the finisher's own: it comes from LDS (s_own; own < 0: none).  SLEEP: the s_sleep argument between two polls.  Sets timed_out when a
+// row never arrived.
+template <int NPART, int INF, int SLEEP, class Want>
+__device__ __forceinline__ double sum_tagged_rows(__amdgpu_buffer_rsrc_t rs, int first, int end, int own, int comp, const double *s_own,
+                                                  unsigned epoch, Want want, double acc, bool &timed_out) {
+    for (int r0 = first; r0 < end; r0 += NPART * INF) {
+        unsigned lo[INF], hi[INF];
+        unsigned spins = 0;
+        for (;;) {
+            bool ok = true;
+#pragma unroll
+            for (int k = 0; k < INF; ++k) {
+                const int r = r0 + NPART * k;
+                if (r < end && r != own && want(r)) {
+                    const v4u32 x = row_load(rs, r, comp);
+                    ok = ok && x.y == epoch && x.w == epoch;
+                    lo[k] = x.x; hi[k] = x.z;
+                } else if (r == own && want(r)) {                              // the own row: from LDS
+                    const unsigned long long ob = (unsigned long long)__double_as_longlong(s_own[comp]);
+                    lo[k] = (unsigned)ob; hi[k] = (unsigned)(ob >> 32);
+                } else { lo[k] = 0u; hi[k] = 0u; }
+            }
+            if (ok) break;
+            if (++spins > SRL_ROW_SPIN_BOUND) { timed_out = true; break; }
+            __builtin_amdgcn_s_sleep(SLEEP);
+        }
+#pragma unroll
+        for (int k = 0; k < INF; ++k) acc += granule_double(lo[k], hi[k]);
+    }
+    return acc;
+}
+#endif
+
+// What one record {J0..J5, distance, weight} adds to sum c of a row; p = srl_rec_pair(c).  (H^T h: h = distance x weight, optimize.cpp:169)
+__device__ __forceinline__ double record_term(const double *r, int c, SrlRowPair p) {
+    return (c >= SRL_ROW_HTH_V && c < SRL_ROW_LOSS) ? r[p.ia] * (r[p.ib] * r[7]) : r[p.ia] * r[p.ib];
+}
+
+// The one writer of SrlDevOut: lane c < SRL_ROW_SUMS files total[c] (the triangle to both halves of H^T H), lane 32 the tail.  Every
+// writer sits in wave 0 (the finishers' mail_out and the reduce kernel's drain rely on it).  put(p, x) stores x at p.
+struct SrlOutTail {
+    double num_res, total_accepted, sum_pk, nan, fallback, visited, timeout;
+    long long last_visited, pad;
+};
+template <class Put>
+__device__ __forceinline__ void write_dev_out(SrlDevOut *out, int tid, const double *total, const SrlOutTail &t, const Put &put) {
+    if (tid < SRL_ROW_HTH_V) {
+        const SrlRowPair p = srl_row_tri_pair(tid);
+        put(&out->HtH[p.ia * 6 + p.ib], total[tid]);
+        if (p.ib != p.ia) put(&out->HtH[p.ib * 6 + p.ia], total[tid]);
+    } else if (tid < SRL_ROW_LOSS) {
+        put(&out->Hth[tid - SRL_ROW_HTH_V], total[tid]);
+    } else if (tid == SRL_ROW_LOSS) {
+        put(&out->loss, total[SRL_ROW_LOSS]);
+    } else if (tid == 32) {
+        put(&out->d_num_res, t.num_res);
+        put(&out->d_total_accepted, t.total_accepted);
+        put(&out->d_sum_pk, t.sum_pk);
+        put(&out->d_nan, t.nan);
+        put(&out->d_fallback, t.fallback);
+        put(&out->d_visited, t.visited);
+        put(&out->d_timeout, t.timeout);
+        put(&out->last_visited, t.last_visited);
+        put(&out->pad, t.pad);
+    }
+}
 
 // debug time line of an ARMED pass (srl_debug_pass_stamps, tools/arm_timeline.py): workgroup 0 files slots 0..7, the finishing
 // workgroup slots 8..15 of row (seq & 63); the pointer is re-read from the kernarg segment at every site (nothing stays live)
@@ -1498,7 +1572,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
         const long long b = __double_as_longlong(v);
         const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, decltype(ctrl)::value, 0xF, 0xF, true);
         const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)b >> 32), decltype(ctrl)::value, 0xF, 0xF, true);
-        return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+        return granule_double((unsigned)lo, (unsigned)hi);
 #else
         return v;
 #endif
@@ -1658,19 +1732,12 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
             *reinterpret_cast<double4 *>(s_row + klw * 8 + 4) = v;
         }
         __builtin_amdgcn_wave_barrier();
-        if (lane < 28) {
+        if (lane < SRL_ROW_SUMS) {
             // (row, column) of component c: upper triangle of H^T H, then J_i h, then distance^2
-            int ia, ib;
-            if (lane < 21) {
-                // triangular index -> (ia, ib), ia <= ib < 6
-                int c = lane, r = 0;
-                while (c >= 6 - r) { c -= 6 - r; ++r; }
-                ia = r; ib = r + c;
-            } else if (lane < 27) { ia = lane - 21; ib = 6; }
-            else { ia = 7; ib = 7; }
+            const SrlRowPair p = srl_row_pair(lane);
             double acc = 0.0;
 #pragma unroll 16
-            for (int k = 0; k < KP2; ++k) acc += s_row[k * 8 + ia] * s_row[k * 8 + ib];
+            for (int k = 0; k < KP2; ++k) acc += s_row[k * 8 + p.ia] * s_row[k * 8 + p.ib];
             s_wpart[w2 * 32 + lane] = acc;
         }
     }
@@ -1722,7 +1789,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
         b.partials[(size_t)blockIdx.x * SRL_PART_STRIDE + tid] =
             (tid == 28) ? (double)dbg_t0 : ((tid == 29) ? (double)(long long)wall_clock64() : (double)__builtin_amdgcn_s_getreg(6164) /* XCC_ID */);
     // ---- block partial = wave partials added in wave order (deterministic)
-    if (tid < 28 && b.granules == nullptr) {
+    if (tid < SRL_ROW_SUMS && b.granules == nullptr) {
         double v = s_wpart[tid];
 #pragma unroll
         for (int w = 1; w < P2W; ++w) v += s_wpart[w * 32 + tid];
@@ -1803,10 +1870,9 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
     const int tid = threadIdx.x;
     const int lane = lane_id();
     const int wave = tid >> 6;
-    (void)lane; (void)wave;
-    // The normal equations are assembled in LDS (every writer sits in wave 0) and leave in ONE step: mail_out() below.
-    auto put_f = [](double *p, double x) { *p = x; };
-    auto put_i = [](long long *p, long long x) { *p = x; };
+    // The normal equations are assembled in LDS (write_dev_out with a plain store; every writer sits in wave 0) and leave in ONE step:
+    // mail_out() below.
+    auto put = [](auto *p, auto x) { *p = x; };
     // mail_out: wave 0 sends the 52 words of the staged SrlDevOut.  Tagged form (the host mailbox of a single-context pass): word w
     // travels as two granules {sequence number, 32-bit half} -- the host checks the tags, so no store has to wait for another (the
     // plain form pays a drain + a second PCIe write for the sequence word: ~1.2 us).  Plain form: a device-side mailbox the RCCL
@@ -1846,24 +1912,23 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
             bool timed_out = false;
             auto ld = [](const unsigned long long *p) { return __hip_atomic_load((gu64 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
             auto fresh = [epoch](unsigned long long x) { return (unsigned)(x >> 32) == epoch; };
-            auto as_double = [](unsigned lo, unsigned hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); };
             // (a) four granules per thread, requested together (every poll round is one memory round trip, not four)
             const __amdgpu_buffer_rsrc_t rs = rows_rsrc(b.granules);
             const double *s_own = reinterpret_cast<const double *>(smem + SRL_OWN_ROW_OFFSET);      // this workgroup's own row (assoc_body)
             long long my_acc = 0;
             if (tid < nbk) {
                 double d_acc, d_nan;
-                if (tid == nbk - 1) { d_acc = s_own[28]; d_nan = s_own[30]; }
+                if (tid == nbk - 1) { d_acc = s_own[SRL_ROW_ACCEPTED]; d_nan = s_own[SRL_ROW_NAN]; }
                 else {
                     v4u32 x0, x1;
                     unsigned spins = 0;
                     for (;;) {
-                        x0 = row_load(rs, tid, 28); x1 = row_load(rs, tid, 30);
+                        x0 = row_load(rs, tid, SRL_ROW_ACCEPTED); x1 = row_load(rs, tid, SRL_ROW_NAN);
                         if (x0.y == epoch && x0.w == epoch && x1.y == epoch && x1.w == epoch) break;
-                        if (++spins > (1u << 18)) { timed_out = true; x0 = x1 = v4u32{0u, 0u, 0u, 0u}; break; }
+                        if (++spins > SRL_ROW_SPIN_BOUND) { timed_out = true; x0 = x1 = v4u32{0u, 0u, 0u, 0u}; break; }
                         __builtin_amdgcn_s_sleep(4);
                     }
-                    d_acc = as_double(x0.x, x0.z); d_nan = as_double(x1.x, x1.z);
+                    d_acc = granule_double(x0.x, x0.z); d_nan = granule_double(x1.x, x1.z);
                 }
                 my_acc = (long long)d_acc;
                 const int nanf = (int)d_nan;
@@ -1890,43 +1955,20 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
             const unsigned long long *p_msk = b.granules + (size_t)(cut ? c : 0) * SRL_ROW_GRANULES + 64 + (tid & 7);
             unsigned long long x_rec = 0ull, x_msk = 0ull;
             if (cut) { x_rec = ld(p_rec); x_msk = ld(p_msk); }
-            // (b)
+            // (b) the sums of the rows below the cut workgroup, the counters of all rows
             const int comp = tid & 31, part = tid >> 5;
-            double s0 = 0.0;
-            for (int r0 = part; r0 < nbk; r0 += NPART * INF) {
-                unsigned lo[INF], hi[INF];
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int k = 0; k < INF; ++k) {
-                        const int r = r0 + NPART * k;
-                        if (r < nbk - 1 && (comp >= 28 || r < c)) {
-                            const v4u32 x = row_load(rs, r, comp);
-                            ok = ok && x.y == epoch && x.w == epoch;
-                            lo[k] = x.x; hi[k] = x.z;
-                        } else if (r == nbk - 1 && (comp >= 28 || r < c)) {        // the own row: from LDS
-                            const unsigned long long ob = (unsigned long long)__double_as_longlong(s_own[comp]);
-                            lo[k] = (unsigned)ob; hi[k] = (unsigned)(ob >> 32);
-                        } else { lo[k] = 0u; hi[k] = 0u; }
-                    }
-                    if (ok) break;
-                    if (++spins > (1u << 18)) { timed_out = true; break; }
-                    __builtin_amdgcn_s_sleep(8);
-                }
-#pragma unroll
-                for (int k = 0; k < INF; ++k) s0 += as_double(lo[k], hi[k]);
-            }
+            const double s0 = sum_tagged_rows<NPART, INF, 8>(rs, part, nbk, nbk - 1, comp, s_own, epoch,
+                                                             [comp, c](int r) { return comp >= SRL_ROW_SUMS || r < c; }, 0.0, timed_out);
             if (cut) {
                 unsigned spins = 0;
                 while (!(fresh(x_rec) && fresh(x_msk))) {
-                    if (++spins > (1u << 18)) { timed_out = true; x_rec = 0ull; x_msk = 0ull; break; }
+                    if (++spins > SRL_ROW_SPIN_BOUND) { timed_out = true; x_rec = 0ull; x_msk = 0ull; break; }
                     __builtin_amdgcn_s_sleep(8);
                     x_rec = ld(p_rec); x_msk = ld(p_msk);
                 }
                 if (tid < 8) s_i[8 + tid] = (int)(unsigned)x_msk;
                 const unsigned hi = __shfl_down((unsigned)x_rec, 1);            // granule 2d + half of keypoint tid >> 4
-                if (tid < KPB * 16 && (tid & 1) == 0) s_recd[tid >> 1] = as_double((unsigned)x_rec, hi);
+                if (tid < KPB * 16 && (tid & 1) == 0) s_recd[tid >> 1] = granule_double((unsigned)x_rec, hi);
             }
             if (timed_out) atomicOr(&s_i[0], 1);
             s_part[part * 32 + comp] = s0;
@@ -1934,7 +1976,7 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
             if (tid < 32) {
                 double sum = s_part[tid];
                 for (int p = 1; p < NPART; ++p) sum += s_part[p * 32 + tid];
-                if (tid < 28 && cut) {
+                if (tid < SRL_ROW_SUMS && cut) {
                     // the stop keypoint: the `allowed`-th accepted one of workgroup c
                     int need = s_i[2], pos = -1;
                     for (int w = 0; w < 8 && pos < 0; ++w) {
@@ -1945,50 +1987,30 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
                         pos = w * 32 + (int)__builtin_ctz(m);
                     }
                     if (tid == 0) s_i[3] = pos;
-                    int ia = 0, ib = 0;
-                    if (tid < 21) { int cc = tid; int rowlen = 6; while (cc >= rowlen) { cc -= rowlen; ia++; rowlen--; } ib = ia + cc; }
-                    else if (tid < 27) ia = tid - 21;
+                    const SrlRowPair p = srl_rec_pair(tid);
                     // keypoints that were not accepted published all-zero records: they add +0.0, i.e. nothing, so the walk needs no
                     // mask test and its LDS reads do not depend on anything (the same sum as srl_reduce_kernel's, which skips them)
                     double accd = 0.0;
-                    if (tid < 21) {
 #pragma unroll 8
-                        for (int k = 0; k <= pos; ++k) accd += s_recd[k * 8 + ia] * s_recd[k * 8 + ib];
-                    } else if (tid < 27) {
-#pragma unroll 8
-                        for (int k = 0; k <= pos; ++k) accd += s_recd[k * 8 + ia] * (s_recd[k * 8 + 6] * s_recd[k * 8 + 7]);
-                    } else {
-#pragma unroll 8
-                        for (int k = 0; k <= pos; ++k) accd += s_recd[k * 8 + 6] * s_recd[k * 8 + 6];
-                    }
+                    for (int k = 0; k <= pos; ++k) accd += record_term(s_recd + k * 8, tid, p);
                     sum += accd;
                 }
                 s_part[tid] = sum;
             }
             __syncthreads();
             SrlDevOut *out = reinterpret_cast<SrlDevOut *>(smem + NPART * 32 * 8 + SRL_FUSED_CUT_MAX_KPB * 64 + WPB * 8 + 64);
-            if (tid < 21) {
-                int ia = 0, cc = tid, rowlen = 6;
-                while (cc >= rowlen) { cc -= rowlen; ia++; rowlen--; }
-                const int ib = ia + cc;
-                put_f(&out->HtH[ia * 6 + ib], s_part[tid]);
-                if (ib != ia) put_f(&out->HtH[ib * 6 + ia], s_part[tid]);
-            } else if (tid < 27) {
-                put_f(&out->Hth[tid - 21], s_part[tid]);
-            } else if (tid == 27) {
-                put_f(&out->loss, s_part[27]);
-            } else if (tid == 32) {
-                const long long last_visited = cut ? (long long)c * KPB + s_i[3] : (long long)n_total - 1;
-                put_f(&out->d_num_res, cut ? (double)cut_max : s_part[28]);
-                put_f(&out->d_total_accepted, s_part[28]);
-                put_f(&out->d_sum_pk, s_part[29]);
-                put_f(&out->d_nan, (long long)s_i[4] <= last_visited ? 1.0 : 0.0);   // NaN planarity only counts for visited keypoints
-                put_f(&out->d_fallback, s_part[31]);
-                put_f(&out->d_visited, (double)(last_visited + 1));
-                put_f(&out->d_timeout, s_i[0] ? 1.0 : 0.0);
-                put_i(&out->last_visited, last_visited);
-                put_i(&out->pad, s_i[0] ? 0x7117ll : 0ll);      // time-out marker
-            }
+            const long long last_visited = cut ? (long long)c * KPB + s_i[3] : (long long)n_total - 1;
+            SrlOutTail t;
+            t.num_res = cut ? (double)cut_max : s_part[SRL_ROW_ACCEPTED];
+            t.total_accepted = s_part[SRL_ROW_ACCEPTED];
+            t.sum_pk = s_part[SRL_ROW_SUM_PK];
+            t.nan = (long long)s_i[4] <= last_visited ? 1.0 : 0.0;           // NaN planarity only counts for visited keypoints
+            t.fallback = s_part[SRL_ROW_FALLBACK];
+            t.visited = (double)(last_visited + 1);
+            t.timeout = s_i[0] ? 1.0 : 0.0;
+            t.last_visited = last_visited;
+            t.pad = s_i[0] ? SRL_ROW_TIMEOUT_MARK : 0ll;
+            write_dev_out(out, tid, s_part, t, put);
             mail_out(out);
         }
         return;
@@ -2011,32 +2033,9 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
         const bool is_last = blockIdx.x == gridDim.x - 1;
         const __amdgpu_buffer_rsrc_t rs = rows_rsrc(b.granules);
         const double *s_own = reinterpret_cast<const double *>(smem + SRL_OWN_ROW_OFFSET);          // this workgroup's own row (assoc_body)
-        double s0 = 0.0;
         bool timed_out = false;
-        for (int r0 = row_lo + part; r0 < nbk; r0 += NPART * INF) {
-            unsigned lo[INF], hi[INF];
-            unsigned spins = 0;
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int k = 0; k < INF; ++k) {
-                    const int r = r0 + NPART * k;
-                    if (r < nbk - 1) {
-                        const v4u32 x = row_load(rs, r, comp);
-                        ok = ok && x.y == epoch && x.w == epoch;
-                        lo[k] = x.x; hi[k] = x.z;
-                    } else if (r == nbk - 1) {                                 // the own row: from LDS
-                        const unsigned long long ob = (unsigned long long)__double_as_longlong(s_own[comp]);
-                        lo[k] = (unsigned)ob; hi[k] = (unsigned)(ob >> 32);
-                    } else { lo[k] = 0u; hi[k] = 0u; }
-                }
-                if (ok) break;
-                if (++spins > (1u << 18)) { timed_out = true; break; }     // ~0.3 s: something died; do not hang the GPU
-                __builtin_amdgcn_s_sleep(4);
-            }
-#pragma unroll
-            for (int k = 0; k < INF; ++k) s0 += __longlong_as_double((long long)(((unsigned long long)hi[k] << 32) | lo[k]));
-        }
+        auto every_row = [](int) { return true; };
+        const double s0 = sum_tagged_rows<NPART, INF, 4>(rs, row_lo + part, nbk, nbk - 1, comp, s_own, epoch, every_row, 0.0, timed_out);
         if (timed_out) atomicOr(s_bad, 1);
         arm_stamp(karg, 16);
         s_part[part * 32 + comp] = s0;
@@ -2049,18 +2048,10 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
                 // a group's finisher: the group's sum leaves as a super row (time-out: the row stays stale, the grid's finisher times out on it)
                 if (!*s_bad) row_store(rs, SRL_FUSED_MAX_BLOCKS + my_group, tid, epoch, sum);
             } else if (two_level) {
-                // the grid's finisher: the super rows of the groups before its own, in group order
-                for (int g = 0; g < my_group; ++g) {
-                    unsigned spins = 0;
-                    v4u32 x;
-                    for (;;) {
-                        x = row_load(rs, SRL_FUSED_MAX_BLOCKS + g, tid);
-                        if (x.y == epoch && x.w == epoch) break;
-                        if (++spins > (1u << 18)) { atomicOr(s_bad, 1); x = v4u32{0u, 0u, 0u, 0u}; break; }
-                        __builtin_amdgcn_s_sleep(4);
-                    }
-                    sum += __longlong_as_double((long long)(((unsigned long long)x.z << 32) | x.x));
-                }
+                // the grid's finisher: the super rows of the groups before its own, in group order (one at a time: at most seven)
+                bool late = false;
+                sum = sum_tagged_rows<1, 1, 4>(rs, SRL_FUSED_MAX_BLOCKS, SRL_FUSED_MAX_BLOCKS + my_group, -1, tid, nullptr, epoch, every_row, sum, late);
+                if (late) atomicOr(s_bad, 1);
             }
             s_part[tid] = sum;                                             // row 0 = the totals
         }
@@ -2076,49 +2067,37 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
                 peer_done = true;
                 if (tid < 64) {
                     double v = 0.0;
-                    if (tid < 36) {
-                        const int i0 = tid / 6, i1 = tid % 6;
-                        const int ia = i0 < i1 ? i0 : i1, ib = i0 < i1 ? i1 : i0;
-                        v = s_part[ia * 6 - (ia * (ia - 1)) / 2 + (ib - ia)];
-                    } else if (tid < 42) v = s_part[21 + (tid - 36)];
-                    else if (tid == 42) v = s_part[27];
-                    else if (tid == 43 || tid == 44) v = s_part[28];
-                    else if (tid == 45) v = s_part[29];
-                    else if (tid == 46) v = s_part[30] > 0.0 ? 1.0 : 0.0;
-                    else if (tid == 47) v = s_part[31];
+                    if (tid < 36) v = s_part[srl_row_tri_comp(tid / 6, tid % 6)];
+                    else if (tid < 42) v = s_part[SRL_ROW_HTH_V + (tid - 36)];
+                    else if (tid == 42) v = s_part[SRL_ROW_LOSS];
+                    else if (tid == 43 || tid == 44) v = s_part[SRL_ROW_ACCEPTED];
+                    else if (tid == 45) v = s_part[SRL_ROW_SUM_PK];
+                    else if (tid == 46) v = s_part[SRL_ROW_NAN] > 0.0 ? 1.0 : 0.0;
+                    else if (tid == 47) v = s_part[SRL_ROW_FALLBACK];
                     else if (tid == 48) v = (double)n_total;
                     else if (tid == 49) v = *s_bad ? 1.0 : 0.0;
                     double sum = 0.0;
                     const bool ok = peer_exchange(b.peer, b.peer_epoch, b.peer_slot, lane, SRL_REDUCED_DOUBLES, (unsigned long long)__double_as_longlong(v),
                                                   [&](int, unsigned long long w) { sum += __longlong_as_double((long long)w); });
                     double *od = reinterpret_cast<double *>(out);
-                    if (tid < SRL_REDUCED_DOUBLES) put_f(od + tid, sum);
-                    else if (tid == SRL_REDUCED_DOUBLES) put_i(&out->last_visited, (long long)n_total - 1);
-                    else if (tid == SRL_REDUCED_DOUBLES + 1) put_i(&out->pad, ok ? 0ll : SRL_PEER_TIMEOUT_MARK);
+                    if (tid < SRL_REDUCED_DOUBLES) od[tid] = sum;
+                    else if (tid == SRL_REDUCED_DOUBLES) out->last_visited = (long long)n_total - 1;
+                    else if (tid == SRL_REDUCED_DOUBLES + 1) out->pad = ok ? 0ll : SRL_PEER_TIMEOUT_MARK;
                 }
             }
         }
-        if (peer_done) {
-        } else if (tid < 21) {
-            int ia = 0, c = tid, rowlen = 6;
-            while (c >= rowlen) { c -= rowlen; ia++; rowlen--; }
-            const int ib = ia + c;
-            put_f(&out->HtH[ia * 6 + ib], s_part[tid]);
-            if (ib != ia) put_f(&out->HtH[ib * 6 + ia], s_part[tid]);
-        } else if (tid < 27) {
-            put_f(&out->Hth[tid - 21], s_part[tid]);
-        } else if (tid == 27) {
-            put_f(&out->loss, s_part[27]);
-        } else if (tid == 32) {
-            put_f(&out->d_num_res, s_part[28]);                            // no ordered cut possible here: every accepted residual counts
-            put_f(&out->d_total_accepted, s_part[28]);
-            put_f(&out->d_sum_pk, s_part[29]);
-            put_f(&out->d_nan, s_part[30] > 0.0 ? 1.0 : 0.0);              // every keypoint is visited
-            put_f(&out->d_fallback, s_part[31]);
-            put_f(&out->d_visited, (double)n_total);
-            put_f(&out->d_timeout, *s_bad ? 1.0 : 0.0);
-            put_i(&out->last_visited, (long long)n_total - 1);
-            put_i(&out->pad, *s_bad ? 0x7117ll : 0ll);          // time-out marker
+        if (!peer_done) {
+            SrlOutTail t;
+            t.num_res = s_part[SRL_ROW_ACCEPTED];                          // no ordered cut possible here: every accepted residual counts
+            t.total_accepted = s_part[SRL_ROW_ACCEPTED];
+            t.sum_pk = s_part[SRL_ROW_SUM_PK];
+            t.nan = s_part[SRL_ROW_NAN] > 0.0 ? 1.0 : 0.0;                 // every keypoint is visited
+            t.fallback = s_part[SRL_ROW_FALLBACK];
+            t.visited = (double)n_total;
+            t.timeout = *s_bad ? 1.0 : 0.0;
+            t.last_visited = (long long)n_total - 1;
+            t.pad = *s_bad ? SRL_ROW_TIMEOUT_MARK : 0ll;
+            write_dev_out(out, tid, s_part, t, put);
         }
         arm_stamp(karg, 19);
         mail_out(out);                                                     // every writer of the staged record sits in wave 0
@@ -2205,7 +2184,7 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
             const unsigned hi = (unsigned)__shfl_down((unsigned)x, 1);
             // granules 2d, 2d + 1 -> pose double d (d < 21); granules 44..49 -> t_last = doubles 21..23
             if (!(lane & 1) && (lane < SRL_POSE_BOX_CTRL || (lane >= SRL_POSE_BOX_TLAST && lane < SRL_POSE_BOX_USED)))
-                s_pose[lane < SRL_POSE_BOX_CTRL ? (lane >> 1) : 21 + ((lane - SRL_POSE_BOX_TLAST) >> 1)] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | (unsigned)x));
+                s_pose[lane < SRL_POSE_BOX_CTRL ? (lane >> 1) : 21 + ((lane - SRL_POSE_BOX_TLAST) >> 1)] = granule_double((unsigned)x, hi);
             if (lane == 0) { s_ctrl[0] = (int)(code & SRL_ARM_CODE_MASK); s_ctrl[2] = (code & SRL_ARM_ALT) ? 1 : 0; }
             if (lane == SRL_POSE_BOX_N) s_ctrl[1] = (code & SRL_ARM_CODE_MASK) == SRL_ARM_GO ? (int)(unsigned)x : a.n;     // keypoints of this pass
         }
@@ -2262,7 +2241,7 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
                     constexpr int NW = (int)(sizeof(SrlDevOut) / 8);
                     unsigned long long w = 0ull;
                     if (tid == (int)(offsetof(SrlDevOut, d_timeout) / 8)) w = (unsigned long long)__double_as_longlong(1.0);
-                    if (tid == (int)(offsetof(SrlDevOut, pad) / 8)) w = 0x7117ull;
+                    if (tid == (int)(offsetof(SrlDevOut, pad) / 8)) w = (unsigned long long)SRL_ROW_TIMEOUT_MARK;
                     if (tid == (int)(offsetof(SrlDevOut, last_visited) / 8)) w = ~0ull;
                     // (system-scope stores like mail_out's: plain stores of this early-exit path were observed NOT to reach the all-reduce's read --
                     //  the record word written through, d_mail->expired above, arrived; the plain ones did not)
@@ -2283,7 +2262,7 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
         const double *s_wpart = reinterpret_cast<const double *>(smem + L.off_wpart);     // [P2W][32]
         const int *s_winfo = reinterpret_cast<const int *>(smem + L.off_winfo);           // [WPB][8]: accepted, sum_pk, 1 + first NaN keypoint, fallback, planes
         double v = 0.0;
-        if (tid < 28) {
+        if (tid < SRL_ROW_SUMS) {
             v = s_wpart[tid];
 #pragma unroll
             for (int w = 1; w < P2W_T; ++w) v += s_wpart[w * 32 + tid];
@@ -2292,7 +2271,7 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
             for (int w = 0; w < WPB; ++w) fb += s_winfo[w * 8 + 3];
             // nanf: 1 + index inside the tile of its first NaN-planarity keypoint (slots are in keypoint order), 0 = none
             for (int w = 0; w < P2W_T; ++w) { acc += s_winfo[w * 8 + 0]; pk += s_winfo[w * 8 + 1]; if (nanf == 0) nanf = s_winfo[w * 8 + 2]; }
-            v = tid == 28 ? (double)acc : (tid == 29 ? (double)(unsigned)pk : (tid == 30 ? (double)nanf : (double)fb));
+            v = tid == SRL_ROW_ACCEPTED ? (double)acc : (tid == SRL_ROW_SUM_PK ? (double)(unsigned)pk : (tid == SRL_ROW_NAN ? (double)nanf : (double)fb));
         }
         row_v = v;
     }
@@ -2320,12 +2299,13 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
     const unsigned epoch = (unsigned)b.seq;
     constexpr int KP2 = p2_keypoints_per_wave(KPB);                       // keypoints per phase-2 wave (as in phase 2)
     constexpr int P2W = (KPB + KP2 - 1) / KP2;
+    // the grid's last workgroup finishes; in a grid of more than two groups also the last workgroup of every group (two-level reduction)
+    const bool finishes = blockIdx.x == gridDim.x - 1 ||
+                          (b.cut_max == 0 && (int)gridDim.x > 2 * SRL_FUSED_GROUP && ((int)blockIdx.x % SRL_FUSED_GROUP) == SRL_FUSED_GROUP - 1);
     if (tid < 32) {
         // lane l publishes component l of the row (row_store: one 16-byte write-through store); the finishing workgroup keeps its own
         // row in LDS -- read back through memory it was the row the finisher's first poll always missed
 #if defined(__HIP_DEVICE_COMPILE__)
-        const bool finishes = blockIdx.x == gridDim.x - 1 ||
-                              (b.cut_max == 0 && (int)gridDim.x > 2 * SRL_FUSED_GROUP && ((int)blockIdx.x % SRL_FUSED_GROUP) == SRL_FUSED_GROUP - 1);
         if (finishes) reinterpret_cast<double *>(smem + SRL_OWN_ROW_OFFSET)[tid] = row_v;
         else row_store(rows_rsrc(b.granules), (int)blockIdx.x, tid, epoch, row_v);
 #endif
@@ -2347,9 +2327,7 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if constexpr (ARMED) arm_stamp((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), 6);
-    // the grid's last workgroup finishes; in a grid of more than two groups also the last workgroup of every group (two-level reduction)
-    const bool group_finisher = b.cut_max == 0 && (int)gridDim.x > 2 * SRL_FUSED_GROUP && ((int)blockIdx.x % SRL_FUSED_GROUP) == SRL_FUSED_GROUP - 1;
-    if (blockIdx.x != gridDim.x - 1 && !group_finisher) return;
+    if (!finishes) return;
     int n_total = b.n;
     if constexpr (ARMED) n_total = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(smem + L.off_pose + SRL_POSE_DOUBLES * 8)[1]);   // the count that came with the pose
     finish_rows<KPW, WPB>((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), epoch, n_total);
@@ -2527,53 +2505,36 @@ __global__ void __launch_bounds__(1024) srl_reduce_kernel(const SrlReduceArgs a,
     // results: to the host-mapped mailbox with system-scope (write-through) stores when given, else to device memory
     SrlDevOut *out = a.mailbox ? &a.mailbox->out : a.out;
     const bool to_host = a.mailbox != nullptr;
-    auto put_f = [to_host](double *p, double x) {
+    auto put = [to_host](auto *p, auto x) {
         if (to_host) __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); else *p = x;
     };
-    auto put_i = [to_host](long long *p, long long x) {
-        if (to_host) __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); else *p = x;
-    };
-    if (tid < 28) {
+    if (tid < SRL_ROW_SUMS) {
         double s = s_part[0][tid];
         for (int p = 1; p < 32; ++p) s += s_part[p][tid];
         // cut block (or the keypoints up to the stop keypoint in mode 1): re-accumulate from the records, in order
+        // (the status test: these records come from phase 2 as they are, not zeroed like the fused cut's)
         if (mode != 2 && cut_block < nb) {
-            int ia = 0, ib = 0;
-            if (tid < 21) { int c = tid; int rowlen = 6; while (c >= rowlen) { c -= rowlen; ia++; rowlen--; } ib = ia + c; }
-            else if (tid < 27) ia = tid - 21;
+            const SrlRowPair p = srl_rec_pair(tid);
             double accd = 0.0;
             for (int k = 0; k < nrows; ++k) {
                 if (s_stat[k] != 2) continue;
-                const double *r = s_rec + k * 8;
-                if (tid < 21) accd += r[ia] * r[ib];
-                else if (tid < 27) accd += r[ia] * (r[6] * r[7]);
-                else accd += r[6] * r[6];
+                accd += record_term(s_rec + k * 8, tid, p);
             }
             s += accd;
         }
-        if (tid < 21) {
-            int ia = 0, c = tid, rowlen = 6;
-            while (c >= rowlen) { c -= rowlen; ia++; rowlen--; }
-            const int ib = ia + c;
-            put_f(&out->HtH[ia * 6 + ib], s);
-            if (ib != ia) put_f(&out->HtH[ib * 6 + ia], s);
-        } else if (tid < 27) {
-            put_f(&out->Hth[tid - 21], s);
-        } else {
-            put_f(&out->loss, s);
-        }
+        s_part[0][tid] = s;                                                  // (read back by this lane alone: row 0 = the totals)
     }
-    if (tid == 32) {
-        put_f(&out->d_num_res, (double)s_cut[3]);
-        put_f(&out->d_total_accepted, (double)s_tot[0]);
-        put_f(&out->d_sum_pk, (double)s_tot[1]);
-        put_f(&out->d_nan, (s_nan_min <= last_visited) ? 1.0 : 0.0);
-        put_f(&out->d_fallback, (double)s_tot[3]);
-        put_f(&out->d_visited, (double)(last_visited + 1));
-        put_f(&out->d_timeout, 0.0);
-        put_i(&out->last_visited, (long long)last_visited);
-        put_i(&out->pad, 0);
-    }
+    SrlOutTail t;
+    t.num_res = (double)s_cut[3];
+    t.total_accepted = (double)s_tot[0];
+    t.sum_pk = (double)s_tot[1];
+    t.nan = (s_nan_min <= last_visited) ? 1.0 : 0.0;
+    t.fallback = (double)s_tot[3];
+    t.visited = (double)(last_visited + 1);
+    t.timeout = 0.0;
+    t.last_visited = (long long)last_visited;
+    t.pad = 0;
+    write_dev_out(out, tid, s_part[0], t, put);
     if (to_host && tid < 64) {
         // every writer sits in wave 0: drain the write-through stores, then publish the sequence word
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

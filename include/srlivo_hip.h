@@ -220,8 +220,9 @@ int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_co
  * cloudFrame::getRgb(u, v, 0) = getSubPixel<cv::Vec3b> (:71-103) and rgbPoint::updateRgb(colour, distance, (15, 15, 15), obs_time)
  * (cloudMap.cpp:59-100).  The per-point colour state (rgb int16 x 3, cov_rgb FP32 x 3, observe_distance, last_observe_time, N_rgb int16:
  * cloudMap.h:51-66) lives in HBM beside the point pool, 40 bytes per stored point, allocated at the first srl_color_image_upload; zero
- * bytes are rgbPoint::reset().  selectPointsForProjection is srl_color_map_select below; the rest of the vision stage (optical flow, PnP,
- * vioEsikf, vioPhotometric, undistortion and equalisation of the image, the publishers) stays with the caller.
+ * bytes are rgbPoint::reset().  selectPointsForProjection is srl_color_map_select below, the measurement loops of vioEsikf and of
+ * vioPhotometric are srl_color_map_vio_rows; the rest of the vision stage (optical flow, PnP, undistortion and equalisation of the
+ * image, the publishers) stays with the caller.
  *
  * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
  *   p = (double) stored FP32 position; pc = R_cw p + t_cw with q_cw = q_world_camera.inverse(), R_cw = q_cw.toRotationMatrix(),
@@ -324,6 +325,63 @@ typedef struct srl_color_select_totals {
 int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, int image_rows, int image_cols, const int32_t *voxels_xyz, int n_voxels,
                          const srl_color_select_opts *opts, srl_color_selected *out /* or NULL */, int64_t capacity,
                          srl_color_select_totals *totals /* or NULL */);
+
+/* ------------------------------------------------------------------ colour voxel map: the camera ESIKF's measurement passes
+ * replaces: the per-point loops of imageProcessing::vioEsikf (imageProcessing.cpp:308-349, the reprojection update of time offset,
+ * extrinsics and intrinsics: 11 columns) and imageProcessing::vioPhotometric (:463-518, the photometric update of the extrinsics: 6
+ * columns), and the products H^T H, H^T r over them.  The 11- and 6-dimensional solves, the state update and the covariance stay on the
+ * host (csrc/host/imageProcessing.cpp, srl_lio_vio_* of srlivo_host.h); with the caller stay optical flow, PnP / RANSAC, undistortion,
+ * equalisation and updateAndAppendTrackPoints.  The points are named by pool position (srl_color_selected.pool) and visited in the
+ * caller's order -- the reference walks a
+ * std::map keyed by pointer value, whose order is not reproducible.
+ *
+ * Per point, FP64, no contraction, sums of three as (a0 + a1) + a2: p = (double) stored FP32 position, pc = R_cw p + t_cw as the render
+ * forms it; pixel = (fx pc.x / pc.z + cx, fy pc.y / pc.z + cy) + time_td * vel.  A pool position outside [0, num_points) is `unknown`,
+ * pc.z < 0.001 (the projection's own threshold) is `behind`: both are left out and counted, where the reference divides unguarded.
+ * huber(x) = 1 for x < 1, else (2 sqrt(x) - 1) / x (getHuberLoss(x, 1.0)); J_u_pc = [fx/z 0 -(fx x)/(z z); 0 fy/z -(fy y)/(z z)].
+ * REPROJECTION: d = pixel - match, residual = |d|, h = huber(residual); r = d h; H column 0 = vel h; with estimate_extrinsic columns
+ *   1-3 = (J_u_pc skew(pc)) h and 4-6 = ((-J_u_pc) R_imu_camera^T) h; with estimate_intrinsic columns 7-10 = [x/z 0 1 0; 0 y/z 0 1] h;
+ *   acc_residual += residual.
+ * PHOTOMETRIC: a point with N_rgb < 3 is `few_views` and left out (the reference's `continue`; tested in front of the projection, so a
+ *   point that is both is few_views; a map never rendered has no state: every point is few_views).  The sample is
+ *   cloudFrame::getRgb(u, v, 0, &dx, &dy) (lioOptimization.cpp:99-140) on the uploaded image: obs = getSubPixel<cv::Vec3b>(v, u), the
+ *   render's four individually rounded, saturating-added bytes; dx = (float)(sum_{b=1..4} sample(v, u + b) - sum sample(v, u - b)) / 20
+ *   with float sums of integers, dy likewise in v.  The reference reads these 17 samples with no bounds check; here a point is sampled
+ *   only if floor(u) - 4 >= 0, floor(u) + 5 <= cols - 1 and the same in v against rows, otherwise (and for a non-finite pixel) it is
+ *   `outside` and left out; nothing is clamped.  info_k = 1 / (double) cov_rgb[k]; res = obs - (double) rgb; h = huber(|res|);
+ *   r = res h; acc_residual += ((r0 i0) r0 + (r1 i1) r1) + (r2 i2) r2; J_color_pc = [dx dy] J_u_pc; with estimate_extrinsic columns
+ *   0-2 = (J_color_pc skew(pc)) h and 3-5 = ((-J_color_pc) R_imu_camera^T) h, zeros without.
+ * rows (optional): 24 doubles per input position: reprojection 2 x (11 H, r), photometric 3 x (6 H, r, info); zeros for a point left
+ * out.  outcome (optional): one byte per input position, srl_color_vio_outcome.  sums: over the used points in list order within a
+ * wave's 64 points, then the four waves of a workgroup, then the workgroups in index order -- no floating-point atomics, so two calls
+ * with the same inputs return the same bytes whether or not rows / outcome are requested: H^T H[a][b] = sum h_a h_b (photometric:
+ * sum (h_a info) h_b, in the leading 6 x 6, rest 0), a point's rows added as (row0 + row1) + row2; H^T r likewise.
+ * Synchronous: one kernel, one DMA per requested output.  n == 0: SRL_OK with zeroed sums.  Before a device is touched: NULL ctx, args,
+ * sums or (n > 0) points, n < 0, n > SRL_COLOR_VIO_MAX_POINTS, a mode that is neither, a non-finite camera, time_td or R_imu_camera:
+ * SRL_ERR_BAD_ARG; no colour map: SRL_ERR_NO_MAP; photometric mode without an uploaded image: SRL_ERR_NO_SWEEP; more than one rank:
+ * SRL_ERR_UNSUPPORTED.  Cancels an armed launch.  Nothing in the map or its colour state is changed. */
+#define SRL_COLOR_VIO_MAX_POINTS 65536
+typedef enum { SRL_VIO_REPROJECTION = 0, SRL_VIO_PHOTOMETRIC = 1 } srl_color_vio_mode;
+typedef enum { SRL_VIO_USED = 0, SRL_VIO_FEW_VIEWS = 1, SRL_VIO_BEHIND = 2, SRL_VIO_OUTSIDE = 3, SRL_VIO_UNKNOWN = 4 } srl_color_vio_outcome;
+typedef struct srl_color_vio_point {   /* 40 B */
+    int32_t pool, pad;                 /* pool position, as srl_color_selected.pool */
+    double match_u, match_v;           /* it->second of map_rgb_points_in_last_image_pose (reprojection mode only) */
+    double vel_u, vel_v;               /* rgbPoint::image_velocity */
+} srl_color_vio_point;
+typedef struct srl_color_vio_args {
+    srl_color_camera cam;              /* q_world_camera, t_world_camera, fx fy cx cy; fov_margin ignored */
+    double time_td, R_imu_camera[9];   /* row-major */
+    int32_t mode;                      /* SRL_VIO_REPROJECTION (11 columns) | SRL_VIO_PHOTOMETRIC (6 columns) */
+    int32_t estimate_extrinsic, estimate_intrinsic;
+} srl_color_vio_args;
+typedef struct srl_color_vio_sums {
+    double HtH[121];                   /* row-major, full and symmetric; photometric: Ht Rinv H in the leading 6 x 6, rest 0 */
+    double Htr[11];                    /* Ht r, photometric: Ht Rinv r */
+    double acc_residual;               /* sum of the loop's acc_residual terms, before any division */
+    int64_t used, few_views, behind, outside, unknown;
+} srl_color_vio_sums;
+int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *args, const srl_color_vio_point *points, int n,
+                           srl_color_vio_sums *sums, double *rows /* n x 24 or NULL */, uint8_t *outcome /* n or NULL */);
 
 /* ------------------------------------------------------------------ colour voxel map: the coloured cloud
  * replaces: the loops of lioOptimization::pubColorPoints (lioOptimization.cpp:1210-1241), threadPubColorPoints (:1243-1344) and

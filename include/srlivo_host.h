@@ -224,6 +224,38 @@ int srl_lio_optimize_resident(srl_lio *lio, const srl_icp_opts *opts, double sam
 int srl_lio_commit_frame(srl_lio *lio, const double state[16], double voxel_size, int max_num_points_in_voxel,
                          double min_distance_points, int min_num_points, double *world_out, int *num_added /* or NULL: see srl_frame_commit */);
 
+/* ------------------------------------------------------------------ the camera ESIKF (csrc/host/imageProcessing.{h,cpp})
+ * imageProcessing::vioEsikf (imageProcessing.cpp:220-380) and vioPhotometric (:402-552) with both updateCameraParameters, setInitialCov
+ * and the 11 x 11 covariance, on the camera state the handle keeps (csrc/host/cameraState.h).  Each iteration's per-point loop is ONE
+ * srl_color_map_vio_rows on the handle's device (srlivo_hip.h); the solve uses its sums: A = HtH + (J0 P J0^T w)^-1, K r = A^-1 Htr,
+ * K H = A^-1 HtH -- the reference forms the 11 x 2N gain K explicitly, the one algebraic difference.  Everything else is the
+ * reference's statements: the < 10 points gates, both convergence breaks, acc_residual / total_point_size, cam_measurement_weight from
+ * number_of_new_visited_voxel, the final covariance update with K H and `solution` of the last iteration (zero when the loop broke at
+ * the gate).  The tracked list is map_rgb_points_in_last_image_pose in the caller's order and n, its length, is also taken as
+ * total_point_size: the reference reads that from map_rgb_points_in_cur_image_pose.size() (:247, :413), so the two maps are assumed to
+ * have one size, as they do behind removeOutlierUsingRansacPnp.
+ * The camera state travels as 31 doubles: time_td, R_imu_camera (9, row-major), t_imu_camera (3), fx fy cx cy, q_world_camera
+ * (w x y z), t_world_camera (3), rotation (w x y z), translation (3). */
+#define SRL_LIO_CAMERA_STATE_DOUBLES 31
+int srl_lio_vio_set_options(srl_lio *lio, int num_iterations, int estimate_intrinsic, int estimate_extrinsic, const double camera_intrinsic[9],
+                            const double R_imu_camera[9], const double t_imu_camera[3]);
+int srl_lio_vio_set_camera_state(srl_lio *lio, const double *state31);
+int srl_lio_vio_get_camera_state(srl_lio *lio, double *state31);
+int srl_lio_vio_set_initial_cov(srl_lio *lio);                    /* setInitialCov (:65-72) */
+int srl_lio_vio_set_cov(srl_lio *lio, const double *cov121);      /* row-major */
+int srl_lio_vio_get_cov(srl_lio *lio, double *cov121);
+/* replaces the measurement pass (tests feed recorded sums through it); NULL puts the device's back.  Returns a srl_status. */
+typedef int (*srl_vio_rows_provider)(const srl_color_vio_args *args, const srl_color_vio_point *points, int n, srl_color_vio_sums *sums, void *user);
+int srl_lio_vio_set_rows_provider(srl_lio *lio, srl_vio_rows_provider fn, void *user);
+/* *accepted = what the reference's function returns (0: fewer than 10 tracked points, nothing done).  *iterations = the number of
+ * updateCameraParameters calls; states (optional, capacity x 31 doubles) takes the camera state behind each of the first `capacity`.
+ * *used = num_used_point_count of the last iteration.  NULL lio, accepted or (n > 0) tracked, n < 0: SRL_ERR_BAD_ARG; a host-only handle
+ * without a provider: SRL_ERR_NO_DEVICE, never a host loop; otherwise what the measurement pass returned. */
+int srl_lio_vio_esikf(srl_lio *lio, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted, int *iterations,
+                      int *used, double *states, int capacity);
+int srl_lio_vio_photometric(srl_lio *lio, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted,
+                            int *iterations, int *used, double *states, int capacity);
+
 /* lioOptimization::searchNeighbors / computeNeighborhoodDistribution single-call forms */
 int srl_lio_search_neighbors(srl_lio *lio, const double point[3], int nb_voxels_visited, double size_voxel_map,
                              int max_num_neighbors, int threshold_voxel_capacity, double *out_xyz /* K x 3 */,

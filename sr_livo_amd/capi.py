@@ -105,6 +105,32 @@ class ColorSelectTotals(C.Structure):
 COLOR_SELECTED_DTYPE = np.dtype([("index", "<i4"), ("pool", "<i4"), ("point_index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                                  ("u", "<f4"), ("v", "<f4")])
 
+
+class ColorVioArgs(C.Structure):
+    """srl_color_vio_args: the camera state one iteration of vioEsikf / vioPhotometric reads (R_imu_camera row-major)"""
+    _fields_ = [("cam", ColorCamera), ("time_td", C.c_double), ("R_imu_camera", C.c_double * 9), ("mode", C.c_int32),
+                ("estimate_extrinsic", C.c_int32), ("estimate_intrinsic", C.c_int32)]
+
+
+class ColorVioSums(C.Structure):
+    """srl_color_vio_sums: H^T H (11 x 11 row-major), H^T r, the acc_residual sum and the outcome counts of one srl_color_map_vio_rows"""
+    _fields_ = [("HtH", C.c_double * 121), ("Htr", C.c_double * 11), ("acc_residual", C.c_double), ("used", C.c_int64),
+                ("few_views", C.c_int64), ("behind", C.c_int64), ("outside", C.c_int64), ("unknown", C.c_int64)]
+
+    def counts(self):
+        return (int(self.used), int(self.few_views), int(self.behind), int(self.outside), int(self.unknown))
+
+    def as_arrays(self):
+        """(HtH (11, 11), Htr (11,), acc_residual)"""
+        return np.array(self.HtH[:]).reshape(11, 11), np.array(self.Htr[:]), float(self.acc_residual)
+
+
+SRL_VIO_REPROJECTION, SRL_VIO_PHOTOMETRIC = 0, 1
+SRL_COLOR_VIO_MAX_POINTS = 65536
+# srl_color_vio_point: list.view(COLOR_VIO_POINT_DTYPE)
+COLOR_VIO_POINT_DTYPE = np.dtype([("pool", "<i4"), ("pad", "<i4"), ("match_u", "<f8"), ("match_v", "<f8"), ("vel_u", "<f8"), ("vel_v", "<f8")])
+
+
 class ColorCloudOpts(C.Structure):
     """srl_color_cloud_opts: pub_point_minimum_views, the direction of the walk and the optional observation-time cut"""
     _fields_ = [("minimum_views", C.c_int32), ("reverse", C.c_int32), ("since", C.c_double)]
@@ -166,6 +192,9 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p)
 PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Frame), C.POINTER(IcpOpts), C.POINTER(NormalEq), C.c_void_p)
 
+VIO_ROWS_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorVioArgs), C.c_void_p, C.c_int, C.POINTER(ColorVioSums), C.c_void_p)
+CAMERA_STATE_DOUBLES = 31      # time_td, R_imu_camera (9), t_imu_camera (3), fx fy cx cy, q_world_camera (4), t_world_camera (3), rotation (4), translation (3)
+
 _lib = None
 
 
@@ -208,6 +237,7 @@ def load_library():
         "srl_color_map_select": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, C.POINTER(ColorSelectOpts), p, C.c_int64,
                                   C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_color_map_render": ([p, C.POINTER(ColorCamera), p, C.c_int, C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
+        "srl_color_map_vio_rows": ([p, C.POINTER(ColorVioArgs), p, C.c_int, C.POINTER(ColorVioSums), p, p], C.c_int),
         "srl_color_cloud_opts_default": ([C.POINTER(ColorCloudOpts)], None),
         "srl_color_map_export_cloud": ([p, C.c_int64, C.c_int64, C.POINTER(ColorCloudOpts), p, p, C.c_int64, C.POINTER(ColorCloudTotals)], C.c_int),
         "srl_color_map_download_rgb": ([p, p, p, p, p, p, C.c_int64], C.c_int),
@@ -343,6 +373,15 @@ def load_library():
         "srl_lio_neighborhood": ([p, p, C.c_int, dp, dp, dp, dp], C.c_int),
         "srl_lio_build_plane_residuals": ([p, C.POINTER(IcpOpts), p, C.c_int, dp, dp, C.c_int, p, C.c_int,
                                            C.POINTER(C.c_int), dp, C.POINTER(C.c_int), p], C.c_int),
+        "srl_lio_vio_set_options": ([p, C.c_int, C.c_int, C.c_int, p, p, p], C.c_int),
+        "srl_lio_vio_set_camera_state": ([p, p], C.c_int),
+        "srl_lio_vio_get_camera_state": ([p, p], C.c_int),
+        "srl_lio_vio_set_initial_cov": ([p], C.c_int),
+        "srl_lio_vio_set_cov": ([p, p], C.c_int),
+        "srl_lio_vio_get_cov": ([p, p], C.c_int),
+        "srl_lio_vio_set_rows_provider": ([p, VIO_ROWS_PROVIDER_FN, p], C.c_int),
+        "srl_lio_vio_esikf": ([p, p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), p, C.c_int], C.c_int),
+        "srl_lio_vio_photometric": ([p, p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), p, C.c_int], C.c_int),
         "srl_grid_sampling": ([p, C.c_int, C.c_double, p, C.POINTER(C.c_int)], C.c_int),
         "srl_debug_tr1_order": ([p, C.c_int, p], C.c_int),
         "srl_debug_tr1_order_by_relation": ([p, C.c_int, p], C.c_int),
@@ -689,6 +728,18 @@ class Context:
             self._chk(self.lib.srl_color_map_select(self.h, C.byref(camera), int(rows), int(cols), lp, len(v), C.byref(o), _ptr(out), len(out),
                                                     C.byref(tot)), "srl_color_map_select")
         return out, tot
+
+    def color_map_vio_rows(self, args, points, with_rows=True, with_outcome=True):
+        """srl_color_map_vio_rows: args = ColorVioArgs, points = COLOR_VIO_POINT_DTYPE records in the caller's order.  Returns
+        (ColorVioSums, rows (n, 24) float64 or None, outcome (n,) uint8 or None)."""
+        pts = np.ascontiguousarray(points, dtype=COLOR_VIO_POINT_DTYPE)
+        n = len(pts)
+        sums = ColorVioSums()
+        rows = np.zeros((n, 24), dtype=np.float64) if with_rows else None
+        outcome = np.zeros(n, dtype=np.uint8) if with_outcome else None
+        self._chk(self.lib.srl_color_map_vio_rows(self.h, C.byref(args), _ptr(pts) if n else None, n, C.byref(sums), _ptr(rows) if n else None,
+                                                  _ptr(outcome) if n else None), "srl_color_map_vio_rows")
+        return sums, rows, outcome
 
     def color_map_export_cloud(self, first=0, count=-1, opts=None, with_index=True, totals_only=False):
         """srl_color_map_export_cloud over rgb_points_vec[first : first + count] (count < 0: to the end); opts = ColorCloudOpts (None =
@@ -1238,6 +1289,64 @@ class Lio:
         if m.value:
             self._chk(self.lib.srl_lio_color_stored(self.h, _ptr(out), m.value, C.byref(m)), "srl_lio_color_stored")
         return out
+
+    # ---- the camera ESIKF (csrc/host/imageProcessing.cpp)
+    def vio_set_options(self, num_iterations=2, estimate_intrinsic=True, estimate_extrinsic=True, camera_intrinsic=None, R_imu_camera=None,
+                        t_imu_camera=None):
+        arr = [None if a is None else _f64(a).reshape(-1) for a in (camera_intrinsic, R_imu_camera, t_imu_camera)]
+        self._chk(self.lib.srl_lio_vio_set_options(self.h, int(num_iterations), int(bool(estimate_intrinsic)), int(bool(estimate_extrinsic)),
+                                                   *[_ptr(a) for a in arr]), "srl_lio_vio_set_options")
+
+    def vio_set_camera_state(self, state31):
+        s = _f64(state31, (CAMERA_STATE_DOUBLES,))
+        self._chk(self.lib.srl_lio_vio_set_camera_state(self.h, _ptr(s)), "srl_lio_vio_set_camera_state")
+
+    def vio_get_camera_state(self):
+        s = np.zeros(CAMERA_STATE_DOUBLES)
+        self._chk(self.lib.srl_lio_vio_get_camera_state(self.h, _ptr(s)), "srl_lio_vio_get_camera_state")
+        return s
+
+    def vio_set_initial_cov(self):
+        self._chk(self.lib.srl_lio_vio_set_initial_cov(self.h), "srl_lio_vio_set_initial_cov")
+
+    def vio_set_cov(self, cov):
+        c = _f64(cov, (11, 11))
+        self._chk(self.lib.srl_lio_vio_set_cov(self.h, _ptr(c)), "srl_lio_vio_set_cov")
+
+    def vio_get_cov(self):
+        c = np.zeros((11, 11))
+        self._chk(self.lib.srl_lio_vio_get_cov(self.h, _ptr(c)), "srl_lio_vio_get_cov")
+        return c
+
+    def vio_set_rows_provider(self, fn):
+        """fn(args: ColorVioArgs, points: COLOR_VIO_POINT_DTYPE array, sums: ColorVioSums) -> status replaces the device's measurement
+        pass; None puts it back"""
+        if fn is None:
+            self._vio_provider = None
+            self._chk(self.lib.srl_lio_vio_set_rows_provider(self.h, VIO_ROWS_PROVIDER_FN(), None), "srl_lio_vio_set_rows_provider")
+            return
+
+        def thunk(args, points, n, sums, user):
+            pts = np.frombuffer((C.c_char * (n * COLOR_VIO_POINT_DTYPE.itemsize)).from_address(points), dtype=COLOR_VIO_POINT_DTYPE) if n else \
+                np.zeros(0, COLOR_VIO_POINT_DTYPE)
+            return int(fn(args.contents, pts, sums.contents))
+        self._vio_provider = VIO_ROWS_PROVIDER_FN(thunk)
+        self._chk(self.lib.srl_lio_vio_set_rows_provider(self.h, self._vio_provider, None), "srl_lio_vio_set_rows_provider")
+
+    def _vio_update(self, fn, name, tracked, number_of_new_visited_voxel, capacity):
+        pts = np.ascontiguousarray(tracked, dtype=COLOR_VIO_POINT_DTYPE)
+        ok, it, used = C.c_int(), C.c_int(), C.c_int()
+        states = np.zeros((capacity, CAMERA_STATE_DOUBLES))
+        self._chk(fn(self.h, _ptr(pts) if len(pts) else None, len(pts), int(number_of_new_visited_voxel), C.byref(ok), C.byref(it), C.byref(used),
+                     _ptr(states), capacity), name)
+        return bool(ok.value), states[:min(it.value, capacity)], used.value
+
+    def vio_esikf(self, tracked, number_of_new_visited_voxel, capacity=16):
+        """imageProcessing::vioEsikf on the handle's camera state.  Returns (accepted, the camera state behind every iteration, used)."""
+        return self._vio_update(self.lib.srl_lio_vio_esikf, "srl_lio_vio_esikf", tracked, number_of_new_visited_voxel, capacity)
+
+    def vio_photometric(self, tracked, number_of_new_visited_voxel, capacity=16):
+        return self._vio_update(self.lib.srl_lio_vio_photometric, "srl_lio_vio_photometric", tracked, number_of_new_visited_voxel, capacity)
 
     def render_points_in_recent_voxel(self, camera, obs_time):
         """rgbMapTracker::renderPointsInRecentVoxel on voxels_recent_visited (srl_lio_render_points_in_recent_voxel); camera = ColorCamera.

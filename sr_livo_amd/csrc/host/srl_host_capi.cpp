@@ -1,6 +1,7 @@
 // srl_host_capi.cpp -- C handles (include/srlivo_host.h) onto the C++ host mirror, so that ctypes
 // harnesses drive the same lioOptimization / eskfEstimator code a C++ consumer links.
 #include "../../../include/srlivo_host.h"
+#include "imageProcessing.h"
 #include "lioOptimization.h"
 #include "tr1_order.h"
 #include "tr1_relation.h"
@@ -16,6 +17,10 @@ struct srl_lio {
     lioOptimization *lio = nullptr;
     std::string err;
     state prev_state, cur_state;
+    imageProcessing vio;                      // the camera ESIKF and the camera state it works on
+    cameraState camera;
+    srl_vio_rows_provider vio_provider = nullptr;
+    void *vio_user = nullptr;
 };
 
 namespace {
@@ -779,4 +784,75 @@ int srl_debug_tr1_order_by_relation(const int16_t *keys_xyz, int n, int32_t *ord
     return SRL_OK;
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------ the camera ESIKF
+namespace {
+void camera_state_to(const cameraState &c, double *s) {
+    s[0] = c.time_td;
+    for (int k = 0; k < 9; k++) s[1 + k] = c.R_imu_camera.a[k];
+    for (int k = 0; k < 3; k++) { s[10 + k] = c.t_imu_camera[k]; s[21 + k] = c.t_world_camera[k]; s[28 + k] = c.translation[k]; }
+    s[13] = c.fx; s[14] = c.fy; s[15] = c.cx; s[16] = c.cy;
+    s[17] = c.q_world_camera.w; s[18] = c.q_world_camera.x; s[19] = c.q_world_camera.y; s[20] = c.q_world_camera.z;
+    s[24] = c.rotation.w; s[25] = c.rotation.x; s[26] = c.rotation.y; s[27] = c.rotation.z;
+}
+void camera_state_from(const double *s, cameraState &c) {
+    c.time_td = s[0];
+    for (int k = 0; k < 9; k++) c.R_imu_camera.a[k] = s[1 + k];
+    for (int k = 0; k < 3; k++) { c.t_imu_camera[k] = s[10 + k]; c.t_world_camera[k] = s[21 + k]; c.translation[k] = s[28 + k]; }
+    c.fx = s[13]; c.fy = s[14]; c.cx = s[15]; c.cy = s[16];
+    c.q_world_camera = srl::Quat(s[17], s[18], s[19], s[20]);
+    c.rotation = srl::Quat(s[24], s[25], s[26], s[27]);
+}
+int vio_update(srl_lio *h, bool photometric, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted, int *iterations,
+               int *used, double *states, int capacity) {
+    if (accepted) *accepted = 0;
+    if (iterations) *iterations = 0;
+    if (used) *used = 0;
+    if (!h || !accepted || n < 0 || (n > 0 && !tracked) || capacity < 0 || (capacity > 0 && !states)) return SRL_ERR_BAD_ARG;
+    srl_ctx *ctx = h->lio->context();
+    if (!h->vio_provider && !ctx) { h->err = "host-only handle: no device, no measurement pass"; return SRL_ERR_NO_DEVICE; }
+    if (h->vio_provider) {
+        srl_lio *self = h;
+        h->vio.rows = [self](const srl_color_vio_args *a, const srl_color_vio_point *p, int m, srl_color_vio_sums *s) { return self->vio_provider(a, p, m, s, self->vio_user); };
+    } else {
+        h->vio.rows = [ctx](const srl_color_vio_args *a, const srl_color_vio_point *p, int m, srl_color_vio_sums *s) { return srl_color_map_vio_rows(ctx, a, p, m, s, nullptr, nullptr); };
+    }
+    const bool ok = photometric ? h->vio.vioPhotometric(h->camera, tracked, n, number_of_new_visited_voxel)
+                                : h->vio.vioEsikf(h->camera, tracked, n, number_of_new_visited_voxel);
+    if (h->vio.status != SRL_OK) { h->err = "the measurement pass of the camera ESIKF failed"; return h->vio.status; }
+    *accepted = ok ? 1 : 0;
+    if (iterations) *iterations = (int)h->vio.iterations.size();
+    if (used) *used = h->vio.last_used;
+    for (int k = 0; k < capacity && k < (int)h->vio.iterations.size(); k++) camera_state_to(h->vio.iterations[k], states + (size_t)k * SRL_LIO_CAMERA_STATE_DOUBLES);
+    return SRL_OK;
+}
+}  // namespace
+
+extern "C" {
+int srl_lio_vio_set_options(srl_lio *h, int num_iterations, int estimate_intrinsic, int estimate_extrinsic, const double camera_intrinsic[9],
+                            const double R_imu_camera[9], const double t_imu_camera[3]) {
+    if (!h || num_iterations < 0) return SRL_ERR_BAD_ARG;
+    h->vio.num_iterations = num_iterations;
+    h->vio.ifEstimateCameraIntrinsic = estimate_intrinsic != 0;
+    h->vio.ifEstimateExtrinsic = estimate_extrinsic != 0;
+    if (camera_intrinsic) for (int k = 0; k < 9; k++) h->vio.camera_intrinsic.a[k] = camera_intrinsic[k];
+    if (R_imu_camera) for (int k = 0; k < 9; k++) h->vio.R_imu_camera.a[k] = R_imu_camera[k];
+    if (t_imu_camera) for (int k = 0; k < 3; k++) h->vio.t_imu_camera[k] = t_imu_camera[k];
+    return SRL_OK;
+}
+int srl_lio_vio_set_camera_state(srl_lio *h, const double *s) { if (!h || !s) return SRL_ERR_BAD_ARG; camera_state_from(s, h->camera); return SRL_OK; }
+int srl_lio_vio_get_camera_state(srl_lio *h, double *s) { if (!h || !s) return SRL_ERR_BAD_ARG; camera_state_to(h->camera, s); return SRL_OK; }
+int srl_lio_vio_set_initial_cov(srl_lio *h) { if (!h) return SRL_ERR_BAD_ARG; h->vio.setInitialCov(); return SRL_OK; }
+int srl_lio_vio_set_cov(srl_lio *h, const double *c) { if (!h || !c) return SRL_ERR_BAD_ARG; for (int k = 0; k < 121; k++) h->vio.covariance.a[k] = c[k]; return SRL_OK; }
+int srl_lio_vio_get_cov(srl_lio *h, double *c) { if (!h || !c) return SRL_ERR_BAD_ARG; for (int k = 0; k < 121; k++) c[k] = h->vio.covariance.a[k]; return SRL_OK; }
+int srl_lio_vio_set_rows_provider(srl_lio *h, srl_vio_rows_provider fn, void *user) { if (!h) return SRL_ERR_BAD_ARG; h->vio_provider = fn; h->vio_user = user; return SRL_OK; }
+int srl_lio_vio_esikf(srl_lio *h, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted, int *iterations, int *used,
+                      double *states, int capacity) {
+    return vio_update(h, false, tracked, n, number_of_new_visited_voxel, accepted, iterations, used, states, capacity);
+}
+int srl_lio_vio_photometric(srl_lio *h, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted, int *iterations, int *used,
+                            double *states, int capacity) {
+    return vio_update(h, true, tracked, n, number_of_new_visited_voxel, accepted, iterations, used, states, capacity);
+}
 }  // extern "C"

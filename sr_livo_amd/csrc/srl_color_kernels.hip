@@ -388,6 +388,7 @@ extern "C" int srl_color_map_destroy(srl_ctx *ctx) {
     if (cm->d_grid) hipFree(cm->d_grid);
     srl_color_render_free(cm);
     srl_color_select_free(cm);
+    srl_color_vio_free(cm);
     srl_epoch_table_free(cm->scratch);
     delete cm;
     ctx->color = nullptr;

@@ -1,5 +1,6 @@
 // srl_color_map.h -- internal: the colour voxel map's device layout, shared by its construction (srl_color_kernels.hip) and its
-// consumers, the rendering pass (srl_color_render.hip) and the selection for projection (srl_color_select.hip).  DESIGN.md section 3.
+// consumers, the rendering pass (srl_color_render.hip), the selection for projection (srl_color_select.hip) and the camera ESIKF's
+// measurement passes (srl_color_vio.hip).  DESIGN.md section 3.
 #pragma once
 #include "srl_ctx.h"
 
@@ -48,6 +49,10 @@ struct SrlColorMap {
     unsigned sel_words_cap = 0;
     unsigned *d_spart = nullptr;       size_t spart_rows = 0;     // per-workgroup counter rows of k_select_cells (4 words each)
     unsigned long long *d_stot = nullptr;                         // [0..3] far, near, behind, outside of the last selection, [4] the workgroup ticket
+
+    // camera ESIKF measurement passes (srl_color_vio.hip); nothing of it exists before the first srl_color_map_vio_rows
+    unsigned long long *d_vpart = nullptr;                        // per-workgroup rows of k_vio_rows: 88 words (78 sums as FP64 bits, 5 counts)
+    unsigned long long *d_vtot = nullptr;                         // [0..87] the row of the last call, [88] the workgroup ticket
 };
 
 #if defined(__HIPCC__)
@@ -73,3 +78,5 @@ int srl_color_state_reserve(srl_ctx *ctx, SrlColorMap *cm);
 void srl_color_render_free(SrlColorMap *cm);
 // frees what the selection allocated (srl_color_map_destroy)
 void srl_color_select_free(SrlColorMap *cm);
+// frees what the measurement passes allocated (srl_color_map_destroy)
+void srl_color_vio_free(SrlColorMap *cm);

@@ -1,6 +1,6 @@
-// srl_color_project.h -- internal: what the consumers of the colour voxel map share (srl_color_render.hip, srl_color_select.hip):
-// cloudFrame::refreshPoseForProjection (src/lioOptimization.cpp:201-205) on the host, project3dPointInThisImage (:142-199) with
-// if2dPointsAvailable (:48-60) and |p - t_world_camera| on the device.  Every operation is an IEEE
+// srl_color_project.h -- internal: what the consumers of the colour voxel map share (srl_color_render.hip, srl_color_select.hip,
+// srl_color_vio.hip): cloudFrame::refreshPoseForProjection (src/lioOptimization.cpp:201-205) on the host, project3dPointInThisImage
+// (:142-199) with if2dPointsAvailable (:48-60), |p - t_world_camera| and the sub-pixel colour getSubPixel<cv::Vec3b> (:71-97) on the device.  Every operation is an IEEE
 // operation in the reference's order (-ffp-contract=off, sums of three as (a0 + a1) + a2).
 #pragma once
 #include "srl_ctx.h"
@@ -57,5 +57,26 @@ __device__ __forceinline__ int srl_color_project(const SrlCamArgs &A, double px,
 __device__ __forceinline__ double srl_color_depth(const SrlCamArgs &A, double px, double py, double pz) {
     const double dx = px - A.t_wc[0], dy = py - A.t_wc[1], dz = pz - A.t_wc[2];
     return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+// saturate_cast<uchar>(w * pixel): cvRound = round to nearest even, then the clamp (w in [0, 1]: the clamp is there for the letter)
+__device__ __forceinline__ int srl_color_sat8(double w, int pixel) {
+    const int r = (int)rint(w * (double)pixel);
+    return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+__device__ __forceinline__ int srl_color_add8(int a, int b) { const int s = a + b; return s > 255 ? 255 : s; }
+// getSubPixel<cv::Vec3b>(img, row, col, 0): per channel the saturating 8-bit sum, left to right, of four individually rounded bytes
+// (SURVEY.md App. C).  The caller keeps 0 <= floor(row) < rows and 0 <= floor(col) < cols; the neighbour past the last row / column is
+// read from the last one: the clamps only ever move a neighbour of weight 0
+__device__ __forceinline__ void srl_color_sub_pixel(const unsigned char *img, int rows, int cols, double row, double col, int out[3]) {
+    const int r0 = (int)floor(row), c0 = (int)floor(col);
+    const double fr = row - (double)r0, fc = col - (double)c0;
+    const int r1 = r0 + 1 < rows ? r0 + 1 : rows - 1, c1 = c0 + 1 < cols ? c0 + 1 : cols - 1;
+    const double w00 = (1.0 - fr) * (1.0 - fc), w10 = fr * (1.0 - fc), w01 = (1.0 - fr) * fc, w11 = fr * fc;
+    const unsigned char *q00 = img + ((size_t)r0 * cols + c0) * 3, *q10 = img + ((size_t)r1 * cols + c0) * 3;
+    const unsigned char *q01 = img + ((size_t)r0 * cols + c1) * 3, *q11 = img + ((size_t)r1 * cols + c1) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        out[k] = srl_color_add8(srl_color_add8(srl_color_add8(srl_color_sat8(w00, q00[k]), srl_color_sat8(w10, q10[k])), srl_color_sat8(w01, q01[k])),
+                                srl_color_sat8(w11, q11[k]));
 }
 #endif

@@ -53,12 +53,6 @@ __global__ void k_render_mark(const int *voxels_xyz, int n, const SrlColorSlot *
     }
 }
 
-// saturate_cast<uchar>(w * pixel): cvRound = round to nearest even, then the clamp (w in [0, 1]: the clamp is there for the letter)
-__device__ __forceinline__ int render_sat8(double w, int pixel) {
-    const int r = (int)rint(w * (double)pixel);
-    return r < 0 ? 0 : (r > 255 ? 255 : r);
-}
-__device__ __forceinline__ int render_add8(int a, int b) { const int s = a + b; return s > 255 ? 255 : s; }
 // (short) of a double as the reference's x86-64 build does it: cvttsd2si to 32 bits (the "integer indefinite" 0x80000000 outside the
 // range), low 16 bits
 __device__ __forceinline__ short render_short(double x) {
@@ -91,18 +85,10 @@ __global__ void __launch_bounds__(256) k_render_points(long long P, const SrlCol
                     c[RC_OUTSIDE] = mult;
                 } else {
                     const double d = srl_color_depth(A.C, px, py, pz);
-                    // the test above leaves 1 <= floor < cols (rows); the clamps only ever move a neighbour of weight 0
-                    const int r0 = (int)floor(v), c0 = (int)floor(u);
-                    const double fr = v - (double)r0, fc = u - (double)c0;
-                    const int r1 = r0 + 1 < A.rows ? r0 + 1 : A.rows - 1, c1 = c0 + 1 < A.cols ? c0 + 1 : A.cols - 1;
-                    const double w00 = (1.0 - fr) * (1.0 - fc), w10 = fr * (1.0 - fc), w01 = (1.0 - fr) * fc, w11 = fr * fc;
-                    const unsigned char *q00 = img + ((size_t)r0 * A.cols + c0) * 3, *q10 = img + ((size_t)r1 * A.cols + c0) * 3;
-                    const unsigned char *q01 = img + ((size_t)r0 * A.cols + c1) * 3, *q11 = img + ((size_t)r1 * A.cols + c1) * 3;
-                    double col[3];
-#pragma unroll
-                    for (int k = 0; k < 3; k++)
-                        col[k] = (double)render_add8(render_add8(render_add8(render_sat8(w00, q00[k]), render_sat8(w10, q10[k])), render_sat8(w01, q01[k])),
-                                                     render_sat8(w11, q11[k]));
+                    // the test above leaves 1 <= floor < cols (rows)
+                    int byte[3];
+                    srl_color_sub_pixel(img, A.rows, A.cols, v, u, byte);
+                    const double col[3] = {(double)byte[0], (double)byte[1], (double)byte[2]};
                     SrlColorState s = state[p];
                     bool changed = false;
                     for (unsigned it = 0; it < mult; ++it) {

@@ -6,12 +6,9 @@
 //
 //   k_cloud_flags   range element e is registered index first + e, or first + n - 1 - e walking down: registered entry -> pool position
 //                   -> N_rgb, and last_observe_time only where `since` can leave a point out; writes the flag word.  The two counters
-//                   (below the views, stale) are reduced per wave and per workgroup into a row of the workgroup's own, with ONE ticket
-//                   atomic per workgroup -- the render's scheme, but the row is written, fenced and ticketed by ONE thread, and a
-//                   workgroup is 1 024 threads with one element each up to 131 072 elements and eight each beyond: the ticket is an
-//                   atomic on one address at agent scope and costs about 30 ns per workgroup, one after the other; with 256-thread
-//                   workgroups of one element each and every thread fencing it was 351 of the 848 us of a 1.2 M-point call (DESIGN.md
-//                   section 4.5, "Cost of the cloud export")
+//                   (below the views, stale) leave through srl_wg_totals (srl_wg_totals.h).  A workgroup is 1 024 threads with one
+//                   element each up to 131 072 elements and eight each beyond: the ticket is an atomic on one address at agent scope
+//                   and costs about 30 ns per workgroup, one after the other ("Cost of the cloud export")
 //   k_scan_small    the flags in walk order (srl_scan: one, two or three levels); the sink gathers the kept point's 12 position bytes and
 //                   6 colour bytes and writes the record as ONE 16-byte store, and its registered index.  The two-level gather is the
 //                   sink's, not the scan's input: in the one-launch regime the scan re-reads everything in front of its tile
@@ -30,8 +27,7 @@ static_assert(sizeof(srl_color_cloud_opts) == 16 && sizeof(srl_color_cloud_total
 namespace {
 
 enum { CC_BELOW, CC_STALE, CC_N };
-#define SRL_CTOT_TICKET 2
-#define SRL_CTOT_PUBLISHED 4            // (an int behind the three 8-byte words)
+#define SRL_CTOT_PUBLISHED 4            // (an int behind the two totals and the ticket; the scan's sink writes it on every call)
 #define SRL_CTOT_BYTES 64
 #define SRL_CLOUD_ITEMS 8
 #define SRL_CLOUD_STAGE_BYTES ((size_t)1 << 20)
@@ -47,8 +43,6 @@ struct CloudWalk {
 template <int BLOCK, int ITEMS>
 __global__ void __launch_bounds__(BLOCK) k_cloud_flags(CloudWalk W, const SrlColorState *state, int minimum_views, int use_since, double since, int *flags,
                                                        unsigned long long *cpart, unsigned long long *ctot) {
-    __shared__ unsigned s_part[BLOCK / 64][CC_N];
-    __shared__ int s_last;
     unsigned c[CC_N] = {0, 0};
 #pragma unroll
     for (int u = 0; u < ITEMS; u++) {
@@ -68,37 +62,7 @@ __global__ void __launch_bounds__(BLOCK) k_cloud_flags(CloudWalk W, const SrlCol
             flags[e] = keep;
         }
     }
-    // the workgroup's counters: waves, then one row per workgroup, then the ticket
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < CC_N; k++) {
-        unsigned v = c[k];
-        for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_xor(v, dlt);
-        if (lane == 0) s_part[wv][k] = v;
-    }
-    __syncthreads();
-    // the workgroup's row, its fence and its ticket: one thread.  The row is ONE 8-byte agent-scope store {below, stale << 32} (it leaves
-    // the L2 of this XCD, whose lines of the row array are shared with workgroups of other XCDs), waited for before the ticket
-    if (threadIdx.x == 0) {
-        unsigned r0 = 0, r1 = 0;
-        for (int w = 0; w < BLOCK / 64; w++) { r0 += s_part[w][CC_BELOW]; r1 += s_part[w][CC_STALE]; }
-        __hip_atomic_store(&cpart[blockIdx.x], (unsigned long long)r0 | ((unsigned long long)r1 << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = atomicAdd(&ctot[SRL_CTOT_TICKET], 1ull) == (unsigned long long)gridDim.x - 1ull ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    // the last workgroup: its first wave over the rows, agent-scope loads
-    if (wv != 0) return;
-    unsigned long long below = 0, stale = 0;
-    for (unsigned b = lane; b < gridDim.x; b += 64) {
-        const unsigned long long row = __hip_atomic_load(&cpart[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        below += row & 0xFFFFFFFFull; stale += row >> 32;
-    }
-    for (int dlt = 32; dlt >= 1; dlt >>= 1) { below += __shfl_xor(below, dlt); stale += __shfl_xor(stale, dlt); }
-    if (lane == 0) { ctot[CC_BELOW] = below; ctot[CC_STALE] = stale; }
+    srl_wg_totals<CC_N, BLOCK>(c, cpart, ctot);
 }
 
 struct CloudRecordSink {
@@ -139,9 +103,8 @@ extern "C" int srl_color_map_export_cloud(srl_ctx *ctx, int64_t first, int64_t c
                                           int32_t *point_index, int64_t capacity, srl_color_cloud_totals *totals) {
     if (totals) std::memset(totals, 0, sizeof *totals);
     if (!ctx || !opts || first < 0 || capacity < 0 || std::isnan(opts->since)) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_color_need_map_one_rank(ctx); if (rc) return rc; }
     SrlColorMap *cm = ctx->color;
-    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
-    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
     if (first > cm->num_registered || (count >= 0 && count > cm->num_registered - first)) { ctx->err = "cloud: the range ends beyond the registered list"; return SRL_ERR_BAD_ARG; }
     if (count < 0) count = cm->num_registered - first;      // to the end of the list as it is now
     if (count > (int64_t)1 << 27) { ctx->err = "cloud: a range of more than 2^27 points (export it in pieces)"; return SRL_ERR_UNSUPPORTED; }
@@ -158,22 +121,20 @@ extern "C" int srl_color_map_export_cloud(srl_ctx *ctx, int64_t first, int64_t c
     const int items = n <= SRL_SCAN_SMALL_MAX ? 1 : SRL_CLOUD_ITEMS;      // elements per thread (see k_cloud_flags above)
     const unsigned nblocks = (unsigned)(((long long)n + 1024 * items - 1) / (1024 * items));
 
-    DevBuf b_tot, b_part, b_flag, b_sc, b_out, b_idx;
-    HIPCHK(ctx, b_tot.alloc(ctx, SRL_CTOT_BYTES));
-    HIPCHK(ctx, b_part.alloc(ctx, (size_t)nblocks * sizeof(unsigned long long)));
+    { const int rc = srl_wg_totals_reserve(ctx, cm->cloud_tot, SRL_CTOT_BYTES / 8, CC_N, nblocks); if (rc) return rc; }
+    DevBuf b_flag, b_sc, b_out, b_idx;
     HIPCHK(ctx, b_flag.alloc(ctx, (size_t)n * sizeof(int)));
     HIPCHK(ctx, b_sc.alloc(ctx, srl_scan_scratch_ints(n) * 4));
     HIPCHK(ctx, b_out.alloc(ctx, (size_t)n * sizeof(srl_color_cloud_point)));
     if (want_index) HIPCHK(ctx, b_idx.alloc(ctx, (size_t)n * sizeof(int)));
-    unsigned long long *ctot = b_tot.as<unsigned long long>();
-    int *published_d = b_tot.as<int>() + 2 * SRL_CTOT_PUBLISHED;
-    HIPCHK(ctx, hipMemsetAsync(b_tot.p, 0, SRL_CTOT_BYTES, st));          // the ticket starts at zero
+    unsigned long long *ctot = cm->cloud_tot.d_tot, *cpart = cm->cloud_tot.d_rows;
+    int *published_d = reinterpret_cast<int *>(ctot + SRL_CTOT_PUBLISHED);
     if (items == 1)
         hipLaunchKernelGGL((k_cloud_flags<1024, 1>), dim3(nblocks), dim3(1024), 0, st, W, (const SrlColorState *)cm->d_state, (int)opts->minimum_views, use_since,
-                           since, b_flag.as<int>(), b_part.as<unsigned long long>(), ctot);
+                           since, b_flag.as<int>(), cpart, ctot);
     else
         hipLaunchKernelGGL((k_cloud_flags<1024, SRL_CLOUD_ITEMS>), dim3(nblocks), dim3(1024), 0, st, W, (const SrlColorState *)cm->d_state, (int)opts->minimum_views,
-                           use_since, since, b_flag.as<int>(), b_part.as<unsigned long long>(), ctot);
+                           use_since, since, b_flag.as<int>(), cpart, ctot);
     HIPCHK(ctx, hipGetLastError());
     srl_scan(SrlIntArrayIn{b_flag.as<int>()},
              CloudRecordSink{W, cm->d_pool, cm->d_state, b_out.as<uint4>(), want_index ? b_idx.as<int>() : nullptr, published_d}, n, b_sc.as<int>(), st);
@@ -181,7 +142,7 @@ extern "C" int srl_color_map_export_cloud(srl_ctx *ctx, int64_t first, int64_t c
 
     // one wait for the totals, then one DMA of exactly `published` records (and one of as many indices)
     { const int rc = ensure_host_scratch(ctx, SRL_CTOT_BYTES); if (rc) return rc; }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, b_tot.p, SRL_CTOT_BYTES, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, ctot, SRL_CTOT_BYTES, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     unsigned long long h_tot[CC_N];
     int h_pub = 0;

@@ -388,7 +388,7 @@ extern "C" int srl_color_map_destroy(srl_ctx *ctx) {
     if (cm->d_grid) hipFree(cm->d_grid);
     srl_color_render_free(cm);
     srl_color_select_free(cm);
-    srl_color_vio_free(cm);
+    for (SrlWgTotals *t : {&cm->render_tot, &cm->select_tot, &cm->vio_tot, &cm->cloud_tot}) srl_wg_totals_free(*t);
     srl_epoch_table_free(cm->scratch);
     delete cm;
     ctx->color = nullptr;
@@ -422,9 +422,8 @@ extern "C" int srl_color_map_insert(srl_ctx *ctx, const double *world_xyz, int n
                                     srl_color_stored *stored, int stored_capacity, int32_t *visited_xyz, int visited_capacity, srl_color_totals *totals) {
     if (totals) std::memset(totals, 0, sizeof *totals);
     if (!ctx || n < 0) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_color_need_map_one_rank(ctx); if (rc) return rc; }
     SrlColorMap *cm = ctx->color;
-    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
-    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
     const bool from_frame = world_xyz == nullptr;
     if (from_frame) {
         if (ctx->frame_world_n < 0 || !ctx->d_frame_world) {

@@ -1,8 +1,12 @@
 // srl_color_map.h -- internal: the colour voxel map's device layout, shared by its construction (srl_color_kernels.hip) and its
-// consumers, the rendering pass (srl_color_render.hip), the selection for projection (srl_color_select.hip) and the camera ESIKF's
-// measurement passes (srl_color_vio.hip).  DESIGN.md section 3.
+// consumers, the rendering pass (srl_color_render.hip), the selection for projection (srl_color_select.hip), the camera ESIKF's
+// measurement passes (srl_color_vio.hip) and the cloud export (srl_color_cloud.hip).  DESIGN.md section 3.
+// The inline host helpers at its end call the HIP runtime (HIPCHK, DevBuf): the runtime's headers come in through srl_ctx.h.
 #pragma once
 #include "srl_ctx.h"
+#include "srl_wg_totals.h"
+
+#include <cstring>
 
 struct SrlColorVoxel { unsigned long long key; double last_visited_time; unsigned count; unsigned pad; };
 struct SrlColorPoint { float x, y, z; int voxel; int slot; int reg; };
@@ -35,10 +39,9 @@ struct SrlColorMap {
     unsigned char *h_img = nullptr;    size_t h_img_cap = 0;      // page-locked staging of the upload
     int img_rows = 0, img_cols = 0;                               // 0: no image uploaded
     hipEvent_t img_ev = nullptr;       bool img_pending = false;  // the DMA out of h_img
-    unsigned *d_rpart = nullptr;       size_t rpart_rows = 0;     // per-workgroup counter rows of k_render_points (8 words each)
-    unsigned long long *d_rtot = nullptr;                         // [0..5] totals of the last render, [6] unknown keys and [7] overflowing marks
-                                                                  // (both since allocation: never reset), [8] the workgroup ticket
-    unsigned long long unknown_seen = 0, overflow_seen = 0;       // host copies of [6] and [7] as of the previous render
+    SrlWgTotals render_tot;                                       // k_render_points: [0..5] totals of the last render, [6] the ticket, [7] unknown keys
+                                                                  // and [8] overflowing marks (both since allocation: never reset)
+    unsigned long long unknown_seen = 0, overflow_seen = 0;       // host copies of [7] and [8] as of the previous render
 
     // selection for projection (srl_color_select.hip); nothing of it exists before the first srl_color_map_select
     int *d_tail = nullptr;             unsigned tail_cap = 0;     // per voxel: pool position of its last point (slot == count - 1)
@@ -47,13 +50,40 @@ struct SrlColorMap {
     unsigned long long *d_sel_last = nullptr;                     // per slot {~call counter, ~(last index whose depth lies below the float minimum)}
     unsigned long long *d_sel_first = nullptr;                    // per slot {~call counter, first index whose depth rounds to the float minimum}
     unsigned sel_words_cap = 0;
-    unsigned *d_spart = nullptr;       size_t spart_rows = 0;     // per-workgroup counter rows of k_select_cells (4 words each)
-    unsigned long long *d_stot = nullptr;                         // [0..3] far, near, behind, outside of the last selection, [4] the workgroup ticket
+    SrlWgTotals select_tot;                                       // k_select_cells: [0..3] far, near, behind, outside of the last selection, [4] the ticket
 
     // camera ESIKF measurement passes (srl_color_vio.hip); nothing of it exists before the first srl_color_map_vio_rows
-    unsigned long long *d_vpart = nullptr;                        // per-workgroup rows of k_vio_rows: 88 words (78 sums as FP64 bits, 5 counts)
-    unsigned long long *d_vtot = nullptr;                         // [0..87] the row of the last call, [88] the workgroup ticket
+    SrlWgTotals vio_tot;                                          // k_vio_rows, rows of 88 words (78 sums as FP64 bits, 5 counts): [0..87] the row of the
+                                                                  // last call, [88] the ticket
+
+    // cloud export (srl_color_cloud.hip); nothing of it exists before the first srl_color_map_export_cloud
+    SrlWgTotals cloud_tot;                                        // k_cloud_flags: [0..1] below the views, stale, [2] the ticket, [4] an int: published
 };
+
+// the refusals every entry point of the map's consumers makes: no map, more than one rank
+inline int srl_color_need_map(srl_ctx *ctx) {
+    if (!ctx->color) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
+    return SRL_OK;
+}
+inline int srl_color_one_rank(srl_ctx *ctx) {
+    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    return SRL_OK;
+}
+inline int srl_color_need_map_one_rank(srl_ctx *ctx) {
+    const int rc = srl_color_need_map(ctx);
+    return rc ? rc : srl_color_one_rank(ctx);
+}
+
+// a caller's voxel list (n x 3 ints) into a block of the pool, through the page-locked scratch behind its first 128 bytes (where the
+// call's totals land)
+inline int srl_color_upload_list(srl_ctx *ctx, const int32_t *voxels_xyz, int n, DevBuf &b) {
+    const size_t bytes = (size_t)n * 12;
+    HIPCHK(ctx, b.alloc(ctx, bytes));
+    { const int rc = ensure_host_scratch(ctx, bytes + 128); if (rc) return rc; }
+    std::memcpy(ctx->h_scratch + 128, voxels_xyz, bytes);
+    HIPCHK(ctx, hipMemcpyAsync(b.p, ctx->h_scratch + 128, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return SRL_OK;
+}
 
 #if defined(__HIPCC__)
 #include "srl_hash.h"
@@ -78,5 +108,3 @@ int srl_color_state_reserve(srl_ctx *ctx, SrlColorMap *cm);
 void srl_color_render_free(SrlColorMap *cm);
 // frees what the selection allocated (srl_color_map_destroy)
 void srl_color_select_free(SrlColorMap *cm);
-// frees what the measurement passes allocated (srl_color_map_destroy)
-void srl_color_vio_free(SrlColorMap *cm);

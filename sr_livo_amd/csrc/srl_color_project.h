@@ -42,11 +42,16 @@ inline bool srl_color_cam_args(const srl_color_camera *cam, int rows, int cols, 
 
 #if defined(__HIPCC__)
 enum { SRL_PROJ_OK = 0, SRL_PROJ_BEHIND = 1, SRL_PROJ_OUTSIDE = 2 };
+// R_camera_world p + t_camera_world
+__device__ __forceinline__ void srl_color_to_camera(const SrlCamArgs &A, double px, double py, double pz, double *xc, double *yc, double *zc) {
+    *xc = ((A.R[0] * px + A.R[1] * py) + A.R[2] * pz) + A.t_cw[0];
+    *yc = ((A.R[3] * px + A.R[4] * py) + A.R[5] * pz) + A.t_cw[1];
+    *zc = ((A.R[6] * px + A.R[7] * py) + A.R[8] * pz) + A.t_cw[2];
+}
 // project3dPointInThisImage(p, u, v, nullptr, 1.0); u, v are written unless the point is behind the camera
 __device__ __forceinline__ int srl_color_project(const SrlCamArgs &A, double px, double py, double pz, double *u_out, double *v_out) {
-    const double xc = ((A.R[0] * px + A.R[1] * py) + A.R[2] * pz) + A.t_cw[0];
-    const double yc = ((A.R[3] * px + A.R[4] * py) + A.R[5] * pz) + A.t_cw[1];
-    const double zc = ((A.R[6] * px + A.R[7] * py) + A.R[8] * pz) + A.t_cw[2];
+    double xc, yc, zc;
+    srl_color_to_camera(A, px, py, pz, &xc, &yc, &zc);
     if (zc < 0.001) return SRL_PROJ_BEHIND;
     const double u = (xc * A.fx / zc + A.cx) * 1.0, v = (yc * A.fy / zc + A.cy) * 1.0;
     *u_out = u; *v_out = v;

@@ -7,8 +7,8 @@
 //   k_render_mark    one thread per list entry: the key is looked up in the map's voxel table and 1 is added to the voxel's mark word,
 //                    (render epoch << 16) | occurrences -- a word of another epoch IS zero occurrences, nothing is cleared per call
 //   k_render_points  one thread per POOL point: 24-byte record, 4-byte mark gather; an unmarked point leaves at once, a marked one runs
-//                    the loop body `occurrences` times and rewrites its 40-byte state record.  The six counters are reduced per workgroup
-//                    into a row of its own; ONE atomic per workgroup (a ticket) finds the last one, which adds the rows up
+//                    the loop body `occurrences` times and rewrites its 40-byte state record.  The six counters leave through
+//                    srl_wg_totals (srl_wg_totals.h)
 // The sweep is linear in the map, not in the list: it needs no per-voxel point index (the layout forbids a cap-sized one).
 //
 // OpenCV's Vec3b arithmetic decides the colour's bits: `double * Vec3b` is a Vec3b of saturate_cast<uchar>(w * pixel)
@@ -32,10 +32,9 @@ struct RenderArgs {
     int rows, cols;
 };
 enum { RC_LISTED, RC_BEHIND, RC_OUTSIDE, RC_GATED, RC_FIRST, RC_UPDATED, RC_N };
-#define SRL_RTOT_UNKNOWN 6
-#define SRL_RTOT_OVERFLOW 7
-#define SRL_RTOT_TICKET 8
-#define SRL_RTOT_WORDS 9
+#define SRL_RTOT_UNKNOWN (RC_N + 1)   // behind the ticket: the two words the mark kernel counts in, since allocation
+#define SRL_RTOT_OVERFLOW (RC_N + 2)
+#define SRL_RTOT_WORDS (RC_N + 3)
 
 __global__ void k_render_mark(const int *voxels_xyz, int n, const SrlColorSlot *vtab, unsigned vmask, unsigned *mark, unsigned epoch, unsigned long long *rtot) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,10 +60,8 @@ __device__ __forceinline__ short render_short(double x) {
 }
 
 __global__ void __launch_bounds__(256) k_render_points(long long P, const SrlColorPoint *pool, const unsigned *mark, unsigned epoch, SrlColorState *state,
-                                                       const unsigned char *img, RenderArgs A, unsigned long long overflow_before, unsigned *rpart,
+                                                       const unsigned char *img, RenderArgs A, unsigned long long overflow_before, unsigned long long *rpart,
                                                        unsigned long long *rtot) {
-    __shared__ unsigned s_part[4][RC_N];
-    __shared__ int s_last;
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     unsigned c[RC_N] = {0, 0, 0, 0, 0, 0};
     // a list that names one voxel more than 65 535 times: the mark kernel has flagged it, nothing is rendered
@@ -121,30 +118,7 @@ __global__ void __launch_bounds__(256) k_render_points(long long P, const SrlCol
             }
         }
     }
-    // the workgroup's counters: waves, then one row per workgroup, then the ticket
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < RC_N; k++) {
-        unsigned v = c[k];
-        for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_xor(v, dlt);
-        if (lane == 0) s_part[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < RC_N) rpart[(size_t)blockIdx.x * 8 + threadIdx.x] = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(&rtot[SRL_RTOT_TICKET], 1ull) == (unsigned long long)gridDim.x - 1ull ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    // the last workgroup: 32 threads per counter over the rows
-    const int k = threadIdx.x >> 5, part = threadIdx.x & 31;
-    unsigned long long sum = 0;
-    if (k < RC_N)
-        for (unsigned b = part; b < gridDim.x; b += 32) sum += __hip_atomic_load(&rpart[(size_t)b * 8 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int dlt = 16; dlt >= 1; dlt >>= 1) sum += __shfl_xor(sum, dlt);
-    if (k < RC_N && part == 0) rtot[k] = sum;
-    if (threadIdx.x == 0) rtot[SRL_RTOT_TICKET] = 0ull;
+    srl_wg_totals<RC_N, 256>(c, rpart, rtot);
 }
 
 // srl_color_registered_rgb
@@ -185,16 +159,13 @@ void srl_color_render_free(SrlColorMap *cm) {
     if (cm->d_img) hipFree(cm->d_img);
     if (cm->h_img) hipHostFree(cm->h_img);
     if (cm->img_ev) hipEventDestroy(cm->img_ev);
-    if (cm->d_rpart) hipFree(cm->d_rpart);
-    if (cm->d_rtot) hipFree(cm->d_rtot);
-    cm->d_state = nullptr; cm->d_mark = nullptr; cm->d_img = nullptr; cm->h_img = nullptr; cm->img_ev = nullptr; cm->d_rpart = nullptr; cm->d_rtot = nullptr;
+    cm->d_state = nullptr; cm->d_mark = nullptr; cm->d_img = nullptr; cm->h_img = nullptr; cm->img_ev = nullptr;
 }
 
 extern "C" int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows, int cols, int64_t row_stride_bytes) {
     if (!ctx || !bgr || rows < 2 || cols < 2 || (int64_t)rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_color_need_map_one_rank(ctx); if (rc) return rc; }
     SrlColorMap *cm = ctx->color;
-    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
-    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
     SRL_DISARM(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t row_bytes = (size_t)cols * 3, bytes = row_bytes * (size_t)rows;
@@ -231,10 +202,10 @@ extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, c
         if (!finite) { ctx->err = "render: camera and observation time must be finite"; return SRL_ERR_BAD_ARG; }
         if (!(cam->fov_margin > 0.0)) { ctx->err = "render: fov_margin must be > 0 (at 0 an integral u = cols - 1 reads one pixel past the row)"; return SRL_ERR_BAD_ARG; }
     }
+    { const int rc = srl_color_need_map(ctx); if (rc) return rc; }
     SrlColorMap *cm = ctx->color;
-    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
     if (cm->img_rows == 0) { ctx->err = "no image uploaded (srl_color_image_upload)"; return SRL_ERR_NO_SWEEP; }
-    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    { const int rc = srl_color_one_rank(ctx); if (rc) return rc; }
     if (n_voxels == 0) return SRL_OK;
     SRL_DISARM(ctx);                      // a waiting launch holds a workgroup on every compute unit
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -246,15 +217,11 @@ extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, c
     if (!srl_color_cam_args(cam, A.rows, A.cols, &A.C)) { ctx->err = "render: camera pose is not finite"; return SRL_ERR_BAD_ARG; }
     const long long P = cm->num_points;
     const unsigned nblocks = (unsigned)((P + 255) / 256);
-    if (!cm->d_rtot) {
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_rtot, SRL_RTOT_WORDS * sizeof(unsigned long long)));
-        HIPCHK(ctx, hipMemsetAsync(cm->d_rtot, 0, SRL_RTOT_WORDS * sizeof(unsigned long long), st));
-        cm->unknown_seen = 0; cm->overflow_seen = 0;
-    }
     if (cm->vtab_cap == 0) {              // a map nothing was ever inserted into: every key is unknown
         if (totals) totals->unknown = n_voxels;
         return SRL_OK;
     }
+    { const int rc = srl_wg_totals_reserve(ctx, cm->render_tot, SRL_RTOT_WORDS, RC_N, nblocks); if (rc) return rc; }
     if (cm->mark_cap < cm->vox_cap) {
         if (cm->d_mark) { HIPCHK(ctx, hipStreamSynchronize(st)); HIPCHK(ctx, hipFree(cm->d_mark)); cm->d_mark = nullptr; cm->mark_cap = 0; }
         HIPCHK(ctx, hipMalloc((void **)&cm->d_mark, (size_t)cm->vox_cap * sizeof(unsigned)));
@@ -265,30 +232,21 @@ extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, c
         cm->render_epoch = 1;
         HIPCHK(ctx, hipMemsetAsync(cm->d_mark, 0, (size_t)cm->mark_cap * sizeof(unsigned), st));
     }
-    if (nblocks > cm->rpart_rows) {
-        if (cm->d_rpart) { HIPCHK(ctx, hipStreamSynchronize(st)); HIPCHK(ctx, hipFree(cm->d_rpart)); cm->d_rpart = nullptr; cm->rpart_rows = 0; }
-        const size_t rows = (size_t)nblocks + nblocks / 2 + 64;
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_rpart, rows * 8 * sizeof(unsigned)));
-        cm->rpart_rows = rows;
-    }
     { const int rc = srl_color_state_reserve(ctx, cm); if (rc) return rc; }
     DevBuf b_list;
-    HIPCHK(ctx, b_list.alloc(ctx, (size_t)n_voxels * 12));
-    { const int rc = ensure_host_scratch(ctx, (size_t)n_voxels * 12 + 128); if (rc) return rc; }
-    std::memcpy(ctx->h_scratch + 128, voxels_xyz, (size_t)n_voxels * 12);
-    HIPCHK(ctx, hipMemcpyAsync(b_list.p, ctx->h_scratch + 128, (size_t)n_voxels * 12, hipMemcpyHostToDevice, st));
+    { const int rc = srl_color_upload_list(ctx, voxels_xyz, n_voxels, b_list); if (rc) return rc; }
     hipLaunchKernelGGL(k_render_mark, dim3((n_voxels + 255) / 256), dim3(256), 0, st, b_list.as<int>(), n_voxels, cm->d_vtab, cm->vtab_cap - 1, cm->d_mark,
-                       cm->render_epoch, cm->d_rtot);
+                       cm->render_epoch, cm->render_tot.d_tot);
     HIPCHK(ctx, hipGetLastError());
     if (nblocks > 0) {
         hipLaunchKernelGGL(k_render_points, dim3(nblocks), dim3(256), 0, st, P, cm->d_pool, cm->d_mark, cm->render_epoch, cm->d_state, cm->d_img, A,
-                           cm->overflow_seen, cm->d_rpart, cm->d_rtot);
+                           cm->overflow_seen, cm->render_tot.d_rows, cm->render_tot.d_tot);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->d_rtot, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->render_tot.d_tot, SRL_RTOT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     cm->img_pending = false;
-    unsigned long long h[8];
+    unsigned long long h[SRL_RTOT_WORDS];
     std::memcpy(h, ctx->h_scratch, sizeof h);
     const unsigned long long unknown = h[SRL_RTOT_UNKNOWN] - cm->unknown_seen, overflow = h[SRL_RTOT_OVERFLOW] - cm->overflow_seen;
     cm->unknown_seen = h[SRL_RTOT_UNKNOWN]; cm->overflow_seen = h[SRL_RTOT_OVERFLOW];

@@ -17,7 +17,7 @@
 //   k_select_cells   (a) one thread per participating candidate (i % skip_step == 0): depth, the two depth tests, the projection, the
 //                    cell key; the cell is found or claimed in an epoch-tagged table that is never cleared (srl_frame_scratch.h) and its
 //                    float minimum lowered.  The minimum only falls: the word is read first and the atomic issued only where it would
-//                    change it.  The four counters leave through one row per workgroup and ONE ticket atomic per workgroup
+//                    change it.  The four counters leave through srl_wg_totals (srl_wg_totals.h)
 //   k_select_file    (b) candidates with f(d) == M file their index: atomicMax among d < M, atomicMin among the others
 //   k_scan_small     (c) the holder flag in index order; the sink writes the records
 // The companion words are {0xFFFFFFFF - call counter, value} and only ever lowered: a word of an earlier call loses against the first
@@ -38,8 +38,6 @@ namespace {
 
 #define SRL_SEL_NONE 0xFFFFFFFFu
 enum { SC_FAR, SC_NEAR, SC_BEHIND, SC_OUTSIDE, SC_N };
-#define SRL_STOT_TICKET 4
-#define SRL_STOT_WORDS 5
 
 struct SelectArgs {
     SrlCamArgs C;
@@ -82,9 +80,7 @@ __device__ __forceinline__ int select_participating(int C, int skip) { return (i
 // (a)
 __global__ void __launch_bounds__(256) k_select_cells(const int *cand, const int *counters, int C_host, const SrlColorPoint *pool, SelectArgs A,
                                                       unsigned long long *keyw, unsigned long long *minw, unsigned mask, unsigned epoch16, unsigned tag,
-                                                      unsigned *slot_out, double *depth_out, float *uv_out, unsigned *spart, unsigned long long *stot) {
-    __shared__ unsigned s_part[4][SC_N];
-    __shared__ int s_last;
+                                                      unsigned *slot_out, double *depth_out, float *uv_out, unsigned long long *spart, unsigned long long *stot) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     const int m = select_participating(counters ? counters[0] : C_host, A.skip);
     unsigned c[SC_N] = {0, 0, 0, 0};
@@ -121,29 +117,7 @@ __global__ void __launch_bounds__(256) k_select_cells(const int *cand, const int
         }
         slot_out[j] = slot;
     }
-    // the workgroup's counters: waves, then one row per workgroup, then the ticket
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SC_N; k++) {
-        unsigned v = c[k];
-        for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_xor(v, dlt);
-        if (lane == 0) s_part[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < SC_N) spart[(size_t)blockIdx.x * 4 + threadIdx.x] = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(&stot[SRL_STOT_TICKET], 1ull) == (unsigned long long)gridDim.x - 1ull ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    // the last workgroup: 64 threads per counter over the rows
-    const int k = threadIdx.x >> 6;
-    unsigned long long sum = 0;
-    for (unsigned b = lane; b < gridDim.x; b += 64) sum += __hip_atomic_load(&spart[(size_t)b * 4 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int dlt = 32; dlt >= 1; dlt >>= 1) sum += __shfl_xor(sum, dlt);
-    if (lane == 0) stot[k] = sum;
-    if (threadIdx.x == 0) stot[SRL_STOT_TICKET] = 0ull;
+    srl_wg_totals<SC_N, 256>(c, spart, stot);
 }
 
 // (b)
@@ -236,11 +210,9 @@ void srl_color_select_free(SrlColorMap *cm) {
     if (cm->d_tail) hipFree(cm->d_tail);
     if (cm->d_sel_last) hipFree(cm->d_sel_last);
     if (cm->d_sel_first) hipFree(cm->d_sel_first);
-    if (cm->d_spart) hipFree(cm->d_spart);
-    if (cm->d_stot) hipFree(cm->d_stot);
     srl_epoch_table_free(cm->sel_cells);
-    cm->d_tail = nullptr; cm->d_sel_last = nullptr; cm->d_sel_first = nullptr; cm->d_spart = nullptr; cm->d_stot = nullptr;
-    cm->tail_cap = 0; cm->tail_swept = 0; cm->sel_words_cap = 0; cm->spart_rows = 0;
+    cm->d_tail = nullptr; cm->d_sel_last = nullptr; cm->d_sel_first = nullptr;
+    cm->tail_cap = 0; cm->tail_swept = 0; cm->sel_words_cap = 0;
 }
 
 extern "C" void srl_color_select_opts_default(srl_color_select_opts *o) {
@@ -266,9 +238,8 @@ extern "C" int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, i
     if (!(cam->fov_margin >= -4.0 && cam->fov_margin < 0.5)) { ctx->err = "select: fov_margin must lie in [-4, 0.5)"; return SRL_ERR_BAD_ARG; }
     SelectArgs A;
     if (!srl_color_cam_args(cam, image_rows, image_cols, &A.C)) { ctx->err = "select: camera pose is not finite"; return SRL_ERR_BAD_ARG; }
+    { const int rc = srl_color_need_map_one_rank(ctx); if (rc) return rc; }
     SrlColorMap *cm = ctx->color;
-    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
-    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
 
     const bool list_mode = !opts->use_all_points && n_voxels > 0;      // (!use_all_points) && boxes_recent_hitted.size() (:74)
     const int skip = opts->skip_step;
@@ -297,17 +268,8 @@ extern "C" int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, i
     const unsigned long long cells_hi = cells_d < (double)m_hi ? (unsigned long long)cells_d : (unsigned long long)m_hi;      // ... and as many records at most
     const unsigned cap2 = select_pow2(2ull * cells_hi);
 
-    if (!cm->d_stot) {
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_stot, SRL_STOT_WORDS * sizeof(unsigned long long)));
-        HIPCHK(ctx, hipMemsetAsync(cm->d_stot, 0, SRL_STOT_WORDS * sizeof(unsigned long long), st));
-    }
     const unsigned nblocks = (unsigned)((m_hi + 255) / 256);
-    if (nblocks > cm->spart_rows) {
-        if (cm->d_spart) { HIPCHK(ctx, hipStreamSynchronize(st)); HIPCHK(ctx, hipFree(cm->d_spart)); cm->d_spart = nullptr; cm->spart_rows = 0; }
-        const size_t rows = (size_t)nblocks + nblocks / 2 + 64;
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_spart, rows * 4 * sizeof(unsigned)));
-        cm->spart_rows = rows;
-    }
+    { const int rc = srl_wg_totals_reserve(ctx, cm->select_tot, SC_N + 1, SC_N, nblocks); if (rc) return rc; }
     { const int rc = srl_epoch_table_begin(ctx, cm->sel_cells, cap2, true); if (rc) return rc; }
     if (cm->sel_words_cap != cm->sel_cells.cap || cm->sel_cells.counter32 == 1) {      // the companions follow the table and the wrap of its counter (srl_epoch_table_begin has just cleared its own words)
         if (cm->sel_words_cap != cm->sel_cells.cap) {
@@ -336,12 +298,9 @@ extern "C" int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, i
     const int *d_C = nullptr;
     if (list_mode) {
         { const int rc = select_tails(ctx, cm); if (rc) return rc; }
-        HIPCHK(ctx, b_list.alloc(ctx, (size_t)n_voxels * 12));
+        { const int rc = srl_color_upload_list(ctx, voxels_xyz, n_voxels, b_list); if (rc) return rc; }
         HIPCHK(ctx, b_entry.alloc(ctx, (size_t)n_voxels * 4));
         HIPCHK(ctx, b_cand.alloc(ctx, (size_t)n_voxels * 4));
-        { const int rc = ensure_host_scratch(ctx, (size_t)n_voxels * 12 + 128); if (rc) return rc; }
-        std::memcpy(ctx->h_scratch + 128, voxels_xyz, (size_t)n_voxels * 12);
-        HIPCHK(ctx, hipMemcpyAsync(b_list.p, ctx->h_scratch + 128, (size_t)n_voxels * 12, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_select_lookup, dim3((n_voxels + 255) / 256), dim3(256), 0, st, b_list.as<int>(), n_voxels, cm->d_vtab, cm->vtab_cap - 1, cm->d_tail,
                            b_entry.as<int>());
         HIPCHK(ctx, hipGetLastError());
@@ -351,7 +310,7 @@ extern "C" int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, i
         d_C = cnt;
     }
     hipLaunchKernelGGL(k_select_cells, dim3(nblocks), dim3(256), 0, st, cand, d_C, C_hi, cm->d_pool, A, cm->sel_cells.keyw, cm->sel_cells.minw, cap2 - 1,
-                       cm->sel_cells.epoch16, tag, b_slot.as<unsigned>(), b_depth.as<double>(), b_uv.as<float>(), cm->d_spart, cm->d_stot);
+                       cm->sel_cells.epoch16, tag, b_slot.as<unsigned>(), b_depth.as<double>(), b_uv.as<float>(), cm->select_tot.d_rows, cm->select_tot.d_tot);
     hipLaunchKernelGGL(k_select_file, dim3(nblocks), dim3(256), 0, st, d_C, C_hi, skip, b_slot.as<unsigned>(), b_depth.as<double>(), cm->sel_cells.minw,
                        cm->d_sel_last, cm->d_sel_first, tag);
     HIPCHK(ctx, hipGetLastError());
@@ -361,7 +320,7 @@ extern "C" int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, i
 
     // one wait for the totals, then one DMA of exactly `selected` records
     { const int rc = ensure_host_scratch(ctx, 128); if (rc) return rc; }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->d_stot, SC_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->select_tot.d_tot, SC_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + 64, cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     unsigned long long h_tot[SC_N];

@@ -8,8 +8,9 @@
 //   k_vio_rows   one thread per listed point: its 24 doubles and its acc_residual term go into the workgroup's LDS block (256 x 25 doubles),
 //                from where they leave to `rows` in whole lines.  The 78 sums (66 of the upper triangle of H^T H, 11 of H^T r, acc_residual)
 //                are formed from that block in a fixed order: every wave walks its 64 points in list order, one sum per lane and round; the
-//                four waves are combined through LDS as (w0 + w1) + (w2 + w3); one row per workgroup; ONE atomic per workgroup (a ticket)
-//                finds the last one, which adds the rows up in index order and sets the ticket back.  No floating-point atomics.
+//                four waves are combined through LDS as (w0 + w1) + (w2 + w3); one row per workgroup and a ticket as in srl_wg_totals.h, but
+//                the kernel keeps its own epilogue: the last workgroup adds the rows up in INDEX order, one thread per word, which is
+//                what makes the FP64 sums a function of the list alone.  No floating-point atomics.
 #include "srl_ctx.h"
 #include "srl_color_map.h"
 #include "srl_color_project.h"
@@ -28,7 +29,6 @@ namespace {
 #define VIO_COUNTS 80                  // words 80 ... 84 of a row: used, few_views, behind, outside, unknown
 #define VIO_ROW_WORDS 88
 #define VIO_TICKET 88
-#define VIO_MAX_BLOCKS (SRL_COLOR_VIO_MAX_POINTS / 256)
 enum { VC_N = 5 };
 
 struct VioArgs {
@@ -69,9 +69,8 @@ __device__ __forceinline__ int vio_point(const srl_color_vio_point &q, const Srl
     }
     const SrlColorPoint pt = pool[q.pool];
     const double px = (double)pt.x, py = (double)pt.y, pz = (double)pt.z;      // getPosition(): position.cast<double>()
-    const double x = ((A.C.R[0] * px + A.C.R[1] * py) + A.C.R[2] * pz) + A.C.t_cw[0];
-    const double y = ((A.C.R[3] * px + A.C.R[4] * py) + A.C.R[5] * pz) + A.C.t_cw[1];
-    const double z = ((A.C.R[6] * px + A.C.R[7] * py) + A.C.R[8] * pz) + A.C.t_cw[2];
+    double x, y, z;
+    srl_color_to_camera(A.C, px, py, pz, &x, &y, &z);
     if (z < 0.001) return SRL_VIO_BEHIND;
     const double u = (A.C.fx * x / z + A.C.cx) + A.time_td * q.vel_u, v = (A.C.fy * y / z + A.C.cy) + A.time_td * q.vel_v;
     const double J0[3] = {A.C.fx / z, 0.0, -(A.C.fx * x) / (z * z)}, J1[3] = {0.0, A.C.fy / z, -(A.C.fy * y) / (z * z)};      // J_u_pc
@@ -167,8 +166,7 @@ __global__ void __launch_bounds__(256) k_vio_rows(const srl_color_vio_point *poi
     }
 #pragma unroll
     for (int k = 0; k < VC_N; k++) {
-        unsigned v = c[k];
-        for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_xor(v, dlt);
+        const unsigned v = srl_wave_sum(c[k]);
         if (lane == 0) s_cnt[wv][k] = v;
     }
     __syncthreads();
@@ -232,12 +230,6 @@ __global__ void __launch_bounds__(256) k_vio_rows(const srl_color_vio_point *poi
 
 }  // namespace
 
-void srl_color_vio_free(SrlColorMap *cm) {
-    if (cm->d_vpart) hipFree(cm->d_vpart);
-    if (cm->d_vtot) hipFree(cm->d_vtot);
-    cm->d_vpart = nullptr; cm->d_vtot = nullptr;
-}
-
 extern "C" int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *args, const srl_color_vio_point *points, int n, srl_color_vio_sums *sums,
                                       double *rows, uint8_t *outcome) {
     if (sums) std::memset(sums, 0, sizeof *sums);
@@ -250,11 +242,11 @@ extern "C" int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *ar
         for (int k = 0; k < 9; k++) finite = finite && std::isfinite(args->R_imu_camera[k]);
         if (!finite) { ctx->err = "vio rows: camera, time_td and R_imu_camera must be finite"; return SRL_ERR_BAD_ARG; }
     }
+    { const int rc = srl_color_need_map(ctx); if (rc) return rc; }
     SrlColorMap *cm = ctx->color;
-    if (!cm) { ctx->err = "no colour map (srl_color_map_create)"; return SRL_ERR_NO_MAP; }
     const bool photometric = args->mode == SRL_VIO_PHOTOMETRIC;
     if (photometric && cm->img_rows == 0) { ctx->err = "no image uploaded (srl_color_image_upload)"; return SRL_ERR_NO_SWEEP; }
-    if (ctx->nranks > 1) { ctx->err = "the colour map is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    { const int rc = srl_color_one_rank(ctx); if (rc) return rc; }
     VioArgs A;
     A.rows = photometric ? cm->img_rows : 0; A.cols = photometric ? cm->img_cols : 0;
     if (!srl_color_cam_args(&cam, A.rows, A.cols, &A.C)) { ctx->err = "vio rows: camera pose is not finite"; return SRL_ERR_BAD_ARG; }
@@ -269,12 +261,9 @@ extern "C" int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *ar
     A.mode = args->mode; A.estimate_extrinsic = args->estimate_extrinsic ? 1 : 0; A.estimate_intrinsic = args->estimate_intrinsic ? 1 : 0;
     A.n = n; A.P = cm->num_points;
 
-    if (!cm->d_vtot) {
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_vtot, (VIO_TICKET + 1) * sizeof(unsigned long long)));
-        HIPCHK(ctx, hipMemsetAsync(cm->d_vtot, 0, (VIO_TICKET + 1) * sizeof(unsigned long long), st));
-    }
-    if (!cm->d_vpart) HIPCHK(ctx, hipMalloc((void **)&cm->d_vpart, (size_t)VIO_MAX_BLOCKS * VIO_ROW_WORDS * sizeof(unsigned long long)));
     const unsigned nblocks = (unsigned)((n + 255) / 256);
+    // rows for the longest list at once, as before: the buffer never grows behind a synchronisation
+    { const int rc = srl_wg_totals_reserve(ctx, cm->vio_tot, VIO_TICKET + 1, VIO_ROW_WORDS, SRL_COLOR_VIO_MAX_POINTS / 256); if (rc) return rc; }
 
     // page-locked scratch: the row of sums, the list, then the outcomes and the rows
     const size_t at_points = 1024, at_outcome = at_points + (size_t)n * sizeof(srl_color_vio_point);
@@ -287,9 +276,9 @@ extern "C" int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *ar
     std::memcpy(ctx->h_scratch + at_points, points, (size_t)n * sizeof(srl_color_vio_point));
     HIPCHK(ctx, hipMemcpyAsync(b_points.p, ctx->h_scratch + at_points, (size_t)n * sizeof(srl_color_vio_point), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_vio_rows, dim3(nblocks), dim3(256), 0, st, b_points.as<srl_color_vio_point>(), cm->d_pool, cm->d_state, cm->d_img, A,
-                       rows ? b_rows.as<double>() : nullptr, outcome ? b_outcome.as<unsigned char>() : nullptr, cm->d_vpart, cm->d_vtot);
+                       rows ? b_rows.as<double>() : nullptr, outcome ? b_outcome.as<unsigned char>() : nullptr, cm->vio_tot.d_rows, cm->vio_tot.d_tot);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->d_vtot, VIO_ROW_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->vio_tot.d_tot, VIO_ROW_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     if (outcome) HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + at_outcome, b_outcome.p, (size_t)n, hipMemcpyDeviceToHost, st));
     if (rows) HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + at_rows, b_rows.p, (size_t)n * 24 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));

@@ -1,6 +1,6 @@
 """Build-time guard for the selection kernels (CPU-only: hipcc cross-compiles gfx950), in the manner of tests/test_color_render_resources.py:
 no kernel of srl_color_select.hip uses scratch; the per-candidate kernels (k_select_tails, k_select_lookup, k_select_cells, k_select_file)
-keep the register budget of eight waves per SIMD (64 VGPRs; recorded at 6 / 11 / 24 / 8) and hold no LDS beyond the counter reduction of
+keep the register budget of eight waves per SIMD (64 VGPRs; recorded at 6 / 11 / 26 / 8) and hold no LDS beyond the counter reduction of
 k_select_cells; the shared scan kernels keep theirs."""
 import os
 import re

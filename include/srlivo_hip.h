@@ -221,7 +221,7 @@ int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_co
  * (cloudMap.cpp:59-100).  The per-point colour state (rgb int16 x 3, cov_rgb FP32 x 3, observe_distance, last_observe_time, N_rgb int16:
  * cloudMap.h:51-66) lives in HBM beside the point pool, 40 bytes per stored point, allocated at the first srl_color_image_upload; zero
  * bytes are rgbPoint::reset().  selectPointsForProjection is srl_color_map_select below, the measurement loops of vioEsikf and of
- * vioPhotometric are srl_color_map_vio_rows; the rest of the vision stage (optical flow, PnP, undistortion and equalisation of the
+ * vioPhotometric are srl_color_map_vio_rows, the optical flow is srl_flow_track_image; the rest of the vision stage (PnP, undistortion and equalisation of the
  * image, the publishers) stays with the caller.
  *
  * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
@@ -330,7 +330,7 @@ int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, int image_ro
  * replaces: the per-point loops of imageProcessing::vioEsikf (imageProcessing.cpp:308-349, the reprojection update of time offset,
  * extrinsics and intrinsics: 11 columns) and imageProcessing::vioPhotometric (:463-518, the photometric update of the extrinsics: 6
  * columns), and the products H^T H, H^T r over them.  The 11- and 6-dimensional solves, the state update and the covariance stay on the
- * host (csrc/host/imageProcessing.cpp, srl_lio_vio_* of srlivo_host.h); with the caller stay optical flow, PnP / RANSAC, undistortion,
+ * host (csrc/host/imageProcessing.cpp, srl_lio_vio_* of srlivo_host.h); with the caller stay PnP / RANSAC, undistortion,
  * equalisation and updateAndAppendTrackPoints.  The points are named by pool position (srl_color_selected.pool) and visited in the
  * caller's order -- the reference walks a
  * std::map keyed by pointer value, whose order is not reproducible.
@@ -382,6 +382,40 @@ typedef struct srl_color_vio_sums {
 } srl_color_vio_sums;
 int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *args, const srl_color_vio_point *points, int n,
                            srl_color_vio_sums *sums, double *rows /* n x 24 or NULL */, uint8_t *outcome /* n or NULL */);
+
+/* ------------------------------------------------------------------ optical flow of the camera stage
+ * replaces: LKOpticalFlowKernel::trackImage (lkpyramid.cpp:755-795) as opticalFlowTracker::trackImage calls it (opticalFlowTracker.cpp:134):
+ * the 8-bit pyramid of the gray image with 21-pixel BORDER_REFLECT_101 borders (opencvBuildOpticalFlowPyramid, :510-625: level k =
+ * cv::pyrDown of level k - 1; building stops after the level whose successor would be 21 or fewer pixels wide or high, and the lowered
+ * level count holds for the tracker's life), the Scharr derivative of every level (calcSharrDeriv, :57-154, int16 (Ix, Iy), zero border)
+ * and the pyramidal Lucas-Kanade track of n points (calculateLKOpticalFlow, :174-496, one channel, err = nullptr, no initial flow)
+ * from the PREVIOUS image and ITS derivatives to the image given.  The two pyramid sets are then swapped.  next_xy and status are
+ * bitwise the reference's: its float statements in its order, its SSE accumulation order, nextPts written before the range tests,
+ * status cleared at level 0 only.  With the caller stay reduce_vector, cv::findFundamentalMat, solvePnPRansac, CLAHE, cvtColor,
+ * undistortion and the bookkeeping of opticalFlowTracker.  gray is the caller's equalised gray image, an upload of its own (it is no
+ * function of the image of srl_color_image_upload).
+ * The first image of a tracker is only stored: next_xy = prev_xy, status is not written, *n_tracked = 0.  Every later call writes
+ * next_xy (n x 2 floats, x then y) and status (n bytes) for ALL points and *n_tracked = the number of status == 1.  n == 0 is accepted
+ * (the pyramid is still built and swapped).
+ * Two departures from the reference, both on input it leaves to cvtss2si's overflow value: a point with a coordinate that is not
+ * finite, or whose window corner (coordinate - 10) does not fit int32, gets status 0 and next = prev; an image whose size differs
+ * from the tracker's first image is SRL_ERR_BAD_ARG (the reference would re-allocate one pyramid set and then assert).
+ * Synchronous.  Before a device is touched: NULL ctx or gray, rows or cols < 2 or > SRL_FLOW_MAX_EXTENT, row_stride_bytes < cols, n < 0,
+ * n > SRL_FLOW_MAX_POINTS, n > 0 with a NULL array: SRL_ERR_BAD_ARG with *n_tracked = 0; no tracker: SRL_ERR_NO_MAP.  Cancels an armed
+ * launch.  srl_flow_create: win other than 21: SRL_ERR_UNSUPPORTED (the order of the float sums is that of a 21-wide window row);
+ * max_level outside 0 ... 3, max_count outside 0 ... 100, epsilon outside [0, 10] (the ranges LKOpticalFlowKernel::setTerminationCriteria
+ * clamps to), a min_eig_threshold that is not finite, or a tracker that already exists: SRL_ERR_BAD_ARG. */
+#define SRL_FLOW_MAX_POINTS 65536
+#define SRL_FLOW_MAX_EXTENT 16384
+typedef struct srl_flow_opts {
+    int32_t win, max_level, max_count, reserved;      /* 21, 3, 10 (opticalFlowTracker.cpp:5-8) */
+    double epsilon, min_eig_threshold;                /* 0.05 (compared with |delta|^2 as it is), 1e-4 */
+} srl_flow_opts;
+void srl_flow_opts_default(srl_flow_opts *opts);
+int srl_flow_create(srl_ctx *ctx, const srl_flow_opts *opts);
+int srl_flow_destroy(srl_ctx *ctx);
+int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n,
+                         float *next_xy, uint8_t *status, int *n_tracked);
 
 /* ------------------------------------------------------------------ colour voxel map: the coloured cloud
  * replaces: the loops of lioOptimization::pubColorPoints (lioOptimization.cpp:1210-1241), threadPubColorPoints (:1243-1344) and

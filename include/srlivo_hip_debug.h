@@ -102,6 +102,13 @@ int srl_debug_device_sqrt(srl_ctx *ctx, const double *in, int n, double *out);
 /* debug (srl_debug_set_ablate(ctx, 128)): {start, end, xcc id} stamps of every workgroup of the last association launch, in ticks of
  * the 100 MHz wall clock; out = max_blocks x 3 doubles.  Used by tools/block_times.py. */
 int srl_debug_block_times(srl_ctx *ctx, double *out, int max_blocks, int *nblocks);
+/* parity tests of the optical flow (srl_flow_track_image): the level count L as lowered by the size rule, and one padded level of
+ * either pyramid set as it is AFTER the last call's swap -- SRL_FLOW_PREV: the image given last, SRL_FLOW_CUR: the one before it (zeros
+ * until a second image has been given).  image_padded: (rows + 42) x (cols + 42) bytes, deriv_padded: as many int16 pairs (Ix, Iy);
+ * either may be NULL.  *rows, *cols: the level's size.  level > L: SRL_ERR_BAD_ARG; no image yet: SRL_ERR_NO_SWEEP. */
+enum { SRL_FLOW_PREV = 0, SRL_FLOW_CUR = 1 };
+int srl_flow_levels(srl_ctx *ctx, int *L);
+int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8_t *image_padded, int16_t *deriv_padded, int *rows, int *cols);
 
 #ifdef __cplusplus
 }

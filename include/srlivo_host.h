@@ -256,6 +256,20 @@ int srl_lio_vio_esikf(srl_lio *lio, const srl_color_vio_point *tracked, int n, i
 int srl_lio_vio_photometric(srl_lio *lio, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted,
                             int *iterations, int *used, double *states, int capacity);
 
+/* class LKOpticalFlowKernel of the host mirror (csrc/host/lkpyramid.h; lkpyramid.cpp:627-795): the reference's constructor arguments
+ * (cv::Size winSize, maxLevel, cv::TermCriteria {type, maxCount, epsilon}, flags, minEigThreshold) with setTerminationCriteria's clamping
+ * (:670-682: without COUNT 30 steps, else 0 ... 100; without EPS 0.01, else 0 ... 10), and trackImage on a raw gray buffer, which is
+ * srl_flow_track_image of srlivo_hip.h on ctx with those values (the device tracker is created at the first image and owned by the
+ * handle).  ctx may be NULL: the handle then answers srl_lk_get, and srl_lk_track_image returns the C-ABI's SRL_ERR_BAD_ARG -- there is
+ * no host loop.  srl_lk_get: the level count (as lowered by the first image) and the clamped criteria; NULL outputs are skipped. */
+typedef struct srl_lk srl_lk;
+int srl_lk_create(srl_ctx *ctx, int win_width, int win_height, int max_level, int criteria_type, int max_count, double epsilon, int flags,
+                  double min_eig_threshold, srl_lk **out);
+int srl_lk_destroy(srl_lk *lk);
+int srl_lk_get(srl_lk *lk, int *max_level, int *max_count, double *epsilon);
+int srl_lk_track_image(srl_lk *lk, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n,
+                       float *next_xy, uint8_t *status, int *n_tracked);
+
 /* lioOptimization::searchNeighbors / computeNeighborhoodDistribution single-call forms */
 int srl_lio_search_neighbors(srl_lio *lio, const double point[3], int nb_voxels_visited, double size_voxel_map,
                              int max_num_neighbors, int threshold_voxel_capacity, double *out_xyz /* K x 3 */,

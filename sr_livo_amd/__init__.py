@@ -10,4 +10,5 @@ from .capi import (  # noqa: F401
     load_library, library_symbols, declared_symbols, default_opts, shard_range, shard_budget,
     grid_sampling, heap_topk, PinnedArray, comm_backend_info, comm_set_library, tr1_order,
     ColorVioArgs, ColorVioSums, COLOR_VIO_POINT_DTYPE, SRL_VIO_REPROJECTION, SRL_VIO_PHOTOMETRIC,
+    Flow, FlowOpts, default_flow_opts,
 )

@@ -131,6 +131,18 @@ SRL_COLOR_VIO_MAX_POINTS = 65536
 COLOR_VIO_POINT_DTYPE = np.dtype([("pool", "<i4"), ("pad", "<i4"), ("match_u", "<f8"), ("match_v", "<f8"), ("vel_u", "<f8"), ("vel_v", "<f8")])
 
 
+class FlowOpts(C.Structure):
+    """srl_flow_opts: the tracker's options (opticalFlowTracker.cpp:5-8); they hold for its life"""
+    _fields_ = [("win", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("reserved", C.c_int32),
+                ("epsilon", C.c_double), ("min_eig_threshold", C.c_double)]
+
+
+SRL_FLOW_MAX_POINTS = 65536
+SRL_FLOW_MAX_EXTENT = 16384
+SRL_FLOW_PREV, SRL_FLOW_CUR = 0, 1
+FLOW_BORDER = 21
+
+
 class ColorCloudOpts(C.Structure):
     """srl_color_cloud_opts: pub_point_minimum_views, the direction of the walk and the optional observation-time cut"""
     _fields_ = [("minimum_views", C.c_int32), ("reverse", C.c_int32), ("since", C.c_double)]
@@ -238,6 +250,16 @@ def load_library():
                                   C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_color_map_render": ([p, C.POINTER(ColorCamera), p, C.c_int, C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
         "srl_color_map_vio_rows": ([p, C.POINTER(ColorVioArgs), p, C.c_int, C.POINTER(ColorVioSums), p, p], C.c_int),
+        "srl_flow_opts_default": ([C.POINTER(FlowOpts)], None),
+        "srl_flow_create": ([p, C.POINTER(FlowOpts)], C.c_int),
+        "srl_flow_destroy": ([p], C.c_int),
+        "srl_flow_track_image": ([p, p, C.c_int, C.c_int, C.c_int64, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
+        "srl_flow_levels": ([p, C.POINTER(C.c_int)], C.c_int),
+        "srl_flow_download_level": ([p, C.c_int, C.c_int, p, p, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "srl_lk_create": ([p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(p)], C.c_int),
+        "srl_lk_destroy": ([p], C.c_int),
+        "srl_lk_get": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
+        "srl_lk_track_image": ([p, p, C.c_int, C.c_int, C.c_int64, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
         "srl_color_cloud_opts_default": ([C.POINTER(ColorCloudOpts)], None),
         "srl_color_map_export_cloud": ([p, C.c_int64, C.c_int64, C.POINTER(ColorCloudOpts), p, p, C.c_int64, C.POINTER(ColorCloudTotals)], C.c_int),
         "srl_color_map_download_rgb": ([p, p, p, p, p, p, C.c_int64], C.c_int),
@@ -444,6 +466,14 @@ def default_color_opts(**kw):
 def default_color_select_opts(**kw):
     o = ColorSelectOpts()
     load_library().srl_color_select_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_flow_opts(**kw):
+    o = FlowOpts()
+    load_library().srl_flow_opts_default(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -1136,6 +1166,51 @@ class Context:
             return 0
         self._cb = (ALLREDUCE_FN(_ar), ALLGATHER_FN(_ag))
         self._chk(self.lib.srl_comm_set_host_callbacks(self.h, nranks, rank, self._cb[0], self._cb[1], None), "srl_comm_set_host_callbacks")
+
+
+class Flow:
+    """The optical-flow tracker of a context (srl_flow_*): LKOpticalFlowKernel::trackImage on the device.  One per context."""
+
+    def __init__(self, ctx, opts=None, **kw):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        o = opts if opts is not None else default_flow_opts(**kw)
+        ctx._chk(self.lib.srl_flow_create(ctx.h, C.byref(o)), "srl_flow_create")
+        self.open = True
+
+    def close(self):
+        if self.open and self.ctx.h:
+            self.lib.srl_flow_destroy(self.ctx.h)
+        self.open = False
+
+    def track_image(self, gray, prev_xy):
+        """srl_flow_track_image: gray (rows, cols) uint8 (rows may be strided), prev_xy (n, 2) float32.  Returns (next_xy (n, 2) float32,
+        status (n,) uint8, n_tracked); on the tracker's first image next_xy = prev_xy, status is zeros and n_tracked 0."""
+        g = np.asarray(gray)
+        if g.dtype != np.uint8 or g.ndim != 2 or g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+            g = np.ascontiguousarray(g, dtype=np.uint8)
+        pts = np.ascontiguousarray(prev_xy, dtype=np.float32).reshape(-1, 2)
+        n = len(pts)
+        nxt = np.zeros((n, 2), dtype=np.float32)
+        status = np.zeros(n, dtype=np.uint8)
+        nt = C.c_int()
+        self.ctx._chk(self.lib.srl_flow_track_image(self.ctx.h, _ptr(g), g.shape[0], g.shape[1], g.strides[0], _ptr(pts) if n else None, n,
+                                                    _ptr(nxt) if n else None, _ptr(status) if n else None, C.byref(nt)), "srl_flow_track_image")
+        return nxt, status, nt.value
+
+    def levels(self):
+        L = C.c_int()
+        self.ctx._chk(self.lib.srl_flow_levels(self.ctx.h, C.byref(L)), "srl_flow_levels")
+        return L.value
+
+    def download_level(self, which, level):
+        """srl_flow_download_level: (padded image (rows + 42, cols + 42) uint8, padded derivative (rows + 42, cols + 42, 2) int16)"""
+        r, c = C.c_int(), C.c_int()
+        self.ctx._chk(self.lib.srl_flow_download_level(self.ctx.h, which, level, None, None, C.byref(r), C.byref(c)), "srl_flow_download_level")
+        img = np.zeros((r.value + 2 * FLOW_BORDER, c.value + 2 * FLOW_BORDER), dtype=np.uint8)
+        der = np.zeros((r.value + 2 * FLOW_BORDER, c.value + 2 * FLOW_BORDER, 2), dtype=np.int16)
+        self.ctx._chk(self.lib.srl_flow_download_level(self.ctx.h, which, level, _ptr(img), _ptr(der), C.byref(r), C.byref(c)), "srl_flow_download_level")
+        return img, der
 
 
 class Lio:

@@ -96,6 +96,7 @@ struct srl_ctx {
     int frame_world_n = -1;            // points of d_frame_world as the last srl_frame_commit left them (-1: none, or a newer frame uploaded since)
     bool frame_world_seen = false;     // a frame has been committed at some time (srl_color_map_insert tells "never" from "a newer frame since")
     struct SrlColorMap *color = nullptr;   // the colour voxel map (srl_color_kernels.hip); nullptr until srl_color_map_create
+    struct SrlFlow *flow = nullptr;        // the optical-flow tracker (srl_flow.hip); nullptr until srl_flow_create
     // undistorted sweep (srl_frame_undistort): inputs, imu_point, corrected raw_point
     double *d_corr_in = nullptr, *d_corr_rel = nullptr, *d_corr_imu = nullptr, *d_corr_raw = nullptr;
     int *d_corr_seg = nullptr;

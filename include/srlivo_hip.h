@@ -330,8 +330,8 @@ int srl_color_map_select(srl_ctx *ctx, const srl_color_camera *cam, int image_ro
  * replaces: the per-point loops of imageProcessing::vioEsikf (imageProcessing.cpp:308-349, the reprojection update of time offset,
  * extrinsics and intrinsics: 11 columns) and imageProcessing::vioPhotometric (:463-518, the photometric update of the extrinsics: 6
  * columns), and the products H^T H, H^T r over them.  The 11- and 6-dimensional solves, the state update and the covariance stay on the
- * host (csrc/host/imageProcessing.cpp, srl_lio_vio_* of srlivo_host.h); with the caller stay PnP / RANSAC, undistortion,
- * equalisation and updateAndAppendTrackPoints.  The points are named by pool position (srl_color_selected.pool) and visited in the
+ * host (csrc/host/imageProcessing.cpp, srl_lio_vio_* of srlivo_host.h); with the caller stay PnP / RANSAC, undistortion and
+ * equalisation (updateAndAppendTrackPoints is srl_color_map_track_update below).  The points are named by pool position (srl_color_selected.pool) and visited in the
  * caller's order -- the reference walks a
  * std::map keyed by pointer value, whose order is not reproducible.
  *
@@ -382,6 +382,68 @@ typedef struct srl_color_vio_sums {
 } srl_color_vio_sums;
 int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *args, const srl_color_vio_point *points, int n,
                            srl_color_vio_sums *sums, double *rows /* n x 24 or NULL */, uint8_t *outcome /* n or NULL */);
+
+/* ------------------------------------------------------------------ colour voxel map: the camera tracker's point set
+ * replaces: opticalFlowTracker::updateAndAppendTrackPoints (opticalFlowTracker.cpp:13-102) without its closing
+ * updateLastTrackingVectorAndIds, which is the host mirror's (csrc/host/opticalFlowTracker.h).  tracked = the elements of
+ * map_rgb_points_in_last_image_pose in the caller's order (the reference walks a std::map keyed by pointer value, whose order is not
+ * reproducible; nothing below depends on it), candidates = points_rgb_vec_for_projection as pool positions in its order.
+ * FP64, no contraction, sums of three as (a0 + a1) + a2; p = (double) stored FP32 position; the projection is the render's
+ * project3dPointInThisImage(p, u_d, v_d, nullptr, 1.0); cam->fov_margin is the frame's own (state.cpp:25: 0.005).
+ * FIRST LOOP (:22-61), per tracked point: max_err = 2.0 * image_cols / 320.0; error = sqrt(du du + dv dv), du = u_d - (double) u,
+ *   dv = v_d - (double) v, (u_d, v_d) as written by a projection inside OR outside the field of view.  error > max_err: the flag is
+ *   raised, and the point is DROPPED (its flag back to 0) if the flag was raised already (flagged >= 1) or error > max_err * 2, otherwise
+ *   KEPT_FLAGGED (flag = flagged + 1).  error <= max_err (or not comparable): KEPT with flag 0.  A kept point whose projection is inside
+ *   the field of view occupies the cell (int)(round(u_d / mini_distance) * mini_distance), v likewise -- the selection's statements.
+ *   The depth the reference stores in the mask is never read and not computed.
+ *   Two departures from the reference: a point BEHIND the camera (pc.z < 0.001) leaves u_d, v_d unwritten there, so its error is formed
+ *   from the previous map element's pixel (for the first element from an uninitialised variable): here it is dropped with flag 0.  A
+ *   pool position outside [0, num_points) is UNKNOWN, one that occurred earlier in `tracked` is DUPLICATE (a std::map cannot hold
+ *   either): both are dropped.
+ * SECOND LOOP (:63-99), as a rule: with T the kept points and s0 = |T|, candidate i is PROCESSED iff its pool position is known, not in
+ *   T and did not occur earlier among the candidates (a later occurrence is found in the map or refused as the first was: it is counted
+ *   ALREADY_TRACKED).  A processed candidate is a WINNER iff its projection is inside the field of view, no point of T occupies its cell
+ *   and no processed candidate with a smaller index and an inside projection has the same cell.  size() >= maximum_tracked_points is
+ *   tested behind every processed candidate and the size changes only on an add: if s0 < maximum_tracked_points the adds are the first
+ *   maximum_tracked_points - s0 winners in index order; otherwise (maximum_tracked_points <= 0 included: the reference's member is
+ *   unsigned, a negative value is taken as 0 is) the only add is the first
+ *   processed candidate, and only if it is a winner.  The loop breaks behind the last add of a filled set, or behind that first
+ *   processed candidate.  Behind the break a winner is CUT and every other candidate NOT_REACHED, whatever it would have been; in front
+ *   of it a processed candidate that is no winner is REFUSED (behind the camera or outside the field of view) or OCCUPIED.  An added
+ *   point enters with cv::Point2f(u_d, v_d) = two casts to float and flagged = 0 (the reference keeps is_out_lier_count in the rgbPoint:
+ *   the host mirror overlays the flags of points that left the set flagged).
+ * out: the kept points in input order, u, v untouched, flags updated, then the added points in candidate order.  The outcome arrays
+ * hold one byte per input position.  totals: tracked_in = n = kept + dropped + behind + unknown + duplicate, kept = s0 with `flagged`
+ * of them KEPT_FLAGGED; candidates = n_candidates = already_tracked + cand_unknown + refused + occupied + added + cut + the not reached.
+ * Synchronous: one wait for the totals (and the requested outcome bytes), then one DMA of exactly kept + added records.  out == NULL:
+ * no records.  capacity < kept + added: SRL_ERR_BAD_ARG with the totals filled and nothing copied (the call changes nothing in the map:
+ * ask again).  n == 0 and n_candidates == 0 are legal; with both zero SRL_OK and zero totals.
+ * Before a device is touched: NULL ctx, cam or opts, a NULL array with a positive count, a negative count or capacity, n >
+ * SRL_COLOR_TRACK_MAX_POINTS, n_candidates > SRL_COLOR_TRACK_MAX_CANDIDATES, mini_distance not finite or outside (0, 65536], rows or
+ * cols < 2, rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS, a non-finite camera, a margin outside [-4, 0.5): SRL_ERR_BAD_ARG; no colour map:
+ * SRL_ERR_NO_MAP; more than one rank: SRL_ERR_UNSUPPORTED.  Cancels an armed launch.  Neither map, nor the colour state, the
+ * neighbourhood bounds, the taps or the selection's buffers are touched. */
+#define SRL_COLOR_TRACK_MAX_POINTS     65536      /* tracked points in */
+#define SRL_COLOR_TRACK_MAX_CANDIDATES 1048576
+typedef enum { SRL_TRACK_KEPT = 0, SRL_TRACK_KEPT_FLAGGED = 1, SRL_TRACK_DROPPED = 2, SRL_TRACK_BEHIND = 3, SRL_TRACK_UNKNOWN = 4, SRL_TRACK_DUPLICATE = 5 } srl_color_track_outcome;
+typedef enum { SRL_TRACK_CAND_ADDED = 0, SRL_TRACK_CAND_ALREADY_TRACKED = 1, SRL_TRACK_CAND_UNKNOWN = 2, SRL_TRACK_CAND_REFUSED = 3, SRL_TRACK_CAND_OCCUPIED = 4,
+               SRL_TRACK_CAND_CUT = 5, SRL_TRACK_CAND_NOT_REACHED = 6 } srl_color_track_candidate_outcome;
+typedef struct srl_color_track_point {   /* 16 B */
+    int32_t pool;        /* pool position, as srl_color_selected.pool */
+    float   u, v;        /* it->second of map_rgb_points_in_last_image_pose (cv::Point2f) */
+    int32_t flagged;     /* rgbPoint::is_out_lier_count: only ever 0 or 1 between calls */
+} srl_color_track_point;
+typedef struct srl_color_track_opts { double mini_distance; int32_t maximum_tracked_points, reserved; } srl_color_track_opts;
+typedef struct srl_color_track_totals {
+    int64_t tracked_in, kept, flagged, dropped, behind, unknown, duplicate;          /* first loop */
+    int64_t candidates, already_tracked, cand_unknown, refused, occupied, added, cut; /* second loop */
+} srl_color_track_totals;
+/* 10.0, 300 (imageProcessing.cpp:161, opticalFlowTracker.cpp:10) */
+void srl_color_track_opts_default(srl_color_track_opts *o);
+int srl_color_map_track_update(srl_ctx *ctx, const srl_color_camera *cam, int image_rows, int image_cols,
+        const srl_color_track_point *tracked, int n, const int32_t *candidates /* pool positions, in order */, int n_candidates,
+        const srl_color_track_opts *opts, srl_color_track_point *out /* capacity, or NULL */, int64_t capacity,
+        uint8_t *tracked_outcome /* n or NULL */, uint8_t *candidate_outcome /* n_candidates or NULL */, srl_color_track_totals *totals /* or NULL */);
 
 /* ------------------------------------------------------------------ optical flow of the camera stage
  * replaces: LKOpticalFlowKernel::trackImage (lkpyramid.cpp:755-795) as opticalFlowTracker::trackImage calls it (opticalFlowTracker.cpp:134):

@@ -270,6 +270,56 @@ int srl_lk_get(srl_lk *lk, int *max_level, int *max_count, double *epsilon);
 int srl_lk_track_image(srl_lk *lk, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n,
                        float *next_xy, uint8_t *status, int *n_tracked);
 
+/* class opticalFlowTracker of the host mirror (csrc/host/opticalFlowTracker.h; opticalFlowTracker.cpp:13-323) without OpenCV: the
+ * bookkeeping between srl_color_map_select, srl_flow_track_image, srl_color_map_vio_rows and srl_color_map_track_update in the loop
+ * of imageProcessing::process (imageProcessing.cpp:137-161).  State is kept by pool position (srl_color_selected.pool); wherever the
+ * reference iterates a std::map keyed by pointer value the mirror iterates by ASCENDING POOL POSITION: last_tracked_points / old_ids,
+ * the point lists handed to the PnP provider, srl_oft_pose_map and srl_oft_tracked_for_vio.  ctx may be NULL for a handle whose flow
+ * and update go through providers.  Providers return a srl_status; NULL puts the default back:
+ *   flow         srl_flow_track_image's arguments without the context; default: the handle's LKOpticalFlowKernel on ctx (21 x 21, 3
+ *                levels, COUNT + EPS 10 / 0.05), whose first image -- srl_oft_init's -- is only stored
+ *   fundamental  the mask of the caller's cv::findFundamentalMat(last, cur, FM_RANSAC, 1.0, 0.997, status), n bytes; no default:
+ *                srl_oft_track_image with 30 or more points and none set is SRL_ERR_BAD_ARG
+ *   pnp          the inlier list of the caller's cv::solvePnPRansac (n x 3 floats, n x 2 floats -> indices); a status other than SRL_OK
+ *                stands for the cv::Exception the reference catches (*accepted = 0); no default: with 10 or more points and none set
+ *                SRL_ERR_BAD_ARG
+ *   update       srl_color_map_track_update's arguments without the context and the outcome arrays; default: that call on ctx
+ * srl_oft_init = init (:188-197) on rgb_points_vec / points_2d_vec as selection records; srl_oft_track_image = trackImage (:111-186):
+ * gray == NULL is the empty image, fewer than 30 points only move the time, *n_cur = map_rgb_points_in_cur_image_pose.size();
+ * image_rows / image_cols are the frame's (if2dPointsAvailable(x, y, 1.0, 0.05)); rejectErrorTrackingPoints is not built (the reference
+ * switches it off with distance = -20).  srl_oft_remove_outlier_using_ransac_pnp (:267-323): *accepted = its return value.
+ * srl_oft_update_and_append_track_points (:13-102): candidates = points_rgb_vec_for_projection as the selection returned it; a point
+ * that left the set flagged comes back flagged.  srl_oft_pose_map: which = 0 map_rgb_points_in_last_image_pose, 1 ..._cur_...; out
+ * may be NULL (the size alone), flagged = is_out_lier_count.  srl_oft_tracked_for_vio: the list srl_color_map_vio_rows takes. */
+typedef struct srl_oft srl_oft;
+typedef int (*srl_oft_flow_provider)(const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n, float *next_xy,
+                                     uint8_t *status, void *user);
+typedef int (*srl_oft_fundamental_provider)(const float *last_xy, const float *cur_xy, int n, uint8_t *status, void *user);
+typedef int (*srl_oft_pnp_provider)(const float *xyz, const float *uv, int n, int32_t *inliers, int *n_inliers, void *user);
+typedef int (*srl_oft_update_provider)(const srl_color_camera *cam, int image_rows, int image_cols, const srl_color_track_point *tracked, int n,
+                                       const int32_t *candidates, int n_candidates, const srl_color_track_opts *opts, srl_color_track_point *out,
+                                       int64_t capacity, srl_color_track_totals *totals, void *user);
+int srl_oft_create(srl_ctx *ctx, srl_oft **out);
+int srl_oft_destroy(srl_oft *oft);
+int srl_oft_set_maximum_tracked_points(srl_oft *oft, int maximum_tracked_points);
+int srl_oft_set_flow_provider(srl_oft *oft, srl_oft_flow_provider fn, void *user);
+int srl_oft_set_fundamental_provider(srl_oft *oft, srl_oft_fundamental_provider fn, void *user);
+int srl_oft_set_pnp_provider(srl_oft *oft, srl_oft_pnp_provider fn, void *user);
+int srl_oft_set_update_provider(srl_oft *oft, srl_oft_update_provider fn, void *user);
+int srl_oft_set_track_points(srl_oft *oft, const srl_color_selected *records, int n);
+int srl_oft_init(srl_oft *oft, const srl_color_selected *records, int n, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes,
+                 double time_sweep_end);
+int srl_oft_track_image(srl_oft *oft, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end, int image_rows,
+                        int image_cols, int *n_cur);
+int srl_oft_remove_outlier_using_ransac_pnp(srl_oft *oft, int if_remove_outlier, int *accepted);
+int srl_oft_update_and_append_track_points(srl_oft *oft, const srl_color_camera *cam, int image_rows, int image_cols,
+                                           const srl_color_selected *candidates, int n_candidates, double mini_distance,
+                                           srl_color_track_totals *totals /* or NULL */);
+int srl_oft_sizes(srl_oft *oft, int *last_pose, int *cur_pose, int *last_tracked, int *flagged);
+int srl_oft_times(srl_oft *oft, double *last_image_time, double *current_image_time);
+int srl_oft_pose_map(srl_oft *oft, int which, srl_color_track_point *out, int capacity, int *n);
+int srl_oft_tracked_for_vio(srl_oft *oft, srl_color_vio_point *out, int capacity, int *n);
+
 /* lioOptimization::searchNeighbors / computeNeighborhoodDistribution single-call forms */
 int srl_lio_search_neighbors(srl_lio *lio, const double point[3], int nb_voxels_visited, double size_voxel_map,
                              int max_num_neighbors, int threshold_voxel_capacity, double *out_xyz /* K x 3 */,

@@ -11,4 +11,5 @@ from .capi import (  # noqa: F401
     grid_sampling, heap_topk, PinnedArray, comm_backend_info, comm_set_library, tr1_order,
     ColorVioArgs, ColorVioSums, COLOR_VIO_POINT_DTYPE, SRL_VIO_REPROJECTION, SRL_VIO_PHOTOMETRIC,
     Flow, FlowOpts, default_flow_opts,
+    ColorTrackOpts, ColorTrackTotals, COLOR_TRACK_POINT_DTYPE, default_color_track_opts, Oft,
 )

@@ -106,6 +106,29 @@ COLOR_SELECTED_DTYPE = np.dtype([("index", "<i4"), ("pool", "<i4"), ("point_inde
                                  ("u", "<f4"), ("v", "<f4")])
 
 
+class ColorTrackOpts(C.Structure):
+    """srl_color_track_opts: updateAndAppendTrackPoints' mini_distance and the tracker's maximum_tracked_points"""
+    _fields_ = [("mini_distance", C.c_double), ("maximum_tracked_points", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ColorTrackTotals(C.Structure):
+    """srl_color_track_totals: what the two loops of one srl_color_map_track_update did"""
+    _fields_ = [(f, C.c_int64) for f in ("tracked_in", "kept", "flagged", "dropped", "behind", "unknown", "duplicate", "candidates",
+                                         "already_tracked", "cand_unknown", "refused", "occupied", "added", "cut")]
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, f)) for f, _ in self._fields_)
+
+
+SRL_COLOR_TRACK_MAX_POINTS, SRL_COLOR_TRACK_MAX_CANDIDATES = 65536, 1048576
+# srl_color_track_point: records.view(COLOR_TRACK_POINT_DTYPE)
+COLOR_TRACK_POINT_DTYPE = np.dtype([("pool", "<i4"), ("u", "<f4"), ("v", "<f4"), ("flagged", "<i4")])
+# srl_color_track_outcome, srl_color_track_candidate_outcome
+(SRL_TRACK_KEPT, SRL_TRACK_KEPT_FLAGGED, SRL_TRACK_DROPPED, SRL_TRACK_BEHIND, SRL_TRACK_UNKNOWN, SRL_TRACK_DUPLICATE) = range(6)
+(SRL_TRACK_CAND_ADDED, SRL_TRACK_CAND_ALREADY_TRACKED, SRL_TRACK_CAND_UNKNOWN, SRL_TRACK_CAND_REFUSED, SRL_TRACK_CAND_OCCUPIED,
+ SRL_TRACK_CAND_CUT, SRL_TRACK_CAND_NOT_REACHED) = range(7)
+
+
 class ColorVioArgs(C.Structure):
     """srl_color_vio_args: the camera state one iteration of vioEsikf / vioPhotometric reads (R_imu_camera row-major)"""
     _fields_ = [("cam", ColorCamera), ("time_td", C.c_double), ("R_imu_camera", C.c_double * 9), ("mode", C.c_int32),
@@ -204,6 +227,12 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p)
 PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Frame), C.POINTER(IcpOpts), C.POINTER(NormalEq), C.c_void_p)
 
+# srl_oft_*_provider (srlivo_host.h)
+OFT_FLOW_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
+OFT_FUNDAMENTAL_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
+OFT_PNP_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p)
+OFT_UPDATE_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorCamera), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(ColorTrackOpts),
+                                     C.c_void_p, C.c_int64, C.POINTER(ColorTrackTotals), C.c_void_p)
 VIO_ROWS_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorVioArgs), C.c_void_p, C.c_int, C.POINTER(ColorVioSums), C.c_void_p)
 CAMERA_STATE_DOUBLES = 31      # time_td, R_imu_camera (9), t_imu_camera (3), fx fy cx cy, q_world_camera (4), t_world_camera (3), rotation (4), translation (3)
 
@@ -249,6 +278,9 @@ def load_library():
         "srl_color_map_select": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, C.POINTER(ColorSelectOpts), p, C.c_int64,
                                   C.POINTER(ColorSelectTotals)], C.c_int),
         "srl_color_map_render": ([p, C.POINTER(ColorCamera), p, C.c_int, C.c_double, C.POINTER(ColorRenderTotals)], C.c_int),
+        "srl_color_track_opts_default": ([C.POINTER(ColorTrackOpts)], None),
+        "srl_color_map_track_update": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, p, C.c_int, C.POINTER(ColorTrackOpts), p, C.c_int64,
+                                        p, p, C.POINTER(ColorTrackTotals)], C.c_int),
         "srl_color_map_vio_rows": ([p, C.POINTER(ColorVioArgs), p, C.c_int, C.POINTER(ColorVioSums), p, p], C.c_int),
         "srl_flow_opts_default": ([C.POINTER(FlowOpts)], None),
         "srl_flow_create": ([p, C.POINTER(FlowOpts)], C.c_int),
@@ -256,6 +288,22 @@ def load_library():
         "srl_flow_track_image": ([p, p, C.c_int, C.c_int, C.c_int64, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
         "srl_flow_levels": ([p, C.POINTER(C.c_int)], C.c_int),
         "srl_flow_download_level": ([p, C.c_int, C.c_int, p, p, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "srl_oft_create": ([p, C.POINTER(p)], C.c_int),
+        "srl_oft_destroy": ([p], C.c_int),
+        "srl_oft_set_maximum_tracked_points": ([p, C.c_int], C.c_int),
+        "srl_oft_set_flow_provider": ([p, OFT_FLOW_PROVIDER_FN, p], C.c_int),
+        "srl_oft_set_fundamental_provider": ([p, OFT_FUNDAMENTAL_PROVIDER_FN, p], C.c_int),
+        "srl_oft_set_pnp_provider": ([p, OFT_PNP_PROVIDER_FN, p], C.c_int),
+        "srl_oft_set_update_provider": ([p, OFT_UPDATE_PROVIDER_FN, p], C.c_int),
+        "srl_oft_set_track_points": ([p, p, C.c_int], C.c_int),
+        "srl_oft_init": ([p, p, C.c_int, p, C.c_int, C.c_int, C.c_int64, C.c_double], C.c_int),
+        "srl_oft_track_image": ([p, p, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_oft_remove_outlier_using_ransac_pnp": ([p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_oft_update_and_append_track_points": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, C.c_double, C.POINTER(ColorTrackTotals)], C.c_int),
+        "srl_oft_sizes": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "srl_oft_times": ([p, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+        "srl_oft_pose_map": ([p, C.c_int, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_oft_tracked_for_vio": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lk_create": ([p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(p)], C.c_int),
         "srl_lk_destroy": ([p], C.c_int),
         "srl_lk_get": ([p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)], C.c_int),
@@ -466,6 +514,14 @@ def default_color_opts(**kw):
 def default_color_select_opts(**kw):
     o = ColorSelectOpts()
     load_library().srl_color_select_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_color_track_opts(**kw):
+    o = ColorTrackOpts()
+    load_library().srl_color_track_opts_default(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -758,6 +814,24 @@ class Context:
             self._chk(self.lib.srl_color_map_select(self.h, C.byref(camera), int(rows), int(cols), lp, len(v), C.byref(o), _ptr(out), len(out),
                                                     C.byref(tot)), "srl_color_map_select")
         return out, tot
+
+    def color_map_track_update(self, camera, rows, cols, tracked, candidates, opts=None, with_outcomes=True, totals_only=False):
+        """srl_color_map_track_update: camera = ColorCamera, tracked = COLOR_TRACK_POINT_DTYPE records in the caller's order, candidates =
+        pool positions (int32) in the order of points_rgb_vec_for_projection, opts = ColorTrackOpts (None = 10.0, 300).  Returns (records
+        (COLOR_TRACK_POINT_DTYPE): the kept points, then the added ones; tracked outcome (n,) uint8 or None; candidate outcome
+        (n_candidates,) uint8 or None; ColorTrackTotals).  One call: kept + added is at most n + min(n_candidates, max(maximum, 1))."""
+        t = np.ascontiguousarray(tracked, dtype=COLOR_TRACK_POINT_DTYPE).reshape(-1)
+        c = np.ascontiguousarray(candidates, dtype=np.int32).reshape(-1)
+        o = default_color_track_opts() if opts is None else opts
+        tot = ColorTrackTotals()
+        out = None if totals_only else np.zeros(len(t) + min(len(c), max(int(o.maximum_tracked_points), 1)), dtype=COLOR_TRACK_POINT_DTYPE)
+        t_out = np.zeros(len(t), dtype=np.uint8) if with_outcomes else None
+        c_out = np.zeros(len(c), dtype=np.uint8) if with_outcomes else None
+        self._chk(self.lib.srl_color_map_track_update(self.h, C.byref(camera), int(rows), int(cols), _ptr(t) if len(t) else None, len(t),
+                                                      _ptr(c) if len(c) else None, len(c), C.byref(o), _ptr(out) if out is not None and len(out) else None,
+                                                      0 if out is None else len(out), _ptr(t_out) if len(t) else None, _ptr(c_out) if len(c) else None,
+                                                      C.byref(tot)), "srl_color_map_track_update")
+        return (None if out is None else out[:tot.kept + tot.added].copy()), t_out, c_out, tot
 
     def color_map_vio_rows(self, args, points, with_rows=True, with_outcome=True):
         """srl_color_map_vio_rows: args = ColorVioArgs, points = COLOR_VIO_POINT_DTYPE records in the caller's order.  Returns
@@ -1211,6 +1285,141 @@ class Flow:
         der = np.zeros((r.value + 2 * FLOW_BORDER, c.value + 2 * FLOW_BORDER, 2), dtype=np.int16)
         self.ctx._chk(self.lib.srl_flow_download_level(self.ctx.h, which, level, _ptr(img), _ptr(der), C.byref(r), C.byref(c)), "srl_flow_download_level")
         return img, der
+
+
+class Oft:
+    """The host mirror's opticalFlowTracker (srl_oft_*): the bookkeeping of the camera tracker's point set by pool position.  ctx may be
+    None for a handle whose flow and update go through providers.  Providers are Python callables on numpy views of the C arrays:
+      flow(gray_address, rows, cols, stride, prev_xy (n, 2) float32, next_xy (n, 2) float32, status (n,) uint8) -> status code
+      fundamental(last_xy, cur_xy, status) -> status code          pnp(xyz (n, 3), uv (n, 2)) -> (status code, inlier indices)
+      update(camera, rows, cols, tracked, candidates, opts, out, totals) -> status code (fills out and totals)"""
+
+    def __init__(self, ctx=None):
+        self.lib = load_library()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self._keep = {}
+        rc = self.lib.srl_oft_create(ctx.h if ctx is not None else None, C.byref(self.h))
+        if rc != SRL_OK:
+            raise SrlError(rc, "srl_oft_create", "")
+
+    def close(self):
+        if self.h:
+            self.lib.srl_oft_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def _chk(self, rc, what):
+        if rc != SRL_OK:
+            raise SrlError(rc, what, (self.lib.srl_last_error(self.ctx.h) or b"").decode() if self.ctx is not None else "")
+
+    @staticmethod
+    def _view(address, count, dtype):
+        dtype = np.dtype(dtype)
+        if not count or not address:
+            return np.zeros(0, dtype)
+        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(address), dtype=dtype)
+
+    def set_maximum_tracked_points(self, m):
+        self._chk(self.lib.srl_oft_set_maximum_tracked_points(self.h, int(m)), "srl_oft_set_maximum_tracked_points")
+
+    def set_flow_provider(self, fn):
+        cb = None if fn is None else OFT_FLOW_PROVIDER_FN(
+            lambda gray, rows, cols, stride, prev, n, nxt, status, user: int(fn(gray, rows, cols, stride, self._view(prev, 2 * n, "<f4").reshape(-1, 2),
+                                                                                self._view(nxt, 2 * n, "<f4").reshape(-1, 2), self._view(status, n, np.uint8))))
+        self._keep["flow"] = cb
+        self._chk(self.lib.srl_oft_set_flow_provider(self.h, cb, None), "srl_oft_set_flow_provider")
+
+    def set_fundamental_provider(self, fn):
+        cb = None if fn is None else OFT_FUNDAMENTAL_PROVIDER_FN(
+            lambda last, cur, n, status, user: int(fn(self._view(last, 2 * n, "<f4").reshape(-1, 2), self._view(cur, 2 * n, "<f4").reshape(-1, 2),
+                                                      self._view(status, n, np.uint8))))
+        self._keep["fundamental"] = cb
+        self._chk(self.lib.srl_oft_set_fundamental_provider(self.h, cb, None), "srl_oft_set_fundamental_provider")
+
+    def set_pnp_provider(self, fn):
+        def shim(xyz, uv, n, inliers, n_inliers, user):
+            rc, idx = fn(self._view(xyz, 3 * n, "<f4").reshape(-1, 3), self._view(uv, 2 * n, "<f4").reshape(-1, 2))
+            idx = np.asarray(idx, dtype=np.int32).reshape(-1)[:n]
+            self._view(inliers, n, "<i4")[:len(idx)] = idx
+            n_inliers[0] = len(idx)
+            return int(rc)
+        cb = None if fn is None else OFT_PNP_PROVIDER_FN(shim)
+        self._keep["pnp"] = cb
+        self._chk(self.lib.srl_oft_set_pnp_provider(self.h, cb, None), "srl_oft_set_pnp_provider")
+
+    def set_update_provider(self, fn):
+        cb = None if fn is None else OFT_UPDATE_PROVIDER_FN(
+            lambda cam, rows, cols, tracked, n, cand, nc, opts, out, cap, tot, user: int(fn(
+                cam.contents, rows, cols, self._view(tracked, n, COLOR_TRACK_POINT_DTYPE), self._view(cand, nc, "<i4"), opts.contents,
+                self._view(out, cap, COLOR_TRACK_POINT_DTYPE), tot.contents)))
+        self._keep["update"] = cb
+        self._chk(self.lib.srl_oft_set_update_provider(self.h, cb, None), "srl_oft_set_update_provider")
+
+    @staticmethod
+    def _gray(gray):
+        if gray is None:
+            return None, 0, 0, 0
+        g = np.asarray(gray)
+        if g.dtype != np.uint8 or g.ndim != 2 or g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+            g = np.ascontiguousarray(g, dtype=np.uint8)
+        return g, g.shape[0], g.shape[1], g.strides[0]
+
+    def set_track_points(self, records):
+        r = np.ascontiguousarray(records, dtype=COLOR_SELECTED_DTYPE)
+        self._chk(self.lib.srl_oft_set_track_points(self.h, _ptr(r) if len(r) else None, len(r)), "srl_oft_set_track_points")
+
+    def init(self, records, gray, time_sweep_end):
+        r = np.ascontiguousarray(records, dtype=COLOR_SELECTED_DTYPE)
+        g, rows, cols, stride = self._gray(gray)
+        self._chk(self.lib.srl_oft_init(self.h, _ptr(r) if len(r) else None, len(r), _ptr(g), rows, cols, stride, float(time_sweep_end)), "srl_oft_init")
+
+    def track_image(self, gray, time_sweep_end, image_rows, image_cols):
+        """trackImage; returns map_rgb_points_in_cur_image_pose.size()"""
+        g, rows, cols, stride = self._gray(gray)
+        n = C.c_int()
+        self._chk(self.lib.srl_oft_track_image(self.h, _ptr(g), rows, cols, stride, float(time_sweep_end), int(image_rows), int(image_cols), C.byref(n)),
+                  "srl_oft_track_image")
+        return n.value
+
+    def remove_outlier_using_ransac_pnp(self, if_remove_outlier=1):
+        a = C.c_int()
+        self._chk(self.lib.srl_oft_remove_outlier_using_ransac_pnp(self.h, int(if_remove_outlier), C.byref(a)), "srl_oft_remove_outlier_using_ransac_pnp")
+        return bool(a.value)
+
+    def update_and_append_track_points(self, camera, image_rows, image_cols, candidates, mini_distance=10.0):
+        """candidates: COLOR_SELECTED_DTYPE records (points_rgb_vec_for_projection).  Returns ColorTrackTotals."""
+        c = np.ascontiguousarray(candidates, dtype=COLOR_SELECTED_DTYPE)
+        tot = ColorTrackTotals()
+        self._chk(self.lib.srl_oft_update_and_append_track_points(self.h, C.byref(camera), int(image_rows), int(image_cols), _ptr(c) if len(c) else None, len(c),
+                                                                  float(mini_distance), C.byref(tot)), "srl_oft_update_and_append_track_points")
+        return tot
+
+    def sizes(self):
+        """(map_rgb_points_in_last_image_pose, map_rgb_points_in_cur_image_pose, last_tracked_points, flagged positions)"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.lib.srl_oft_sizes(self.h, *[C.byref(x) for x in v]), "srl_oft_sizes")
+        return tuple(x.value for x in v)
+
+    def times(self):
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.lib.srl_oft_times(self.h, C.byref(a), C.byref(b)), "srl_oft_times")
+        return a.value, b.value
+
+    def pose_map(self, which=0):
+        n = C.c_int()
+        self._chk(self.lib.srl_oft_pose_map(self.h, which, None, 0, C.byref(n)), "srl_oft_pose_map")
+        out = np.zeros(n.value, dtype=COLOR_TRACK_POINT_DTYPE)
+        if n.value:
+            self._chk(self.lib.srl_oft_pose_map(self.h, which, _ptr(out), len(out), C.byref(n)), "srl_oft_pose_map")
+        return out
+
+    def tracked_for_vio(self):
+        n = C.c_int()
+        self._chk(self.lib.srl_oft_tracked_for_vio(self.h, None, 0, C.byref(n)), "srl_oft_tracked_for_vio")
+        out = np.zeros(n.value, dtype=COLOR_VIO_POINT_DTYPE)
+        if n.value:
+            self._chk(self.lib.srl_oft_tracked_for_vio(self.h, _ptr(out), len(out), C.byref(n)), "srl_oft_tracked_for_vio")
+        return out
 
 
 class Lio:

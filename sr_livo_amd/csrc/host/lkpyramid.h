@@ -2,7 +2,8 @@
 // reference's constructor arguments, its setTerminationCriteria clamping (:670-682) and trackImage (:755-795) on a raw gray buffer.  The
 // pyramid, the derivative and the track are one call on the device (srl_flow_track_image, csrc/srl_flow.hip); nothing of them is
 // computed here and there is no host loop to fall back to.  The object owns the context's one device tracker, which it creates at
-// the first image with the clamped criteria.  reduce_vector, findFundamentalMat and the rest of opticalFlowTracker stay with the caller.
+// the first image with the clamped criteria.  findFundamentalMat stays with the caller; the rest of
+// opticalFlowTracker is opticalFlowTracker.h of this directory.
 #pragma once
 #include "../../../include/srlivo_hip.h"
 

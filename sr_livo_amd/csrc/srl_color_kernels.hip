@@ -388,7 +388,8 @@ extern "C" int srl_color_map_destroy(srl_ctx *ctx) {
     if (cm->d_grid) hipFree(cm->d_grid);
     srl_color_render_free(cm);
     srl_color_select_free(cm);
-    for (SrlWgTotals *t : {&cm->render_tot, &cm->select_tot, &cm->vio_tot, &cm->cloud_tot}) srl_wg_totals_free(*t);
+    srl_color_track_free(cm);
+    for (SrlWgTotals *t : {&cm->render_tot, &cm->select_tot, &cm->vio_tot, &cm->cloud_tot, &cm->track_old_tot, &cm->track_cand_tot}) srl_wg_totals_free(*t);
     srl_epoch_table_free(cm->scratch);
     delete cm;
     ctx->color = nullptr;

@@ -1,6 +1,6 @@
 // srl_color_map.h -- internal: the colour voxel map's device layout, shared by its construction (srl_color_kernels.hip) and its
 // consumers, the rendering pass (srl_color_render.hip), the selection for projection (srl_color_select.hip), the camera ESIKF's
-// measurement passes (srl_color_vio.hip) and the cloud export (srl_color_cloud.hip).  DESIGN.md section 3.
+// measurement passes (srl_color_vio.hip), the cloud export (srl_color_cloud.hip) and the tracker's point set (srl_color_track.hip).  DESIGN.md section 3.
 // The inline host helpers at its end call the HIP runtime (HIPCHK, DevBuf): the runtime's headers come in through srl_ctx.h.
 #pragma once
 #include "srl_ctx.h"
@@ -56,6 +56,12 @@ struct SrlColorMap {
     SrlWgTotals vio_tot;                                          // k_vio_rows, rows of 88 words (78 sums as FP64 bits, 5 counts): [0..87] the row of the
                                                                   // last call, [88] the ticket
 
+    // the tracker's point set (srl_color_track.hip); nothing of it exists before the first srl_color_map_track_update
+    SrlEpochTable trk_pool;                                       // (pool position << 1 | candidate) -> slot; minw = {~call counter, smallest input index}
+    SrlEpochTable trk_cells;                                      // image cell -> slot; minw = {~call counter, 0 for a kept point, else 1 + smallest candidate index}
+    SrlWgTotals track_old_tot;                                    // k_track_old: [0..5] the first loop's outcomes of the last call, [6] the ticket
+    SrlWgTotals track_cand_tot;                                   // k_track_count: [0..6] the second loop's outcomes of the last call, [7] the ticket
+
     // cloud export (srl_color_cloud.hip); nothing of it exists before the first srl_color_map_export_cloud
     SrlWgTotals cloud_tot;                                        // k_cloud_flags: [0..1] below the views, stale, [2] the ticket, [4] an int: published
 };
@@ -108,3 +114,5 @@ int srl_color_state_reserve(srl_ctx *ctx, SrlColorMap *cm);
 void srl_color_render_free(SrlColorMap *cm);
 // frees what the selection allocated (srl_color_map_destroy)
 void srl_color_select_free(SrlColorMap *cm);
+// frees what the tracker's update allocated (srl_color_map_destroy)
+void srl_color_track_free(SrlColorMap *cm);

@@ -261,7 +261,8 @@ int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows, int cols,
 /* voxels_xyz: n_voxels x 3 int32, the caller's voxels_recent_visited (the visited output of srl_color_map_insert).  The list may name a
  * voxel several times (lioOptimization.cpp:523-550: the temp list accumulates while to_rendering is false); the reference renders such
  * a voxel once per occurrence with the same observation, and so does this call: updateRgb runs `multiplicity` times in a row per point
- * (at most 65 535 occurrences of one voxel: SRL_ERR_UNSUPPORTED beyond, nothing changed).  A key the map does not hold is counted in
+ * (at most 65 535 occurrences of one voxel: SRL_ERR_UNSUPPORTED beyond, nothing changed, *totals all zero as for every other
+ * refusal; the call after a refusal is an ordinary one).  A key the map does not hold is counted in
  * totals->unknown and otherwise ignored (the reference's map[voxel] would create an empty block; lists come from the insertion, so this
  * does not arise).  The pass visits every stored point of the map once, whatever the list's length.  Synchronous: one wait for the totals.
  * Return codes, all before a device is touched: NULL ctx, cam or (n_voxels > 0) voxels_xyz, n_voxels < 0, a non-finite camera or obs_time,

@@ -92,6 +92,33 @@ int srl_debug_frame_timing(srl_ctx *ctx, int enable, double out16[16]);
  * the tables are cleared when it wraps, every 65 535 frames (1.8 h of a 10 Hz sensor).  Test hook: set the epoch counters of both tables so
  * that the wrap happens `frames_to_wrap` frames from now. */
 int srl_debug_set_frame_epoch(srl_ctx *ctx, int frames_to_wrap);
+/* The 32-bit companions of the same tables wrap as well: the selection's table and the insertion's carry a call counter (1 ... 0xFFFFFFFE; the
+ * selection's first-index words hold 0xFFFFFFFF - counter) and are cleared when it wraps, and the seen words of srl_frame_subsample carry a
+ * tag (1 ... 0xFFFFFFFF) and are cleared when that wraps.  srl_debug_set_frame_counters moves all three forward so that each owner's next
+ * `calls_to_wrap` calls use its last `calls_to_wrap` values and the call after them wraps (the selection's table is opened once by every
+ * srl_frame_subsample AND once by every srl_frame_select_keypoints; the seen words take a tag in every srl_frame_subsample AND in every
+ * srl_frame_take_subsampled of m > 0 points).  It synchronises the stream first and only moves forward
+ * (SRL_ERR_BAD_ARG otherwise, and nothing is changed): what the tables hold stays stale.  srl_frame_subsample sets its tag back to 0 when its
+ * buffers grow, so apply the hook after a sub-sample of the largest sweep of the run has allocated them.
+ * srl_debug_frame_counters: out = {counter of the selection's table, counter of the insertion's table, tag of the seen words} as the last
+ * calls left them. */
+int srl_debug_set_frame_counters(srl_ctx *ctx, int calls_to_wrap);
+int srl_debug_frame_counters(srl_ctx *ctx, uint32_t out[3]);
+/* The colour map keeps five structures of the same kind: the insertion's scratch table (srl_color_map_insert), the
+ * selection's image cells with their two companion arrays (srl_color_map_select), the tracker's pool-position and image-cell tables (one
+ * srl_color_map_track_update opens both) and the render's mark words (srl_color_map_render).  Each table carries a 16-bit epoch
+ * (1 ... 0xFFFF) and a 32-bit call counter (1 ... 0xFFFFFFFE; companion words hold 0xFFFFFFFF - counter), the mark words the 16-bit render
+ * epoch; a structure is cleared when its number wraps to 1.
+ * srl_debug_color_epochs: out = { [0] scratch epoch, [1] selection epoch, [2] tracker pool epoch, [3] tracker cell epoch,
+ *                                 [4] selection counter, [5] tracker pool counter, [6] tracker cell counter, [7] scratch counter,
+ *                                 [8] render epoch } as the last calls left them (0: never used).  SRL_ERR_NO_MAP without a colour map.
+ * srl_debug_set_color_epochs: -1 leaves a family alone; a value k >= 0 moves every number of the family forward so that the next k calls of
+ * each owner use the last k values and call k + 1 wraps -- calls_to_epoch_wrap (<= 0xFFFF): the four epochs and the render epoch,
+ * calls_to_counter_wrap: the four counters.  It synchronises the stream first and only moves forward (entries written so far then stay
+ * stale: a larger counter is a smaller companion tag, and the smaller tag wins atomicMin); if any number would move backward it returns
+ * SRL_ERR_BAD_ARG and changes nothing. */
+int srl_debug_color_epochs(srl_ctx *ctx, uint32_t out[9]);
+int srl_debug_set_color_epochs(srl_ctx *ctx, int calls_to_epoch_wrap, int calls_to_counter_wrap);
 /* tuning experiments: force the association kernel's launch shape -- keypoints per wave (16-wave workgroups: 2 / 3 / 4 / 6 / 8 /
  * 12 / 16; 4-wave workgroups: 4 / 8 / 16) and waves per workgroup (4 / 16); 0, 0 = automatic (by sweep size).  Results do not
  * depend on the shape beyond FP64 summation order. */

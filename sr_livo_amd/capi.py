@@ -273,6 +273,8 @@ def load_library():
         "srl_color_map_download": ([p, p, p, p, C.c_int, p, p, C.c_int64], C.c_int),
         "srl_color_registered_download": ([p, C.c_int64, C.c_int, p], C.c_int),
         "srl_debug_color_map_rebuilds": ([p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+        "srl_debug_color_epochs": ([p, C.POINTER(C.c_uint32)], C.c_int),
+        "srl_debug_set_color_epochs": ([p, C.c_int, C.c_int], C.c_int),
         "srl_color_image_upload": ([p, p, C.c_int, C.c_int, C.c_int64], C.c_int),
         "srl_color_select_opts_default": ([C.POINTER(ColorSelectOpts)], None),
         "srl_color_map_select": ([p, C.POINTER(ColorCamera), C.c_int, C.c_int, p, C.c_int, C.POINTER(ColorSelectOpts), p, C.c_int64,
@@ -365,6 +367,8 @@ def load_library():
         "srl_debug_pass_stamps": ([p, C.c_int, p, p], C.c_int),
         "srl_debug_frame_timing": ([p, C.c_int, p], C.c_int),
         "srl_debug_set_frame_epoch": ([p, C.c_int], C.c_int),
+        "srl_debug_set_frame_counters": ([p, C.c_int], C.c_int),
+        "srl_debug_frame_counters": ([p, C.POINTER(C.c_uint32)], C.c_int),
         "srl_set_armed_launch": ([p, C.c_int], C.c_int),
         "srl_disarm": ([p], C.c_int),
         "srl_solve_end": ([p], C.c_int),
@@ -883,6 +887,20 @@ class Context:
         self._chk(self.lib.srl_debug_color_map_rebuilds(self.h, C.byref(a), C.byref(b)), "srl_debug_color_map_rebuilds")
         return a.value, b.value
 
+    COLOR_EPOCHS = ("scratch_epoch", "select_epoch", "track_pool_epoch", "track_cell_epoch", "select_counter", "track_pool_counter",
+                    "track_cell_counter", "scratch_counter", "render_epoch")
+
+    def color_epochs(self):
+        """test hook: the numbers of the colour map's never-cleared structures as a dict (COLOR_EPOCHS; srl_debug_color_epochs)"""
+        out = (C.c_uint32 * 9)()
+        self._chk(self.lib.srl_debug_color_epochs(self.h, out), "srl_debug_color_epochs")
+        return dict(zip(self.COLOR_EPOCHS, (int(v) for v in out)))
+
+    def set_color_epochs(self, calls_to_epoch_wrap=-1, calls_to_counter_wrap=-1):
+        """test hook: the next k calls of each owner use the family's last k values, call k + 1 wraps; -1 leaves a family alone
+        (srl_debug_set_color_epochs)"""
+        self._chk(self.lib.srl_debug_set_color_epochs(self.h, int(calls_to_epoch_wrap), int(calls_to_counter_wrap)), "srl_debug_set_color_epochs")
+
     def sweep_upload(self, raw_xyz):
         r = _f64(raw_xyz, (-1, 3))
         self._chk(self.lib.srl_sweep_upload(self.h, _ptr(r), len(r)), "srl_sweep_upload")
@@ -1012,6 +1030,17 @@ class Context:
     def set_frame_epoch(self, frames_to_wrap):
         """test hook: the epoch of the frame pipeline's scratch tables wraps `frames_to_wrap` frames from now (srl_debug_set_frame_epoch)"""
         self._chk(self.lib.srl_debug_set_frame_epoch(self.h, int(frames_to_wrap)), "srl_debug_set_frame_epoch")
+
+    def set_frame_counters(self, calls_to_wrap):
+        """test hook: the 32-bit counters of the frame pipeline's scratch tables and the tag of the sub-sample's seen words wrap
+        `calls_to_wrap` calls of each owner from now; apply it after the sub-sample's buffers exist (srl_debug_set_frame_counters)"""
+        self._chk(self.lib.srl_debug_set_frame_counters(self.h, int(calls_to_wrap)), "srl_debug_set_frame_counters")
+
+    def frame_counters(self):
+        """(counter of the selection's table, counter of the insertion's table, tag of the sub-sample's seen words)"""
+        out = (C.c_uint32 * 3)()
+        self._chk(self.lib.srl_debug_frame_counters(self.h, out), "srl_debug_frame_counters")
+        return tuple(int(v) for v in out)
 
     def frame_timing(self, enable=True):
         """accumulated stage times (us) of the frame pipeline since the last call (which clears them); see srl_debug_frame_timing"""

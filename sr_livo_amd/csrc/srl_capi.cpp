@@ -840,6 +840,27 @@ int srl_debug_set_frame_epoch(srl_ctx *ctx, int frames_to_wrap) {
     return SRL_OK;
 }
 
+int srl_debug_set_frame_counters(srl_ctx *ctx, int calls_to_wrap) {
+    if (!ctx || calls_to_wrap < 0) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // the tables' counters end at 0xFFFFFFFE (srl_epoch_table_begin), the seen words' tag at 0xFFFFFFFF (sub_seen_begin); words written so
+    // far carry smaller numbers and stay stale when the numbers move forward
+    const unsigned counter = 0xFFFFFFFEu - (unsigned)calls_to_wrap, seen = 0xFFFFFFFFu - (unsigned)calls_to_wrap;
+    if (ctx->sel_table.counter32 > counter || ctx->ins_table.counter32 > counter || ctx->sub_seen_tag > seen) return SRL_ERR_BAD_ARG;
+    ctx->sel_table.counter32 = counter;
+    ctx->ins_table.counter32 = counter;
+    ctx->sub_seen_tag = seen;
+    return SRL_OK;
+}
+
+int srl_debug_frame_counters(srl_ctx *ctx, uint32_t out[3]) {
+    if (!ctx || !out) return SRL_ERR_BAD_ARG;
+    out[0] = ctx->sel_table.counter32; out[1] = ctx->ins_table.counter32; out[2] = ctx->sub_seen_tag;
+    return SRL_OK;
+}
+
 int srl_debug_frame_timing(srl_ctx *ctx, int enable, double out16[16]) {
     if (!ctx) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);

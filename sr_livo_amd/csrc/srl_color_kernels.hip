@@ -419,6 +419,38 @@ extern "C" int srl_debug_color_map_rebuilds(srl_ctx *ctx, int32_t *voxel_table, 
     return SRL_OK;
 }
 
+extern "C" int srl_debug_color_epochs(srl_ctx *ctx, uint32_t out[9]) {
+    if (!ctx || !out) return SRL_ERR_BAD_ARG;
+    const SrlColorMap *cm = ctx->color;
+    if (!cm) return SRL_ERR_NO_MAP;
+    out[0] = cm->scratch.epoch16; out[1] = cm->sel_cells.epoch16; out[2] = cm->trk_pool.epoch16; out[3] = cm->trk_cells.epoch16;
+    out[4] = cm->sel_cells.counter32; out[5] = cm->trk_pool.counter32; out[6] = cm->trk_cells.counter32; out[7] = cm->scratch.counter32;
+    out[8] = cm->render_epoch;
+    return SRL_OK;
+}
+
+extern "C" int srl_debug_set_color_epochs(srl_ctx *ctx, int calls_to_epoch_wrap, int calls_to_counter_wrap) {
+    if (!ctx || calls_to_epoch_wrap < -1 || calls_to_epoch_wrap > 0xFFFF || calls_to_counter_wrap < -1) return SRL_ERR_BAD_ARG;
+    SrlColorMap *cm = ctx->color;
+    if (!cm) return SRL_ERR_NO_MAP;
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // entries written so far carry numbers <= the old ones: moving a number forward keeps all of them stale (epochs compare unequal, a
+    // companion word {0xFFFFFFFF - counter, ...} of an earlier call is larger than any of a later one and loses atomicMin)
+    const unsigned epoch = 0xFFFFu - (unsigned)calls_to_epoch_wrap, counter = 0xFFFFFFFEu - (unsigned)calls_to_counter_wrap;
+    SrlEpochTable *const tables[4] = {&cm->scratch, &cm->sel_cells, &cm->trk_pool, &cm->trk_cells};
+    for (const SrlEpochTable *t : tables)
+        if ((calls_to_epoch_wrap >= 0 && t->epoch16 > epoch) || (calls_to_counter_wrap >= 0 && t->counter32 > counter)) return SRL_ERR_BAD_ARG;
+    if (calls_to_epoch_wrap >= 0 && cm->render_epoch > epoch) return SRL_ERR_BAD_ARG;
+    for (SrlEpochTable *t : tables) {
+        if (calls_to_epoch_wrap >= 0) t->epoch16 = epoch;
+        if (calls_to_counter_wrap >= 0) t->counter32 = counter;
+    }
+    if (calls_to_epoch_wrap >= 0) cm->render_epoch = epoch;
+    return SRL_OK;
+}
+
 extern "C" int srl_color_map_insert(srl_ctx *ctx, const double *world_xyz, int n, double time_sweep_end, double time_last_process, uint8_t *outcome,
                                     srl_color_stored *stored, int stored_capacity, int32_t *visited_xyz, int visited_capacity, srl_color_totals *totals) {
     if (totals) std::memset(totals, 0, sizeof *totals);

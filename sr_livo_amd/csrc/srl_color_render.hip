@@ -4,8 +4,9 @@
 // rgbPoint::updateRgb (src/cloudMap.cpp:59-100).  Every operation is an IEEE operation in the reference's order (-ffp-contract=off,
 // sums of three as (a0 + a1) + a2), so the state is held to the bar of the rest of this tree: bitwise.
 //
-//   k_render_mark    one thread per list entry: the key is looked up in the map's voxel table and 1 is added to the voxel's mark word,
-//                    (render epoch << 16) | occurrences -- a word of another epoch IS zero occurrences, nothing is cleared per call
+//   k_render_mark    one thread per list entry: the key is looked up in the map's voxel table and the voxel's mark word,
+//                    (render epoch << 16) | occurrences, is raised by the entries of the wave that name it -- a word of another epoch IS
+//                    zero occurrences, nothing is cleared per call
 //   k_render_points  one thread per POOL point: 24-byte record, 4-byte mark gather; an unmarked point leaves at once, a marked one runs
 //                    the loop body `occurrences` times and rewrites its 40-byte state record.  The six counters leave through
 //                    srl_wg_totals (srl_wg_totals.h)
@@ -38,17 +39,32 @@ enum { RC_LISTED, RC_BEHIND, RC_OUTSIDE, RC_GATED, RC_FIRST, RC_UPDATED, RC_N };
 
 __global__ void k_render_mark(const int *voxels_xyz, int n, const SrlColorSlot *vtab, unsigned vmask, unsigned *mark, unsigned epoch, unsigned long long *rtot) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int v = srl_color_find_voxel(vtab, vmask, voxels_xyz[(size_t)e * 3], voxels_xyz[(size_t)e * 3 + 1], voxels_xyz[(size_t)e * 3 + 2]);
-    if (v < 0) { atomicAdd(&rtot[SRL_RTOT_UNKNOWN], 1ull); return; }
-    unsigned old = mark[v];
-    for (;;) {
-        const bool cur = (old >> 16) == epoch;
-        if (cur && (old & 0xFFFFu) == 0xFFFFu) { atomicAdd(&rtot[SRL_RTOT_OVERFLOW], 1ull); return; }
-        const unsigned want = cur ? old + 1u : ((epoch << 16) | 1u);
-        const unsigned prev = atomicCAS(&mark[v], old, want);
-        if (prev == old) return;
-        old = prev;
+    const int lane = threadIdx.x & 63;
+    int v = -1;
+    if (e < n) {
+        v = srl_color_find_voxel(vtab, vmask, voxels_xyz[(size_t)e * 3], voxels_xyz[(size_t)e * 3 + 1], voxels_xyz[(size_t)e * 3 + 2]);
+        if (v < 0) atomicAdd(&rtot[SRL_RTOT_UNKNOWN], 1ull);
+    }
+    // the entries of a wave that name one voxel add their number in ONE compare-and-swap: with one per entry a list that names a voxel
+    // tens of thousands of times retries n^2 / 2 times on one word (seconds for the 65 535 a mark word counts).  The sum of what was added
+    // never passes 0xFFFF, so a list is flagged exactly when it names a voxel more often than that, whatever the order of the waves
+    unsigned long long pending = __ballot(v >= 0);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int lv = __shfl(v, leader);
+        const unsigned long long same = __ballot(v == lv);
+        pending &= ~same;
+        if (lane == leader) {                 // (the wave meets again behind this block: `pending` and the ballots stay those of the whole wave)
+            const unsigned add = (unsigned)__popcll(same);
+            unsigned old = mark[lv];
+            for (;;) {
+                const unsigned have = (old >> 16) == epoch ? (old & 0xFFFFu) : 0u;
+                if (have + add > 0xFFFFu) { atomicAdd(&rtot[SRL_RTOT_OVERFLOW], 1ull); break; }
+                const unsigned prev = atomicCAS(&mark[lv], old, (epoch << 16) | (have + add));
+                if (prev == old) break;
+                old = prev;
+            }
+        }
     }
 }
 

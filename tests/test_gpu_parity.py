@@ -1388,6 +1388,70 @@ def test_scratch_table_epoch_wrap_changes_nothing():
         a.close(); b.close()
 
 
+def test_scratch_table_counter_wraps_change_nothing():
+    """The 32-bit numbers beside the epochs wrap too: the call counter of the selection's table (its first-index words hold
+    0xFFFFFFFF - counter; the sub-sample and the keypoint selection of a frame each open the table once) and of the insertion's table, both
+    behind 0xFFFFFFFE, and the tag of the sub-sample's seen words (one per sub-sample, one per take) behind 0xFFFFFFFF.  The seven-frame stream of the epoch test with the
+    sub-sample in front of every selection: a context whose three numbers wrap in the middle of it gives the same sub-sample, keypoints,
+    world points and map as one far from the wrap, and the read-back shows every number going from its last value to 1 in one call.
+    (A sub-sample of the largest sweep comes first: the hook is for buffers that exist, a growth sets the tag back to 0.)"""
+    pts, L = synth.map_candidates(1401, 40_000)
+    sizes = (8_000, 8_000, 5_000, 12_000, 8_000, 300, 9_000)
+    st = np.zeros((2, 17)); st[:, 0] = [200.0, 200.1]; st[:, 10] = 1.0          # identity motion: corrected == sensor-frame points
+    LAST = (0xFFFFFFFE, 0xFFFFFFFE, 0xFFFFFFFF)
+    a = srl.Context(0); b = srl.Context(0)
+    try:
+        rng = np.random.default_rng(1402)
+        warm = synth.make_sweep(1409, max(sizes), L)["raw"]
+        for c in (a, b):
+            c.map_insert(pts[:15_000])
+            c.frame_undistort(warm, np.sort(rng.uniform(0.0, 100.0, len(warm))), st, 200.0, capi.MC_CONSTANT_VELOCITY, want_outputs=False)
+            assert c.frame_subsample(np.arange(len(warm), dtype=np.int32), 0.3) > 0
+        assert a.frame_counters() == b.frame_counters() and all(1 <= v < 16 for v in a.frame_counters())      # low numbers, written into many slots
+        wrapped = [[], [], []]                                # per number: the (frame, step) whose call took it from its last value to 1
+
+        def step(k, name, fn):
+            before = a.frame_counters()
+            out = fn(a), fn(b)
+            after = a.frame_counters()
+            for i in range(3):
+                if after[i] == 1 and before[i] > 1:
+                    assert before[i] == LAST[i], (k, name, before, after)
+                    wrapped[i].append((k, name))
+                else:
+                    assert after[i] in (before[i], before[i] + 1), (k, name, before, after)
+            return out
+
+        for k, n in enumerate(sizes):
+            if k == 1:
+                a.set_frame_counters(2)                       # the next two calls of each owner use its last two numbers, the third wraps
+                assert a.frame_counters() == tuple(v - 2 for v in LAST)
+                assert a.lib.srl_debug_set_frame_counters(a.h, 3) == -3 and a.frame_counters() == tuple(v - 2 for v in LAST)      # never backward
+            sw = synth.make_sweep(1410 + k, n, L)
+            q, t = sw["q_pred"], sw["t_pred"]
+            order = rng.permutation(n).astype(np.int32)
+            rel_t = np.sort(rng.uniform(0.0, 100.0, n))
+            for c in (a, b):
+                c.frame_undistort(sw["raw"], rel_t, st, 200.0, capi.MC_CONSTANT_VELOCITY, want_outputs=False)
+            ma, mb = step(k, "subsample", lambda c: c.frame_subsample(order, 0.3))
+            assert ma == mb and ma > 0, f"frame {k}"
+            perm = rng.permutation(ma).astype(np.int32)
+            ia, ib = step(k, "take", lambda c: c.frame_take_subsampled(perm)["index"])
+            assert np.array_equal(ia, ib), f"frame {k}"
+            kpa, kpb = step(k, "select", lambda c: c.frame_select_keypoints(q, t, 0.9))
+            (wa, _), (wb, _) = step(k, "commit", lambda c: c.frame_commit(sw["q_gt"], sw["t_gt"], want_added=(k % 2 == 0)))
+            assert np.array_equal(kpa, kpb) and np.array_equal(wa, wb) and len(kpa) > 0, f"frame {k}"
+            assert a.map_size() == b.map_size(), f"frame {k}"
+        # the selection's table is opened twice per frame (sub-sample, selection) and the seen words take two tags (sub-sample, take): both
+        # wrap one frame earlier than the insertion's table
+        assert wrapped == [[(2, "subsample")], [(3, "commit")], [(2, "subsample")]], wrapped
+        assert a.frame_counters() != b.frame_counters()
+        ka, ca, xa = a.map_download(); kb, cb, xb = b.map_download()
+        assert np.array_equal(ka, kb) and np.array_equal(ca, cb) and np.array_equal(xa, xb)
+    finally:
+        a.close(); b.close()
+
+
 # ----------------------------------------------------------------------------- frame-resident pipeline (rows f1/f2)
 def test_deferred_commit_equals_the_synchronous_one_over_a_stream_of_frames():
     """srl_frame_commit with num_added = NULL only enqueues the insertion (the map's totals are folded in by the next reader); the

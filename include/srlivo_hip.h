@@ -221,8 +221,9 @@ int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_co
  * (cloudMap.cpp:59-100).  The per-point colour state (rgb int16 x 3, cov_rgb FP32 x 3, observe_distance, last_observe_time, N_rgb int16:
  * cloudMap.h:51-66) lives in HBM beside the point pool, 40 bytes per stored point, allocated at the first srl_color_image_upload; zero
  * bytes are rgbPoint::reset().  selectPointsForProjection is srl_color_map_select below, the measurement loops of vioEsikf and of
- * vioPhotometric are srl_color_map_vio_rows, the optical flow is srl_flow_track_image; the rest of the vision stage (PnP, undistortion and equalisation of the
- * image, the publishers) stays with the caller.
+ * vioPhotometric are srl_color_map_vio_rows, the optical flow is srl_flow_track_image, the inlier sets the reference takes from findFundamentalMat and
+ * solvePnPRansac have a stand-in of this library's own (srl_consensus_*, not OpenCV's results); the rest of the vision stage (undistortion and
+ * equalisation of the image, the publishers) stays with the caller.
  *
  * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
  *   p = (double) stored FP32 position; pc = R_cw p + t_cw with q_cw = q_world_camera.inverse(), R_cw = q_cw.toRotationMatrix(),
@@ -479,6 +480,62 @@ int srl_flow_create(srl_ctx *ctx, const srl_flow_opts *opts);
 int srl_flow_destroy(srl_ctx *ctx);
 int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n,
                          float *next_xy, uint8_t *status, int *n_tracked);
+
+/* ------------------------------------------------------------------ consensus outlier rejection of the camera tracker
+ * stands where the reference calls cv::findFundamentalMat(last, cur, FM_RANSAC, 1.0, 0.997, status) (opticalFlowTracker.cpp:144) and
+ * cv::solvePnPRansac(points_3d, points_2d, intrinsic, ..., 200, 1.5, 0.99, status) (:295).  The reference reads ONLY the inlier mask /
+ * inlier list of either call (mat_F, cv_so3 and cv_trans are never used), and OpenCV's own mask depends on its private random generator,
+ * so every consumer already takes any valid consensus set.  These two calls are therefore NOT OpenCV's results and claim no parity
+ * with them: they are a deterministic RANSAC of this library, a function of (inputs, options) alone -- the same bytes call after call.
+ *
+ * H = opts->hypotheses hypotheses, always all of them (the run time does not depend on the data).  Hypothesis h draws its minimal sample
+ * from the USABLE points (every coordinate finite; in input order, m of them) with a counter-based generator, no state between calls:
+ *   draw(seed, h, k, m) = ((mix(((uint64) seed << 32 | h) * 0x9E3779B97F4A7C15 + (k + 1) * 0xBF58476D1CE4E5B9) >> 32) * m) >> 32,
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31      (all modulo 2^64)
+ * for k = 0, 1, ...: a draw that repeats an earlier position is rejected, and a hypothesis that has not collected its sample after 64
+ * draws has none.  The minimal problem is solved in FP64:
+ *   fundamental  the 7-point algorithm on Hartley-normalised points (per call: centroid and sqrt 2 / mean distance of the usable points
+ *                of each view): the two null vectors F1, F2 of the 7 x 9 system, the real roots of det(a F1 + (1 - a) F2) = 0, each
+ *                solution de-normalised and scaled to unit Frobenius norm -- up to 3 model slots per hypothesis;
+ *   PnP          P3P (Grunert's quartic as in Haralick et al., IJCV 1994, each root refined on the three distance equations) on image
+ *                points normalised by fx, fy, cx, cy; every solution with positive depth at the three sample points is kept as R, t
+ *                (camera = R world + t) -- up to 4 slots; no fourth point disambiguates, every solution is scored.
+ * A degenerate sample (repeated or collinear points, a vanishing leading coefficient) gives no model, never a NaN model.
+ * Every model is scored on all n points, FP64, no contraction, in exactly this order (float inputs converted to double first):
+ *   fundamental, F row-major, (x1, y1) of last_xy, (x2, y2) of cur_xy:
+ *     a = (F0 x1 + F1 y1) + F2, b = (F3 x1 + F4 y1) + F5, c = (F6 x1 + F7 y1) + F8, d2 = (a x2 + b y2) + c, e2 = (d2 d2) / (a a + b b);
+ *     a' = (F0 x2 + F3 y2) + F6, b' = (F1 x2 + F4 y2) + F7, c' = (F2 x2 + F5 y2) + F8, d1 = (a' x1 + b' y1) + c', e1 = (d1 d1) / (a' a' + b' b');
+ *     inlier iff e1 <= threshold^2 and e2 <= threshold^2 (the larger of the two squared distances to the epipolar lines);
+ *   PnP: xc = ((R0 X + R1 Y) + R2 Z) + t0, yc and zc likewise with rows 1 and 2; du = (fx (xc / zc) + cx) - u, dv = (fy (yc / zc) + cy) - v;
+ *     inlier iff zc > 0 and du du + dv dv <= threshold^2.
+ * A point with a non-finite coordinate is never an inlier.  The valid model with the most inliers wins, ties go to the lowest model
+ * index = hypothesis * slots + slot (slots: 3, 4).  status = its n-byte mask; inliers = the ascending indices of its inliers.
+ * result: model = F row-major in [0, 9) (the rest 0), or R row-major then t; sample = the 7 or 3 sample indices padded with -1;
+ * hypothesis, slot = the winner's; inliers = its count; models_valid = valid models among all slots; confidence_reached = 1 iff
+ * 1 - (1 - w^s)^H >= confidence with w = inliers / n, s = 7 or 3 (powers by repeated multiplication) -- the only role of OpenCV's
+ * confidence argument.  Without any valid model (every sample degenerate), or with n < 8 (fundamental) / n < 4 (PnP): SRL_OK, an
+ * all-zero mask, no inliers, models_valid = 0, model 0, sample, hypothesis and slot -1.
+ * Before a device is touched, SRL_ERR_BAD_ARG with the result zeroed and the outputs untouched: a NULL ctx (first), n < 0,
+ * n > SRL_CONSENSUS_MAX_POINTS, a NULL array with n > 0, NULL n_inliers or intrinsics, hypotheses outside 1 ... SRL_CONSENSUS_MAX_HYPOTHESES,
+ * a threshold that is not finite and positive, a confidence outside (0, 1), intrinsics that are not finite, fx or fy equal to 0.
+ * opts == NULL: the defaults; result may be NULL.  More than one rank: SRL_ERR_UNSUPPORTED.  Synchronous; cancels an armed launch.  The
+ * workspace (about 2 MB of device memory) is allocated at a context's first call and freed with the context. */
+#define SRL_CONSENSUS_FUNDAMENTAL 0
+#define SRL_CONSENSUS_PNP 1
+#define SRL_CONSENSUS_MAX_POINTS 4096
+#define SRL_CONSENSUS_MAX_HYPOTHESES 4096
+typedef struct srl_consensus_opts { double threshold; double confidence; int32_t hypotheses; uint32_t seed; } srl_consensus_opts;
+typedef struct srl_consensus_result {
+    double model[12];
+    int32_t sample[8];
+    int32_t hypothesis, slot, inliers, models_valid, confidence_reached, reserved;
+} srl_consensus_result;
+/* SRL_CONSENSUS_FUNDAMENTAL: 1.0, 0.997, 512, 0; SRL_CONSENSUS_PNP: 1.5, 0.99, 200, 0 (the reference's call-site arguments; 512 is ours) */
+void srl_consensus_opts_default(srl_consensus_opts *o, int model);
+int srl_consensus_fundamental(srl_ctx *ctx, const float *last_xy, const float *cur_xy, int n, const srl_consensus_opts *opts, uint8_t *status,
+                              srl_consensus_result *result);
+int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, const double *fx_fy_cx_cy, const srl_consensus_opts *opts,
+                      int32_t *inliers, int *n_inliers, srl_consensus_result *result);
 
 /* ------------------------------------------------------------------ colour voxel map: the coloured cloud
  * replaces: the loops of lioOptimization::pubColorPoints (lioOptimization.cpp:1210-1241), threadPubColorPoints (:1243-1344) and

@@ -284,6 +284,15 @@ int srl_lk_track_image(srl_lk *lk, const uint8_t *gray, int rows, int cols, int6
  *                stands for the cv::Exception the reference catches (*accepted = 0); no default: with 10 or more points and none set
  *                SRL_ERR_BAD_ARG
  *   update       srl_color_map_track_update's arguments without the context and the outcome arrays; default: that call on ctx
+ * srl_oft_use_device_consensus (the reference's setIntrinsic, :104-109, plus its two cv:: calls) installs as the fundamental and the PnP
+ * provider this library's own estimators on the handle's context: srl_consensus_fundamental and srl_consensus_pnp (srlivo_hip.h) with
+ * the intrinsics fx, fy, cx, cy and the options given (NULL: srl_consensus_opts_default of either model).  They are NOT OpenCV's
+ * results; they stand in because the reference reads only the mask / inlier list, which in OpenCV depends on its private generator.
+ * A handle made with a NULL ctx: SRL_ERR_NO_DEVICE; intrinsics or options srl_consensus_* would refuse: their status (SRL_ERR_BAD_ARG;
+ * a context with more than one rank: SRL_ERR_UNSUPPORTED), nothing installed -- the rules are theirs and are asked of them.  A provider set later with srl_oft_set_fundamental_provider / srl_oft_set_pnp_provider replaces it.  While it is in
+ * place a failing device call is the status of srl_oft_track_image / srl_oft_remove_outlier_using_ransac_pnp, never the "caught
+ * cv::Exception" path.  Without this call (and without providers) both steps refuse as before.  srl_oft_last_consensus: the result
+ * record of the handle's last device call, which = 0 fundamental, 1 PnP (zeros before the first).
  * srl_oft_init = init (:188-197) on rgb_points_vec / points_2d_vec as selection records; srl_oft_track_image = trackImage (:111-186):
  * gray == NULL is the empty image, fewer than 30 points only move the time, *n_cur = map_rgb_points_in_cur_image_pose.size();
  * image_rows / image_cols are the frame's (if2dPointsAvailable(x, y, 1.0, 0.05)); rejectErrorTrackingPoints is not built (the reference
@@ -306,6 +315,9 @@ int srl_oft_set_flow_provider(srl_oft *oft, srl_oft_flow_provider fn, void *user
 int srl_oft_set_fundamental_provider(srl_oft *oft, srl_oft_fundamental_provider fn, void *user);
 int srl_oft_set_pnp_provider(srl_oft *oft, srl_oft_pnp_provider fn, void *user);
 int srl_oft_set_update_provider(srl_oft *oft, srl_oft_update_provider fn, void *user);
+int srl_oft_use_device_consensus(srl_oft *oft, const double *fx_fy_cx_cy, const srl_consensus_opts *fundamental /* NULL = default */,
+                                 const srl_consensus_opts *pnp /* NULL = default */);
+int srl_oft_last_consensus(srl_oft *oft, int which /* 0 fundamental, 1 pnp */, srl_consensus_result *out);
 int srl_oft_set_track_points(srl_oft *oft, const srl_color_selected *records, int n);
 int srl_oft_init(srl_oft *oft, const srl_color_selected *records, int n, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes,
                  double time_sweep_end);

@@ -12,4 +12,6 @@ from .capi import (  # noqa: F401
     ColorVioArgs, ColorVioSums, COLOR_VIO_POINT_DTYPE, SRL_VIO_REPROJECTION, SRL_VIO_PHOTOMETRIC,
     Flow, FlowOpts, default_flow_opts,
     ColorTrackOpts, ColorTrackTotals, COLOR_TRACK_POINT_DTYPE, default_color_track_opts, Oft,
+    ConsensusOpts, ConsensusResult, default_consensus_opts, SRL_CONSENSUS_FUNDAMENTAL, SRL_CONSENSUS_PNP,
+    SRL_CONSENSUS_MAX_POINTS, SRL_CONSENSUS_MAX_HYPOTHESES,
 )

@@ -166,6 +166,28 @@ SRL_FLOW_PREV, SRL_FLOW_CUR = 0, 1
 FLOW_BORDER = 21
 
 
+class ConsensusOpts(C.Structure):
+    """srl_consensus_opts: inlier threshold (pixels), confidence, the fixed number of hypotheses, the generator's seed"""
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("hypotheses", C.c_int32), ("seed", C.c_uint32)]
+
+
+class ConsensusResult(C.Structure):
+    """srl_consensus_result: the winning model (F row-major in [0, 9), or R row-major then t), its sample, where it came from, its count"""
+    _fields_ = [("model", C.c_double * 12), ("sample", C.c_int32 * 8), ("hypothesis", C.c_int32), ("slot", C.c_int32), ("inliers", C.c_int32),
+                ("models_valid", C.c_int32), ("confidence_reached", C.c_int32), ("reserved", C.c_int32)]
+
+    def model_array(self):
+        return np.array(self.model[:], dtype=np.float64)
+
+    def sample_array(self):
+        return np.array(self.sample[:], dtype=np.int32)
+
+
+SRL_CONSENSUS_FUNDAMENTAL, SRL_CONSENSUS_PNP = 0, 1
+SRL_CONSENSUS_MAX_POINTS = 4096
+SRL_CONSENSUS_MAX_HYPOTHESES = 4096
+
+
 class ColorCloudOpts(C.Structure):
     """srl_color_cloud_opts: pub_point_minimum_views, the direction of the walk and the optional observation-time cut"""
     _fields_ = [("minimum_views", C.c_int32), ("reverse", C.c_int32), ("since", C.c_double)]
@@ -290,6 +312,11 @@ def load_library():
         "srl_flow_track_image": ([p, p, C.c_int, C.c_int, C.c_int64, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
         "srl_flow_levels": ([p, C.POINTER(C.c_int)], C.c_int),
         "srl_flow_download_level": ([p, C.c_int, C.c_int, p, p, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "srl_consensus_opts_default": ([C.POINTER(ConsensusOpts), C.c_int], None),
+        "srl_consensus_fundamental": ([p, p, p, C.c_int, C.POINTER(ConsensusOpts), p, C.POINTER(ConsensusResult)], C.c_int),
+        "srl_consensus_pnp": ([p, p, p, C.c_int, dp, C.POINTER(ConsensusOpts), p, C.POINTER(C.c_int), C.POINTER(ConsensusResult)], C.c_int),
+        "srl_oft_use_device_consensus": ([p, dp, C.POINTER(ConsensusOpts), C.POINTER(ConsensusOpts)], C.c_int),
+        "srl_oft_last_consensus": ([p, C.c_int, C.POINTER(ConsensusResult)], C.c_int),
         "srl_oft_create": ([p, C.POINTER(p)], C.c_int),
         "srl_oft_destroy": ([p], C.c_int),
         "srl_oft_set_maximum_tracked_points": ([p, C.c_int], C.c_int),
@@ -534,6 +561,24 @@ def default_color_track_opts(**kw):
 def default_flow_opts(**kw):
     o = FlowOpts()
     load_library().srl_flow_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_consensus_opts(model, **kw):
+    o = ConsensusOpts()
+    load_library().srl_consensus_opts_default(C.byref(o), int(model))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _consensus_opts(model, opts, kw):
+    """opts (None = the model's defaults) with the keywords applied to a copy"""
+    if opts is None:
+        return default_consensus_opts(model, **kw)
+    o = ConsensusOpts(opts.threshold, opts.confidence, opts.hypotheses, opts.seed)
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -818,6 +863,38 @@ class Context:
             self._chk(self.lib.srl_color_map_select(self.h, C.byref(camera), int(rows), int(cols), lp, len(v), C.byref(o), _ptr(out), len(out),
                                                     C.byref(tot)), "srl_color_map_select")
         return out, tot
+
+    def consensus_fundamental(self, last_xy, cur_xy, opts=None, **kw):
+        """srl_consensus_fundamental: last_xy, cur_xy (n, 2) float32; opts = ConsensusOpts (None = 1.0, 0.997, 512, seed 0; keywords
+        override fields).  Returns (mask (n,) uint8, ConsensusResult)."""
+        a = np.ascontiguousarray(last_xy, dtype=np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(cur_xy, dtype=np.float32).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("last_xy and cur_xy differ in length")
+        o = _consensus_opts(SRL_CONSENSUS_FUNDAMENTAL, opts, kw)
+        n = len(a)
+        mask = np.zeros(n, dtype=np.uint8)
+        res = ConsensusResult()
+        self._chk(self.lib.srl_consensus_fundamental(self.h, _ptr(a) if n else None, _ptr(b) if n else None, n, C.byref(o), _ptr(mask) if n else None,
+                                                     C.byref(res)), "srl_consensus_fundamental")
+        return mask, res
+
+    def consensus_pnp(self, xyz, uv, fx_fy_cx_cy, opts=None, **kw):
+        """srl_consensus_pnp: xyz (n, 3), uv (n, 2) float32, the intrinsics fx, fy, cx, cy; opts = ConsensusOpts (None = 1.5, 0.99, 200,
+        seed 0; keywords override fields).  Returns (ascending inlier indices int32, ConsensusResult)."""
+        x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        if len(x) != len(u):
+            raise ValueError("xyz and uv differ in length")
+        K = _f64(fx_fy_cx_cy, (4,))
+        o = _consensus_opts(SRL_CONSENSUS_PNP, opts, kw)
+        n = len(x)
+        idx = np.zeros(n, dtype=np.int32)
+        cnt = C.c_int()
+        res = ConsensusResult()
+        self._chk(self.lib.srl_consensus_pnp(self.h, _ptr(x) if n else None, _ptr(u) if n else None, n, _dptr(K), C.byref(o), _ptr(idx) if n else None,
+                                             C.byref(cnt), C.byref(res)), "srl_consensus_pnp")
+        return idx[:cnt.value].copy(), res
 
     def color_map_track_update(self, camera, rows, cols, tracked, candidates, opts=None, with_outcomes=True, totals_only=False):
         """srl_color_map_track_update: camera = ColorCamera, tracked = COLOR_TRACK_POINT_DTYPE records in the caller's order, candidates =
@@ -1383,6 +1460,22 @@ class Oft:
                 self._view(out, cap, COLOR_TRACK_POINT_DTYPE), tot.contents)))
         self._keep["update"] = cb
         self._chk(self.lib.srl_oft_set_update_provider(self.h, cb, None), "srl_oft_set_update_provider")
+
+    def use_device_consensus(self, fx_fy_cx_cy, fundamental_opts=None, pnp_opts=None):
+        """srl_oft_use_device_consensus: the context's own consensus estimators as the fundamental and the PnP provider (NOT OpenCV's
+        results: see srlivo_hip.h).  Raises SrlError(SRL_ERR_NO_DEVICE) on a handle made without a context."""
+        K = _f64(fx_fy_cx_cy, (4,))
+        self._chk(self.lib.srl_oft_use_device_consensus(self.h, _dptr(K), C.byref(fundamental_opts) if fundamental_opts is not None else None,
+                                                        C.byref(pnp_opts) if pnp_opts is not None else None), "srl_oft_use_device_consensus")
+        # a refused call installs nothing, so the handle may still call through earlier Python providers: let go of them only now
+        self._keep.pop("fundamental", None)
+        self._keep.pop("pnp", None)
+
+    def last_consensus(self, which):
+        """srl_oft_last_consensus: the ConsensusResult of the handle's last device call, which = 0 fundamental, 1 PnP"""
+        res = ConsensusResult()
+        self._chk(self.lib.srl_oft_last_consensus(self.h, int(which), C.byref(res)), "srl_oft_last_consensus")
+        return res
 
     @staticmethod
     def _gray(gray):

@@ -1,4 +1,5 @@
-// opticalFlowTracker.cpp (host mirror) -- see opticalFlowTracker.h.  The C handle of include/srlivo_host.h (srl_oft_*) is at the end.
+// opticalFlowTracker.cpp (host mirror) -- see opticalFlowTracker.h.  The C handle of include/srlivo_host.h (srl_oft_*) is at the end;
+// useDeviceConsensus and its two C functions are opticalFlowTrackerDevice.cpp.
 #include "opticalFlowTracker.h"
 #include "../../../include/srlivo_host.h"
 
@@ -145,7 +146,11 @@ bool opticalFlowTracker::removeOutlierUsingRansacPnp(int if_remove_ourlier, bool
     const int n = (int)map_ptr.size();
     std::vector<int32_t> inliers((size_t)n);
     int n_inliers = 0;
-    if (pnp(points_3d.data(), points_2d.data(), n, inliers.data(), &n_inliers) != SRL_OK) return true;      // the caught cv::Exception: return 0
+    {
+        const int rc = pnp(points_3d.data(), points_2d.data(), n, inliers.data(), &n_inliers);
+        if (rc != SRL_OK && pnp_is_device) { status = rc; return false; }  // the device's estimator throws nothing: its failure is the handle's
+        if (rc != SRL_OK) return true;                                      // the caught cv::Exception: return 0
+    }
     if (n_inliers < 0 || n_inliers > n) { status = SRL_ERR_BAD_ARG; return false; }
     for (int i = 0; i < n_inliers; i++)
         if (inliers[i] < 0 || inliers[i] >= n) { status = SRL_ERR_BAD_ARG; return false; }
@@ -220,11 +225,6 @@ std::vector<srl_color_vio_point> opticalFlowTracker::trackedForVio() const {
 
 }  // namespace srlivo
 
-struct srl_oft {
-    srlivo::opticalFlowTracker t;
-    explicit srl_oft(srl_ctx *ctx) : t(ctx) {}
-};
-
 extern "C" {
 int srl_oft_create(srl_ctx *ctx, srl_oft **out) {
     if (!out) return SRL_ERR_BAD_ARG;
@@ -253,6 +253,7 @@ int srl_oft_set_pnp_provider(srl_oft *h, srl_oft_pnp_provider fn, void *user) {
     if (!h) return SRL_ERR_BAD_ARG;
     if (fn) h->t.pnp = [fn, user](const float *xyz, const float *uv, int n, int32_t *in, int *nin) { return fn(xyz, uv, n, in, nin, user); };
     else h->t.pnp = nullptr;
+    h->t.pnp_is_device = false;
     return SRL_OK;
 }
 int srl_oft_set_update_provider(srl_oft *h, srl_oft_update_provider fn, void *user) {

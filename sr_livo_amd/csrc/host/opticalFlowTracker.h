@@ -1,8 +1,11 @@
 // opticalFlowTracker.h (host mirror) -- class opticalFlowTracker (include/opticalFlowTracker.h, src/opticalFlowTracker.cpp) without
 // OpenCV: the bookkeeping that ties srl_color_map_select, srl_flow_track_image, srl_color_map_vio_rows and
 // srl_color_map_track_update into the loop of imageProcessing::process (imageProcessing.cpp:137-161).  The optical flow and
-// updateAndAppendTrackPoints are one device call each (or a provider with its signature); cv::findFundamentalMat and
-// cv::solvePnPRansac are the caller's, reached through providers -- nothing of them is computed here.
+// updateAndAppendTrackPoints are one device call each (or a provider with its signature).  cv::findFundamentalMat and
+// cv::solvePnPRansac are reached through providers: the caller's own OpenCV, or -- after useDeviceConsensus -- this library's consensus
+// estimators on the handle's context (srl_consensus_fundamental, srl_consensus_pnp).  Those are NOT OpenCV's results and claim no
+// parity with them; they stand in soundly because the reference reads only the inlier mask / list of either call, and OpenCV's own
+// mask depends on its private random generator.  With neither, both steps refuse.
 //
 // State is kept by POOL POSITION (srl_color_selected.pool) where the reference keys by rgbPoint pointer: wherever it iterates a
 // std::map keyed by pointer value -- an order that is not reproducible -- the mirror iterates by ascending pool position
@@ -65,6 +68,13 @@ public:
     FundamentalProvider fundamental;                                        // none: trackImage refuses with SRL_ERR_BAD_ARG
     PnpProvider pnp;                                                        // none: removeOutlierUsingRansacPnp refuses with SRL_ERR_BAD_ARG
     UpdateProvider update;                                                  // default: srl_color_map_track_update on ctx
+    // useDeviceConsensus: setIntrinsic (:104-109) plus the two cv:: calls on ctx.  A provider set later replaces it.  While it is in
+    // place a failing PnP call is a failure of the handle (status), not the cv::Exception the reference catches
+    bool pnp_is_device = false;
+    double intrinsic[4] = {0.0, 0.0, 0.0, 0.0};                             // fx, fy, cx, cy
+    srl_consensus_opts consensus_opts[2] = {};                              // [0] fundamental, [1] PnP
+    srl_consensus_result last_consensus[2] = {};                            // of the last device call of either kind (zeros: none yet)
+    int useDeviceConsensus(const double *fx_fy_cx_cy, const srl_consensus_opts *fundamental_opts, const srl_consensus_opts *pnp_opts);
 
     // :188-197; records: rgb_points_vec with points_2d_vec (pool, position, u, v).  false: a call refused or failed (status)
     bool init(const srl_color_selected *records, int n, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end);
@@ -88,3 +98,10 @@ private:
 };
 
 }  // namespace srlivo
+
+// the C handle of include/srlivo_host.h (srl_oft_*): opticalFlowTracker.cpp, and opticalFlowTrackerDevice.cpp for the two functions
+// that reach srl_consensus_* -- a translation unit of their own, so that the mirror links without the device library
+struct srl_oft {
+    srlivo::opticalFlowTracker t;
+    explicit srl_oft(srl_ctx *ctx) : t(ctx) {}
+};

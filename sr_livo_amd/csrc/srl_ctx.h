@@ -97,6 +97,7 @@ struct srl_ctx {
     bool frame_world_seen = false;     // a frame has been committed at some time (srl_color_map_insert tells "never" from "a newer frame since")
     struct SrlColorMap *color = nullptr;   // the colour voxel map (srl_color_kernels.hip); nullptr until srl_color_map_create
     struct SrlFlow *flow = nullptr;        // the optical-flow tracker (srl_flow.hip); nullptr until srl_flow_create
+    struct SrlConsensus *consensus = nullptr;   // workspace of srl_consensus_* (srl_consensus.hip): made by the first call, freed by srl_consensus_release
     // undistorted sweep (srl_frame_undistort): inputs, imu_point, corrected raw_point
     double *d_corr_in = nullptr, *d_corr_rel = nullptr, *d_corr_imu = nullptr, *d_corr_raw = nullptr;
     int *d_corr_seg = nullptr;
@@ -287,6 +288,8 @@ struct srl_ctx {
 // that nobody fires would hold the stream until its bound)
 extern "C" int srl_ctx_disarm(srl_ctx *ctx);
 #define SRL_DISARM(ctx) do { if ((ctx)->armed) { int rcd__ = srl_ctx_disarm(ctx); if (rcd__) return rcd__; } } while (0)
+// frees the consensus workspace (srl_consensus.hip); srl_ctx_destroy calls it
+extern "C" void srl_consensus_release(srl_ctx *ctx);
 
 // frame pipeline stage stamps (only while srl_debug_frame_timing is on): close stage `slot` here
 #include <chrono>

@@ -222,8 +222,9 @@ int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_co
  * cloudMap.h:51-66) lives in HBM beside the point pool, 40 bytes per stored point, allocated at the first srl_color_image_upload; zero
  * bytes are rgbPoint::reset().  selectPointsForProjection is srl_color_map_select below, the measurement loops of vioEsikf and of
  * vioPhotometric are srl_color_map_vio_rows, the optical flow is srl_flow_track_image, the inlier sets the reference takes from findFundamentalMat and
- * solvePnPRansac have a stand-in of this library's own (srl_consensus_*, not OpenCV's results); the rest of the vision stage (undistortion and
- * equalisation of the image, the publishers) stays with the caller.
+ * solvePnPRansac have a stand-in of this library's own (srl_consensus_*, not OpenCV's results), and so have the undistortion and the
+ * equalisation of the image (srl_image_prepare: this library's specified operations, not OpenCV's bytes); the rest of the vision stage
+ * (cv::resize at a ratio other than 1, the publishers) stays with the caller.
  *
  * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
  *   p = (double) stored FP32 position; pc = R_cw p + t_cw with q_cw = q_world_camera.inverse(), R_cw = q_cw.toRotationMatrix(),
@@ -253,7 +254,8 @@ typedef struct srl_color_camera {
 typedef struct srl_color_render_totals { int64_t listed, behind, outside, gated, first, updated, unknown; } srl_color_render_totals;
 #define SRL_COLOR_IMAGE_MAX_PIXELS 67108864
 /* rgb_image of the frame (cloudFrame::rgb_image: 8-bit, 3 channels, BGR as OpenCV holds it; getRgb returns channels 0, 1, 2 as they lie),
- * already undistorted and equalised by the caller (imageProcessing.cpp:113-125).  Copied through page-locked staging into a device buffer
+ * already undistorted and equalised (imageProcessing.cpp:113-125) by the caller -- srl_image_prepare does both on the device and
+ * installs its result here without this call.  Copied through page-locked staging into a device buffer
  * that is reused while the size stays the same; the call returns when the staging copy is made, the DMA is ordered in front of the next
  * render.  The first upload allocates the colour state.  NULL, rows or cols < 2, rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS or
  * row_stride_bytes < 3 cols: SRL_ERR_BAD_ARG; no colour map: SRL_ERR_NO_MAP; more than one rank: SRL_ERR_UNSUPPORTED -- all before a
@@ -455,9 +457,10 @@ int srl_color_map_track_update(srl_ctx *ctx, const srl_color_camera *cam, int im
  * and the pyramidal Lucas-Kanade track of n points (calculateLKOpticalFlow, :174-496, one channel, err = nullptr, no initial flow)
  * from the PREVIOUS image and ITS derivatives to the image given.  The two pyramid sets are then swapped.  next_xy and status are
  * bitwise the reference's: its float statements in its order, its SSE accumulation order, nextPts written before the range tests,
- * status cleared at level 0 only.  With the caller stay reduce_vector, cv::findFundamentalMat, solvePnPRansac, CLAHE, cvtColor,
- * undistortion and the bookkeeping of opticalFlowTracker.  gray is the caller's equalised gray image, an upload of its own (it is no
- * function of the image of srl_color_image_upload).
+ * status cleared at level 0 only.  With the caller stay reduce_vector and the bookkeeping of opticalFlowTracker (the
+ * host mirror's); cv::findFundamentalMat and solvePnPRansac have srl_consensus_*, and CLAHE, cvtColor and the undistortion have
+ * srl_image_prepare, as stand-ins of this library's own.  gray is the caller's equalised gray image, an upload of its own (it is no
+ * function of the image of srl_color_image_upload); srl_flow_track_prepared tracks on srl_image_prepare's gray image without an upload.
  * The first image of a tracker is only stored: next_xy = prev_xy, status is not written, *n_tracked = 0.  Every later call writes
  * next_xy (n x 2 floats, x then y) and status (n bytes) for ALL points and *n_tracked = the number of status == 1.  n == 0 is accepted
  * (the pyramid is still built and swapped).
@@ -536,6 +539,74 @@ int srl_consensus_fundamental(srl_ctx *ctx, const float *last_xy, const float *c
                               srl_consensus_result *result);
 int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, const double *fx_fy_cx_cy, const srl_consensus_opts *opts,
                       int32_t *inliers, int *n_inliers, srl_consensus_result *result);
+
+/* ------------------------------------------------------------------ image preparation of the camera stage
+ * stands where imageProcessing::process (imageProcessing.cpp:113-125, :166-200) calls cv::remap with the maps of
+ * initUndistortRectifyMap(..., CV_16SC2) (:103), cvtColor(COLOR_RGB2GRAY) + imageEqualize(gray, 3.0) and equalizeColorImageYcrcb: one raw
+ * BGR frame in, the equalised gray image (srl_flow_track_prepared's) and the equalised BGR image (the colour map's, as by
+ * srl_color_image_upload) out, nothing in between on the host.  As for the consensus estimators, these are operations OF THIS LIBRARY,
+ * specified here and checked against an independent restatement; they claim NO equality with OpenCV's bytes.  Followed from OpenCV: the
+ * CV_16SC2 map layout with 5 fractional bits, the 15-bit fixed-point bilinear weights, the 15-bit gray and 14-bit YCrCb coefficients,
+ * CLAHE's clip / redistribute / bilinear-LUT structure and the reference's tile rule.  The one deliberate difference: the map is the
+ * explicit formula below on (j - cx) / fx (OpenCV iterates an inverse camera matrix along the row); DESIGN.md section 4.5 lists the rest.
+ * cv::resize stays with the caller (image_resize_ratio is 1.0 in the reference, :11).
+ * Notation: DESCALE(x, n) = (x + (1 << (n - 1))) >> n with an arithmetic shift; sat8 clamps to 0 ... 255; rne = round half to even.
+ * (a) map, built once per preparer on the HOST in FP64, no contraction (srl_image_prep_build_map: pure, no device).  For destination
+ *     pixel (column j, row i): x = (j - cx) / fx, y = (i - cy) / fy, r2 = x x + y y, kr = 1 + ((k3 r2 + k2) r2 + k1) r2,
+ *     xd = x kr + (p1 (2 x y) + p2 (r2 + 2 x x)), yd = y kr + (p1 (r2 + 2 y y) + p2 (2 x y)), u = fx xd + cx, v = fy yd + cy,
+ *     iu = rne(u 32), iv = rne(v 32) as int32; map1 = (iu >> 5, iv >> 5) as int16 x 2, each clamped to the int16 range;
+ *     map2 = (iv & 31) 32 + (iu & 31) as uint16.  A u or v that is not finite, or |u 32| or |v 32| >= 2^31 - 1: map1 = (-32768, -32768),
+ *     map2 = 0 (wholly outside the image).
+ * (b) remap, 8 bit x 3 channels, constant border 0: (sx, sy) = map1, ax = map2 & 31, ay = map2 >> 5, w00 = (32 - ax)(32 - ay) 32,
+ *     w01 = ax (32 - ay) 32, w10 = (32 - ax) ay 32, w11 = ax ay 32 (sum 32768); per channel
+ *     out = (w00 p(sy, sx) + w01 p(sy, sx + 1) + w10 p(sy + 1, sx) + w11 p(sy + 1, sx + 1) + 16384) >> 15, a neighbour outside = 0.
+ * (c) gray = (9798 c0 + 19235 c1 + 3735 c2 + 16384) >> 15: the reference calls COLOR_RGB2GRAY on a BGR-held image, so channel 0 gets
+ *     the red weight.
+ * (d) BGR -> YCrCb, channels b, g, r as they lie: Y = DESCALE(1868 b + 9617 g + 4899 r, 14),
+ *     Cr = sat8(DESCALE((r - Y) 11682 + (128 << 14), 14)), Cb = sat8(DESCALE((b - Y) 9241 + (128 << 14), 14)).
+ * (e) YCrCb -> BGR: b = sat8(Y + DESCALE((Cb - 128) 29049, 14)), g = sat8(Y + DESCALE((Cb - 128)(-5636) + (Cr - 128)(-11698), 14)),
+ *     r = sat8(Y + DESCALE((Cr - 128) 22987, 14)).
+ * (f) CLAHE(plane, clip), clip = 3.0 for gray, 1.0 for Y (:124, :195).  T x T tiles, T = max((int)(cols 32.0 / 640), 4) (:169; both
+ *     counts from cols) unless opts->tiles gives T.  If cols % T != 0 or rows % T != 0 the plane is extended on the right by T - cols % T
+ *     and at the bottom by T - rows % T (a dimension that divided grows by a whole T) with reflect-101 (index 2 (n - 1) - k); otherwise
+ *     not at all.  Tile tw x th = extended / T, area = tw th.  Per tile: the 256-bin histogram; limit = max((int)(clip area / 256), 1) in
+ *     FP64; every bin above limit is cut to it, the cuts summed into excess; batch = excess / 256, res = excess - 256 batch; every bin
+ *     + batch; if res > 0, step = max(256 / res, 1) and bin i gets + 1 iff i % step == 0 and i / step < res;
+ *     lut[i] = sat8(rne((float)cumsum_i (255.0f / (float)area))), quotient and product FP32.  Per pixel (x, y) of the plane, all FP32:
+ *     txf = (float)x (1.0f / (float)tw) - 0.5f, tx1 = floor(txf), xa = txf - (float)tx1, xa1 = 1.0f - xa, tx2 = tx1 + 1, then tx1 clamped
+ *     up to 0 and tx2 down to T - 1; the same in y;
+ *     out = sat8(rne((lut[ty1][tx1][v] xa1 + lut[ty1][tx2][v] xa) ya1 + (lut[ty2][tx1][v] xa1 + lut[ty2][tx2][v] xa) ya)).
+ * The chain: undist = remap(raw); gray_eq = CLAHE(gray(undist), 3.0); bgr_eq = YCrCb->BGR(CLAHE(Y, 1.0), Cr, Cb) of undist.  Integer
+ * arithmetic and uncontracted IEEE FP32: the same input gives the same bytes, call after call.
+ *
+ * srl_image_prepare copies the raw image through page-locked staging (one upload), runs the chain on the device and keeps both results;
+ * when the context has a colour map, bgr_eq is left as the map's image exactly as if handed to srl_color_image_upload (the colour state
+ * is allocated on the first image) and info->installed_color = 1.  Synchronous.  srl_image_prep_download: which = 0 gray_eq (rows x cols),
+ * 1 bgr_eq (rows x cols x 3).  srl_flow_track_prepared is srl_flow_track_image with the prepared gray_eq as its image and no host round
+ * trip (first image of a tracker: next = prev, *n_tracked = 0, as there).
+ * Before a device is touched -- SRL_ERR_BAD_ARG: NULL arguments (info may be NULL); rows or cols outside 16 ... SRL_FLOW_MAX_EXTENT;
+ * rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS; rows <= T or cols <= T (the reflection would leave the image); tiles given and below 2 or
+ * above min(rows, cols) / 2; intrinsics or coefficients that are not finite, fx or fy equal to 0, a clip that is not finite and positive;
+ * row_stride_bytes below a row; an image whose size differs from the preparer's (or, for srl_flow_track_prepared, from the tracker's
+ * first image); a second create; n as for srl_flow_track_image.  SRL_ERR_NO_MAP: no preparer, or srl_flow_track_prepared without a
+ * tracker.  SRL_ERR_NO_SWEEP: a download or srl_flow_track_prepared before the first image.  SRL_ERR_UNSUPPORTED: more than one rank.
+ * A refused srl_image_prepare zeroes *info and leaves the previous results in place.  Every call cancels an armed launch;
+ * srl_ctx_destroy frees the preparer.  Device memory: 16 bytes per pixel and 512 T T bytes of look-up tables (2 MB at T = 64). */
+typedef struct srl_image_prep_opts {
+    int32_t rows, cols;
+    double fx, fy, cx, cy;
+    double dist[5];                 /* k1 k2 p1 p2 k3 */
+    double clip_gray, clip_color;   /* 3.0, 1.0 */
+    int32_t tiles, reserved;        /* 0 = the reference's rule */
+} srl_image_prep_opts;
+typedef struct srl_image_prep_info { int32_t tiles, tile_w, tile_h, ext_rows, ext_cols, limit_gray, limit_color, installed_color; } srl_image_prep_info;
+void srl_image_prep_opts_default(srl_image_prep_opts *o);      /* clips 3.0 / 1.0, everything else 0 */
+int srl_image_prep_build_map(const srl_image_prep_opts *o, int16_t *map1 /* rows x cols x 2 */, uint16_t *map2 /* rows x cols */);   /* host only */
+int srl_image_prep_create(srl_ctx *ctx, const srl_image_prep_opts *o);
+int srl_image_prep_destroy(srl_ctx *ctx);
+int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_image_prep_info *info /* or NULL */);
+int srl_image_prep_download(srl_ctx *ctx, int which /* 0 gray_eq, 1 bgr_eq */, uint8_t *out, int64_t row_stride_bytes);
+int srl_flow_track_prepared(srl_ctx *ctx, const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked);
 
 /* ------------------------------------------------------------------ colour voxel map: the coloured cloud
  * replaces: the loops of lioOptimization::pubColorPoints (lioOptimization.cpp:1210-1241), threadPubColorPoints (:1243-1344) and

@@ -136,6 +136,12 @@ int srl_debug_block_times(srl_ctx *ctx, double *out, int max_blocks, int *nblock
 enum { SRL_FLOW_PREV = 0, SRL_FLOW_CUR = 1 };
 int srl_flow_levels(srl_ctx *ctx, int *L);
 int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8_t *image_padded, int16_t *deriv_padded, int *rows, int *cols);
+/* parity tests of the image preparation (srl_image_prepare): one intermediate stage of the last image.  UNDIST: rows x cols x 3 bytes;
+ * GRAY: rows x cols; YCRCB: the Y plane (rows x cols) followed by the (Cr, Cb) pairs (rows x cols x 2), as the device holds them;
+ * LUT_GRAY, LUT_Y: T x T x 256 bytes, [ty][tx][value].  capacity: bytes of out (SRL_ERR_BAD_ARG when the stage is larger, as for a NULL
+ * argument or an unknown stage); no preparer: SRL_ERR_NO_MAP; no image yet: SRL_ERR_NO_SWEEP. */
+enum { SRL_PREP_STAGE_UNDIST = 0, SRL_PREP_STAGE_GRAY = 1, SRL_PREP_STAGE_YCRCB = 2, SRL_PREP_STAGE_LUT_GRAY = 3, SRL_PREP_STAGE_LUT_Y = 4 };
+int srl_image_prep_download_stage(srl_ctx *ctx, int stage, uint8_t *out, int64_t capacity);
 
 #ifdef __cplusplus
 }

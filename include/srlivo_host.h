@@ -293,6 +293,11 @@ int srl_lk_track_image(srl_lk *lk, const uint8_t *gray, int rows, int cols, int6
  * place a failing device call is the status of srl_oft_track_image / srl_oft_remove_outlier_using_ransac_pnp, never the "caught
  * cv::Exception" path.  Without this call (and without providers) both steps refuse as before.  srl_oft_last_consensus: the result
  * record of the handle's last device call, which = 0 fundamental, 1 PnP (zeros before the first).
+ * srl_oft_use_prepared_image(oft, on): with on != 0 srl_oft_init and srl_oft_track_image ignore their gray argument (NULL included: it is
+ * no longer the empty image) and the default flow step calls srl_flow_track_prepared on the handle's context, i.e. tracks on the gray
+ * image the last srl_image_prepare left on the device; the caller prepares every frame before it tracks.  Without the opt-in nothing
+ * changes; a flow provider still takes precedence (and is handed the arguments as given).  A handle made with a NULL ctx:
+ * SRL_ERR_NO_DEVICE.
  * srl_oft_init = init (:188-197) on rgb_points_vec / points_2d_vec as selection records; srl_oft_track_image = trackImage (:111-186):
  * gray == NULL is the empty image, fewer than 30 points only move the time, *n_cur = map_rgb_points_in_cur_image_pose.size();
  * image_rows / image_cols are the frame's (if2dPointsAvailable(x, y, 1.0, 0.05)); rejectErrorTrackingPoints is not built (the reference
@@ -318,6 +323,7 @@ int srl_oft_set_update_provider(srl_oft *oft, srl_oft_update_provider fn, void *
 int srl_oft_use_device_consensus(srl_oft *oft, const double *fx_fy_cx_cy, const srl_consensus_opts *fundamental /* NULL = default */,
                                  const srl_consensus_opts *pnp /* NULL = default */);
 int srl_oft_last_consensus(srl_oft *oft, int which /* 0 fundamental, 1 pnp */, srl_consensus_result *out);
+int srl_oft_use_prepared_image(srl_oft *oft, int on);
 int srl_oft_set_track_points(srl_oft *oft, const srl_color_selected *records, int n);
 int srl_oft_init(srl_oft *oft, const srl_color_selected *records, int n, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes,
                  double time_sweep_end);

@@ -166,6 +166,25 @@ SRL_FLOW_PREV, SRL_FLOW_CUR = 0, 1
 FLOW_BORDER = 21
 
 
+class ImagePrepOpts(C.Structure):
+    """srl_image_prep_opts: image size, intrinsics, distortion (k1 k2 p1 p2 k3), CLAHE clips, tiles per side (0 = the reference's rule)"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("dist", C.c_double * 5), ("clip_gray", C.c_double), ("clip_color", C.c_double), ("tiles", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ImagePrepInfo(C.Structure):
+    """srl_image_prep_info: the tiling of the preparer and whether the last image became the colour map's"""
+    _fields_ = [("tiles", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32), ("ext_rows", C.c_int32), ("ext_cols", C.c_int32),
+                ("limit_gray", C.c_int32), ("limit_color", C.c_int32), ("installed_color", C.c_int32)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+SRL_PREP_GRAY_EQ, SRL_PREP_BGR_EQ = 0, 1
+SRL_PREP_STAGE_UNDIST, SRL_PREP_STAGE_GRAY, SRL_PREP_STAGE_YCRCB, SRL_PREP_STAGE_LUT_GRAY, SRL_PREP_STAGE_LUT_Y = 0, 1, 2, 3, 4
+
+
 class ConsensusOpts(C.Structure):
     """srl_consensus_opts: inlier threshold (pixels), confidence, the fixed number of hypotheses, the generator's seed"""
     _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("hypotheses", C.c_int32), ("seed", C.c_uint32)]
@@ -312,6 +331,15 @@ def load_library():
         "srl_flow_track_image": ([p, p, C.c_int, C.c_int, C.c_int64, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
         "srl_flow_levels": ([p, C.POINTER(C.c_int)], C.c_int),
         "srl_flow_download_level": ([p, C.c_int, C.c_int, p, p, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "srl_image_prep_opts_default": ([C.POINTER(ImagePrepOpts)], None),
+        "srl_image_prep_build_map": ([C.POINTER(ImagePrepOpts), p, p], C.c_int),
+        "srl_image_prep_create": ([p, C.POINTER(ImagePrepOpts)], C.c_int),
+        "srl_image_prep_destroy": ([p], C.c_int),
+        "srl_image_prepare": ([p, p, C.c_int, C.c_int, C.c_int64, C.POINTER(ImagePrepInfo)], C.c_int),
+        "srl_image_prep_download": ([p, C.c_int, p, C.c_int64], C.c_int),
+        "srl_image_prep_download_stage": ([p, C.c_int, p, C.c_int64], C.c_int),
+        "srl_flow_track_prepared": ([p, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
+        "srl_oft_use_prepared_image": ([p, C.c_int], C.c_int),
         "srl_consensus_opts_default": ([C.POINTER(ConsensusOpts), C.c_int], None),
         "srl_consensus_fundamental": ([p, p, p, C.c_int, C.POINTER(ConsensusOpts), p, C.POINTER(ConsensusResult)], C.c_int),
         "srl_consensus_pnp": ([p, p, p, C.c_int, dp, C.POINTER(ConsensusOpts), p, C.POINTER(C.c_int), C.POINTER(ConsensusResult)], C.c_int),
@@ -564,6 +592,26 @@ def default_flow_opts(**kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def default_image_prep_opts(**kw):
+    """srl_image_prep_opts_default with the keywords applied (dist: a sequence of five)"""
+    o = ImagePrepOpts()
+    load_library().srl_image_prep_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, (C.c_double * 5)(*v) if k == "dist" else v)
+    return o
+
+
+def image_prep_build_map(opts):
+    """srl_image_prep_build_map (host only): (map1 (rows, cols, 2) int16, map2 (rows, cols) uint16); raises SrlError where it refuses"""
+    n = max(int(opts.rows), 0) * max(int(opts.cols), 0)
+    map1 = np.zeros((max(n, 1), 2), dtype=np.int16)
+    map2 = np.zeros(max(n, 1), dtype=np.uint16)
+    rc = load_library().srl_image_prep_build_map(C.byref(opts), _ptr(map1), _ptr(map2))
+    if rc != SRL_OK:
+        raise SrlError(rc, "srl_image_prep_build_map", "")
+    return map1[:n].reshape(opts.rows, opts.cols, 2), map2[:n].reshape(opts.rows, opts.cols)
 
 
 def default_consensus_opts(model, **kw):
@@ -1378,6 +1426,17 @@ class Flow:
                                                     _ptr(nxt) if n else None, _ptr(status) if n else None, C.byref(nt)), "srl_flow_track_image")
         return nxt, status, nt.value
 
+    def track_prepared(self, prev_xy):
+        """srl_flow_track_prepared: track_image on the gray image the context's preparer holds"""
+        pts = np.ascontiguousarray(prev_xy, dtype=np.float32).reshape(-1, 2)
+        n = len(pts)
+        nxt = np.zeros((n, 2), dtype=np.float32)
+        status = np.zeros(n, dtype=np.uint8)
+        nt = C.c_int()
+        self.ctx._chk(self.lib.srl_flow_track_prepared(self.ctx.h, _ptr(pts) if n else None, n, _ptr(nxt) if n else None, _ptr(status) if n else None,
+                                                       C.byref(nt)), "srl_flow_track_prepared")
+        return nxt, status, nt.value
+
     def levels(self):
         L = C.c_int()
         self.ctx._chk(self.lib.srl_flow_levels(self.ctx.h, C.byref(L)), "srl_flow_levels")
@@ -1391,6 +1450,47 @@ class Flow:
         der = np.zeros((r.value + 2 * FLOW_BORDER, c.value + 2 * FLOW_BORDER, 2), dtype=np.int16)
         self.ctx._chk(self.lib.srl_flow_download_level(self.ctx.h, which, level, _ptr(img), _ptr(der), C.byref(r), C.byref(c)), "srl_flow_download_level")
         return img, der
+
+
+class ImagePrep:
+    """The image preparer of a context (srl_image_prep_*): undistortion, gray, CLAHE and YCrCb equalisation on the device.  One per context."""
+
+    def __init__(self, ctx, opts=None, **kw):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.opts = opts if opts is not None else default_image_prep_opts(**kw)
+        self.open = False
+        ctx._chk(self.lib.srl_image_prep_create(ctx.h, C.byref(self.opts)), "srl_image_prep_create")
+        self.open = True
+
+    def close(self):
+        if self.open and self.ctx.h:
+            self.lib.srl_image_prep_destroy(self.ctx.h)
+        self.open = False
+
+    def prepare(self, raw_bgr):
+        """srl_image_prepare: raw_bgr (rows, cols, 3) uint8 (rows may be strided).  Returns ImagePrepInfo."""
+        b = np.asarray(raw_bgr)
+        if b.dtype != np.uint8 or b.ndim != 3 or b.shape[2] != 3 or b.strides[2] != 1 or b.strides[1] != 3 or b.strides[0] < 3 * b.shape[1]:
+            b = np.ascontiguousarray(b, dtype=np.uint8)
+        info = ImagePrepInfo()
+        self.ctx._chk(self.lib.srl_image_prepare(self.ctx.h, _ptr(b), b.shape[0], b.shape[1], b.strides[0], C.byref(info)), "srl_image_prepare")
+        return info
+
+    def download(self, which):
+        """srl_image_prep_download: SRL_PREP_GRAY_EQ -> (rows, cols) uint8, SRL_PREP_BGR_EQ -> (rows, cols, 3) uint8"""
+        shape = (self.opts.rows, self.opts.cols, 3) if which == SRL_PREP_BGR_EQ else (self.opts.rows, self.opts.cols)
+        out = np.zeros(shape, dtype=np.uint8)
+        self.ctx._chk(self.lib.srl_image_prep_download(self.ctx.h, int(which), _ptr(out), out.strides[0]), "srl_image_prep_download")
+        return out
+
+    def download_stage(self, stage, tiles):
+        """srl_image_prep_download_stage: the stage's bytes as one flat uint8 array (tiles: ImagePrepInfo.tiles, for the LUT stages)"""
+        npix = self.opts.rows * self.opts.cols
+        size = {SRL_PREP_STAGE_UNDIST: 3 * npix, SRL_PREP_STAGE_GRAY: npix, SRL_PREP_STAGE_YCRCB: 3 * npix}.get(stage, int(tiles) * int(tiles) * 256)
+        out = np.zeros(size, dtype=np.uint8)
+        self.ctx._chk(self.lib.srl_image_prep_download_stage(self.ctx.h, int(stage), _ptr(out), out.size), "srl_image_prep_download_stage")
+        return out
 
 
 class Oft:
@@ -1470,6 +1570,10 @@ class Oft:
         # a refused call installs nothing, so the handle may still call through earlier Python providers: let go of them only now
         self._keep.pop("fundamental", None)
         self._keep.pop("pnp", None)
+
+    def use_prepared_image(self, on=True):
+        """srl_oft_use_prepared_image: init / track_image ignore their gray and track on the context's prepared image"""
+        self._chk(self.lib.srl_oft_use_prepared_image(self.h, int(bool(on))), "srl_oft_use_prepared_image")
 
     def last_consensus(self, which):
         """srl_oft_last_consensus: the ConsensusResult of the handle's last device call, which = 0 fundamental, 1 PnP"""

@@ -3,8 +3,8 @@
 // without OpenCV.  The per-point loops of the two updates are one call each iteration (srl_color_map_vio_rows, or a provider with its
 // signature); what surrounds them is written statement by statement.  One algebraic difference: the reference forms the 11 x 2N gain K
 // explicitly; here A = HtH + (J0 P J0^T w)^-1, K r = A^-1 Htr and K H = A^-1 HtH come from the call's sums.
-// Optical flow is lkpyramid.h of this directory and the tracker's bookkeeping opticalFlowTracker.h; PnP / RANSAC, undistortion and equalisation stay
-// with the caller.
+// Optical flow is lkpyramid.h of this directory and the tracker's bookkeeping opticalFlowTracker.h; PnP / RANSAC (srl_consensus_*) and the
+// undistortion and equalisation of the image (srl_image_prepare) are the device library's own specified operations, not OpenCV's.
 #pragma once
 #include "../../../include/srlivo_hip.h"
 #include "cameraState.h"

@@ -49,8 +49,11 @@ int LKOpticalFlowKernel::trackImage(const uint8_t *gray, int rows, int cols, int
     std::vector<uint8_t> st(last_tracked_pts.size(), 1);
     int n_tracked = 0, L = maxLevel;
     // n == 0: the arrays may be NULL
-    last_status = srl_flow_track_image(ctx, gray, rows, cols, row_stride_bytes, n ? &last_tracked_pts[0].x : nullptr, n, n ? &next[0].x : nullptr,
-                                       n ? st.data() : nullptr, &n_tracked);
+    if (device_track)
+        last_status = device_track(n ? &last_tracked_pts[0].x : nullptr, n, n ? &next[0].x : nullptr, n ? st.data() : nullptr, &n_tracked);
+    else
+        last_status = srl_flow_track_image(ctx, gray, rows, cols, row_stride_bytes, n ? &last_tracked_pts[0].x : nullptr, n, n ? &next[0].x : nullptr,
+                                           n ? st.data() : nullptr, &n_tracked);
     if (last_status != SRL_OK) return -1;
     const bool first = !seen_image_;
     seen_image_ = true;

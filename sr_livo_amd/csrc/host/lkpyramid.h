@@ -8,6 +8,7 @@
 #include "../../../include/srlivo_hip.h"
 
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 namespace srlivo {
@@ -42,6 +43,9 @@ public:
     int trackImage(const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const std::vector<Point2f> &last_tracked_pts,
                    std::vector<Point2f> &curr_tracked_pts, std::vector<uint8_t> &status);
     int last_status = 0;
+    // when set, stands where trackImage calls srl_flow_track_image: the image is then whatever the hook tracks on, and gray, rows, cols and
+    // the stride are not read (opticalFlowTracker::usePreparedImage: srl_flow_track_prepared on ctx).  It returns a srl_status.
+    std::function<int(const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked)> device_track;
 
 private:
     srl_ctx *ctx;

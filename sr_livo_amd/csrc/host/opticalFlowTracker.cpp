@@ -81,7 +81,7 @@ bool opticalFlowTracker::trackImage(const uint8_t *gray, int rows, int cols, int
     status = SRL_OK;
     current_image_time = time_sweep_end;
     map_rgb_points_in_cur_image_pose.clear();
-    if (!gray) return true;                                                 // cur_image.empty()
+    if (!gray && !use_prepared_image) return true;                          // cur_image.empty()
 
     std::vector<uint8_t> st;
     cur_tracked_points = last_tracked_points;

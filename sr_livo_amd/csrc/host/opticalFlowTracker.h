@@ -75,6 +75,10 @@ public:
     srl_consensus_opts consensus_opts[2] = {};                              // [0] fundamental, [1] PnP
     srl_consensus_result last_consensus[2] = {};                            // of the last device call of either kind (zeros: none yet)
     int useDeviceConsensus(const double *fx_fy_cx_cy, const srl_consensus_opts *fundamental_opts, const srl_consensus_opts *pnp_opts);
+    // usePreparedImage: init and trackImage ignore their gray argument (NULL included) and the default flow step tracks on the image
+    // srl_image_prepare left on ctx (srl_flow_track_prepared).  A flow provider still takes precedence and gets the arguments as given
+    bool use_prepared_image = false;
+    int usePreparedImage(bool on);
 
     // :188-197; records: rgb_points_vec with points_2d_vec (pool, position, u, v).  false: a call refused or failed (status)
     bool init(const srl_color_selected *records, int n, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end);

@@ -1,6 +1,7 @@
-// opticalFlowTrackerDevice.cpp (host mirror) -- the opt-in of opticalFlowTracker.h that puts this library's consensus estimators
-// (srl_consensus_fundamental, srl_consensus_pnp) in the place of cv::findFundamentalMat and cv::solvePnPRansac, with its two C functions
-// of include/srlivo_host.h.  Apart from opticalFlowTracker.cpp so that the rest of the mirror links without the device library.
+// opticalFlowTrackerDevice.cpp (host mirror) -- the opt-ins of opticalFlowTracker.h: this library's consensus estimators
+// (srl_consensus_fundamental, srl_consensus_pnp) in the place of cv::findFundamentalMat and cv::solvePnPRansac, and the prepared image
+// (srl_image_prepare) in the place of the caller's gray image, with their C functions of include/srlivo_host.h.  Apart from
+// opticalFlowTracker.cpp and lkpyramid.cpp so that they link against no more of the device library than before.
 #include "opticalFlowTracker.h"
 #include "../../../include/srlivo_host.h"
 
@@ -36,12 +37,30 @@ int opticalFlowTracker::useDeviceConsensus(const double *fx_fy_cx_cy, const srl_
     return SRL_OK;
 }
 
+int opticalFlowTracker::usePreparedImage(bool on) {
+    if (!ctx) return SRL_ERR_NO_DEVICE;
+    use_prepared_image = on;
+    if (on) {
+        srl_ctx *c = ctx;
+        lk_optical_flow_kernel->device_track = [c](const float *prev_xy, int n, float *next_xy, uint8_t *st, int *n_tracked) {
+            return srl_flow_track_prepared(c, prev_xy, n, next_xy, st, n_tracked);
+        };
+    } else {
+        lk_optical_flow_kernel->device_track = nullptr;
+    }
+    return SRL_OK;
+}
+
 }  // namespace srlivo
 
 extern "C" {
 int srl_oft_use_device_consensus(srl_oft *h, const double *fx_fy_cx_cy, const srl_consensus_opts *fundamental, const srl_consensus_opts *pnp) {
     if (!h) return SRL_ERR_BAD_ARG;
     return h->t.useDeviceConsensus(fx_fy_cx_cy, fundamental, pnp);
+}
+int srl_oft_use_prepared_image(srl_oft *h, int on) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    return h->t.usePreparedImage(on != 0);
 }
 int srl_oft_last_consensus(srl_oft *h, int which, srl_consensus_result *out) {
     if (out) std::memset(out, 0, sizeof *out);

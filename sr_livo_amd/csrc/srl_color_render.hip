@@ -18,6 +18,7 @@
 #include "srl_ctx.h"
 #include "srl_color_map.h"
 #include "srl_color_project.h"
+#include "srl_image_prep.h"
 #include "srl_hash.h"
 #include "host/srl_la.h"
 
@@ -204,6 +205,24 @@ extern "C" int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows
     HIPCHK(ctx, hipEventRecord(cm->img_ev, ctx->stream));
     cm->img_pending = true;
     cm->render_on = true;                 // from here on the colour state exists and follows the pool
+    { const int rc = srl_color_state_reserve(ctx, cm); if (rc) return rc; }
+    cm->img_rows = rows; cm->img_cols = cols;
+    return SRL_OK;
+}
+
+// srl_image_prepare's hand-over: what srl_color_image_upload leaves, with the image already on the device (the caller has made the
+// upload's refusals; the copy is ordered on the context's stream behind the kernels that wrote d_bgr and in front of the next render)
+int srl_color_image_install(srl_ctx *ctx, const unsigned char *d_bgr, int rows, int cols) {
+    SrlColorMap *cm = ctx->color;
+    const size_t bytes = (size_t)cols * 3 * (size_t)rows;
+    if (bytes > cm->img_cap) {
+        if (cm->d_img) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(cm->d_img)); cm->d_img = nullptr; cm->img_cap = 0; }
+        HIPCHK(ctx, hipMalloc((void **)&cm->d_img, bytes));
+        cm->img_cap = bytes;
+    }
+    cm->img_rows = 0; cm->img_cols = 0;
+    HIPCHK(ctx, hipMemcpyAsync(cm->d_img, d_bgr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    cm->render_on = true;
     { const int rc = srl_color_state_reserve(ctx, cm); if (rc) return rc; }
     cm->img_rows = rows; cm->img_cols = cols;
     return SRL_OK;

@@ -97,6 +97,7 @@ struct srl_ctx {
     bool frame_world_seen = false;     // a frame has been committed at some time (srl_color_map_insert tells "never" from "a newer frame since")
     struct SrlColorMap *color = nullptr;   // the colour voxel map (srl_color_kernels.hip); nullptr until srl_color_map_create
     struct SrlFlow *flow = nullptr;        // the optical-flow tracker (srl_flow.hip); nullptr until srl_flow_create
+    struct SrlImagePrep *prep = nullptr;   // the image preparer (srl_image_prep.hip); nullptr until srl_image_prep_create
     struct SrlConsensus *consensus = nullptr;   // workspace of srl_consensus_* (srl_consensus.hip): made by the first call, freed by srl_consensus_release
     // undistorted sweep (srl_frame_undistort): inputs, imu_point, corrected raw_point
     double *d_corr_in = nullptr, *d_corr_rel = nullptr, *d_corr_imu = nullptr, *d_corr_raw = nullptr;

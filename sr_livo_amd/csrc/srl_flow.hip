@@ -22,7 +22,11 @@
 // columns ix ... ix + 21 and rows iy ... iy + 21 of the level, i.e. padded columns ix + 21 ... ix + 42 in [0, cols + 41] and padded rows in
 // [0, rows + 41]: exactly the first and last column and row of the (rows + 42) x (cols + 42) buffers.  A corner that is not an int32 is
 // treated as outside (the reference's cvFloor yields INT_MIN there, which its tests reject too).
+//
+// Two entries, one body (flow_track): srl_flow_track_image uploads the caller's gray image, srl_flow_track_prepared takes the equalised
+// gray image srl_image_prepare left on the device (srl_image_prep.hip); level 0 is copied from either and nothing after that differs.
 #include "srl_ctx.h"
+#include "srl_image_prep.h"
 #include "../../include/srlivo_hip_debug.h"
 
 #include <cmath>
@@ -319,15 +323,10 @@ extern "C" int srl_flow_destroy(srl_ctx *ctx) {
     return SRL_OK;
 }
 
-extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n,
-                                    float *next_xy, uint8_t *status, int *n_tracked) {
-    if (n_tracked) *n_tracked = 0;
-    if (!ctx || !gray || rows < 2 || cols < 2 || rows > SRL_FLOW_MAX_EXTENT || cols > SRL_FLOW_MAX_EXTENT || row_stride_bytes < (int64_t)cols || n < 0 ||
-        n > SRL_FLOW_MAX_POINTS || (n > 0 && (!prev_xy || !next_xy || !status)))
-        return SRL_ERR_BAD_ARG;
-    SrlFlow *f = ctx->flow;
-    if (!f) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
-    if (f->rows && (rows != f->rows || cols != f->cols)) { ctx->err = "flow: the image size differs from the tracker's first image"; return SRL_ERR_BAD_ARG; }
+// Everything of a track call behind its refusals.  The image is either the caller's (gray: staged and uploaded) or one a kernel of this
+// context's stream has left on the device (d_prepared: rows x cols bytes, packed) -- from there on the two entries are one.
+static int flow_track(srl_ctx *ctx, SrlFlow *f, const uint8_t *gray, const unsigned char *d_prepared, int rows, int cols, int64_t row_stride_bytes,
+                      const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked) {
     SRL_DISARM(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -342,8 +341,8 @@ extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows,
             if (e == hipSuccess) e = hipMemsetAsync(f->d_img[k], 0, f->img_bytes, st);
             if (e == hipSuccess) e = hipMemsetAsync(f->d_der[k], 0, f->der_pairs * 2 * sizeof(short), st);
         }
-        if (e == hipSuccess) e = hipMalloc((void **)&f->d_gray, gray_bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_gray, gray_bytes, hipHostMallocDefault);
+        if (e == hipSuccess && gray) e = hipMalloc((void **)&f->d_gray, gray_bytes);
+        if (e == hipSuccess && gray) e = hipHostMalloc((void **)&f->h_gray, gray_bytes, hipHostMallocDefault);
         if (e != hipSuccess) {
             flow_free(f);
             f->d_img[0] = f->d_img[1] = f->d_gray = f->h_gray = nullptr; f->d_der[0] = f->d_der[1] = nullptr;
@@ -363,14 +362,21 @@ extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows,
         f->pts_cap = cap;
     }
     // the current image's pyramid and derivatives into set 1 (every call ends synchronised, so the staging block is free)
-    if (row_stride_bytes == (int64_t)cols) std::memcpy(f->h_gray, gray, gray_bytes);
-    else for (int r = 0; r < rows; r++) std::memcpy(f->h_gray + (size_t)r * cols, gray + (size_t)r * (size_t)row_stride_bytes, (size_t)cols);
-    HIPCHK(ctx, hipMemcpyAsync(f->d_gray, f->h_gray, gray_bytes, hipMemcpyHostToDevice, st));
+    const unsigned char *d_level0 = d_prepared;
+    if (gray) {
+        // (a tracker whose first image was a prepared one has no upload buffers yet)
+        if (!f->d_gray) HIPCHK(ctx, hipMalloc((void **)&f->d_gray, gray_bytes));
+        if (!f->h_gray) HIPCHK(ctx, hipHostMalloc((void **)&f->h_gray, gray_bytes, hipHostMallocDefault));
+        if (row_stride_bytes == (int64_t)cols) std::memcpy(f->h_gray, gray, gray_bytes);
+        else for (int r = 0; r < rows; r++) std::memcpy(f->h_gray + (size_t)r * cols, gray + (size_t)r * (size_t)row_stride_bytes, (size_t)cols);
+        HIPCHK(ctx, hipMemcpyAsync(f->d_gray, f->h_gray, gray_bytes, hipMemcpyHostToDevice, st));
+        d_level0 = f->d_gray;
+    }
     for (int level = 0; level <= f->max_level; level++) {
         const SrlFlowLevel &V = f->lev[level];
         const size_t padded = (size_t)(V.rows + 2 * FLOW_WIN) * (size_t)(V.cols + 2 * FLOW_WIN);
         const unsigned nb = (unsigned)((padded + 255) / 256);
-        if (level == 0) hipLaunchKernelGGL(k_flow_level0, dim3(nb), dim3(256), 0, st, f->d_gray, f->d_img[1] + V.img_at, V.rows, V.cols);
+        if (level == 0) hipLaunchKernelGGL(k_flow_level0, dim3(nb), dim3(256), 0, st, d_level0, f->d_img[1] + V.img_at, V.rows, V.cols);
         else hipLaunchKernelGGL(k_flow_down, dim3(nb), dim3(256), 0, st, f->d_img[1] + f->lev[level - 1].img_at, f->lev[level - 1].rows, f->lev[level - 1].cols,
                                 f->d_img[1] + V.img_at, V.rows, V.cols);
         hipLaunchKernelGGL(k_flow_scharr, dim3(nb), dim3(256), 0, st, f->d_img[1] + V.img_at, reinterpret_cast<short2 *>(f->d_der[1] + V.der_at * 2), V.rows, V.cols);
@@ -411,6 +417,30 @@ extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows,
         if (n_tracked) *n_tracked = cnt;
     }
     return SRL_OK;
+}
+
+extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows, int cols, int64_t row_stride_bytes, const float *prev_xy, int n,
+                                    float *next_xy, uint8_t *status, int *n_tracked) {
+    if (n_tracked) *n_tracked = 0;
+    if (!ctx || !gray || rows < 2 || cols < 2 || rows > SRL_FLOW_MAX_EXTENT || cols > SRL_FLOW_MAX_EXTENT || row_stride_bytes < (int64_t)cols || n < 0 ||
+        n > SRL_FLOW_MAX_POINTS || (n > 0 && (!prev_xy || !next_xy || !status)))
+        return SRL_ERR_BAD_ARG;
+    SrlFlow *f = ctx->flow;
+    if (!f) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
+    if (f->rows && (rows != f->rows || cols != f->cols)) { ctx->err = "flow: the image size differs from the tracker's first image"; return SRL_ERR_BAD_ARG; }
+    return flow_track(ctx, f, gray, nullptr, rows, cols, row_stride_bytes, prev_xy, n, next_xy, status, n_tracked);
+}
+
+extern "C" int srl_flow_track_prepared(srl_ctx *ctx, const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked) {
+    if (n_tracked) *n_tracked = 0;
+    if (!ctx || n < 0 || n > SRL_FLOW_MAX_POINTS || (n > 0 && (!prev_xy || !next_xy || !status))) return SRL_ERR_BAD_ARG;
+    SrlFlow *f = ctx->flow;
+    if (!f) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
+    const SrlImagePrep *p = ctx->prep;
+    if (!p) { ctx->err = "no image preparer (srl_image_prep_create)"; return SRL_ERR_NO_MAP; }
+    if (!p->have_image) { ctx->err = "image preparer: no image yet (srl_image_prepare)"; return SRL_ERR_NO_SWEEP; }
+    if (f->rows && (p->rows != f->rows || p->cols != f->cols)) { ctx->err = "flow: the image size differs from the tracker's first image"; return SRL_ERR_BAD_ARG; }
+    return flow_track(ctx, f, nullptr, p->d_gray_eq, p->rows, p->cols, p->cols, prev_xy, n, next_xy, status, n_tracked);
 }
 
 extern "C" int srl_flow_levels(srl_ctx *ctx, int *L) {

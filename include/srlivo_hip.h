@@ -522,7 +522,9 @@ int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows, int cols, 
  * n > SRL_CONSENSUS_MAX_POINTS, a NULL array with n > 0, NULL n_inliers or intrinsics, hypotheses outside 1 ... SRL_CONSENSUS_MAX_HYPOTHESES,
  * a threshold that is not finite and positive, a confidence outside (0, 1), intrinsics that are not finite, fx or fy equal to 0.
  * opts == NULL: the defaults; result may be NULL.  More than one rank: SRL_ERR_UNSUPPORTED.  Synchronous; cancels an armed launch.  The
- * workspace (about 2 MB of device memory) is allocated at a context's first call and freed with the context. */
+ * workspace (about 2 MB of device memory) is allocated at a context's first call and freed with the context; it is shared by both models
+ * and never cleared, and no call depends on what it held (srl_debug_consensus_download of srlivo_hip_debug.h reads the usable list, the
+ * normalisation and every hypothesis' sample, models and counts of the last call back for the tests of all the above). */
 #define SRL_CONSENSUS_FUNDAMENTAL 0
 #define SRL_CONSENSUS_PNP 1
 #define SRL_CONSENSUS_MAX_POINTS 4096

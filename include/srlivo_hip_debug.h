@@ -142,6 +142,19 @@ int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8_t *image_p
  * argument or an unknown stage); no preparer: SRL_ERR_NO_MAP; no image yet: SRL_ERR_NO_SWEEP. */
 enum { SRL_PREP_STAGE_UNDIST = 0, SRL_PREP_STAGE_GRAY = 1, SRL_PREP_STAGE_YCRCB = 2, SRL_PREP_STAGE_LUT_GRAY = 3, SRL_PREP_STAGE_LUT_Y = 4 };
 int srl_image_prep_download_stage(srl_ctx *ctx, int stage, uint8_t *out, int64_t capacity);
+/* tests of the consensus estimators (srl_consensus_fundamental, srl_consensus_pnp) on EVERY hypothesis: what this context's last call that
+ * ran on the device (n >= 8 / n >= 4, not refused) left in the workspace.  Synchronous; cancels an armed launch.
+ * info: model = SRL_CONSENSUS_FUNDAMENTAL / _PNP, hypotheses = H, n, slots = 3 / 4, usable = the number of usable points, norm = Hartley's
+ *   normalisation mx1, my1, s1, mx2, my2, s2 of the two views (fundamental; six zeros after a PnP call);
+ * usable[0 .. info->usable): the usable points, ascending (the rest of the array is left alone);
+ * samples: H x 8, each hypothesis' sample indices padded with -1 (all -1: no sample);
+ * models: H x slots x 12 doubles as srl_consensus_result.model holds the winner's, twelve zeros where a slot has no model;
+ * counts: H x slots, each model's inlier count, -1 where a slot has no model.
+ * point_capacity, hypothesis_capacity: the entries of usable, and the hypotheses samples, models and counts have room for.
+ * SRL_ERR_BAD_ARG: a NULL argument, point_capacity < n or hypothesis_capacity < H; SRL_ERR_NO_MAP: no workspace yet, or no such call. */
+typedef struct srl_debug_consensus_info { int32_t model, hypotheses, n, slots, usable, reserved; double norm[6]; } srl_debug_consensus_info;
+int srl_debug_consensus_download(srl_ctx *ctx, srl_debug_consensus_info *info, int32_t *usable, int64_t point_capacity, int32_t *samples,
+                                 double *models, int32_t *counts, int64_t hypothesis_capacity);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ SRL_OK = 0
 SRL_ERR_NO_DEVICE = -1
 SRL_ERR_BAD_ARG = -3
 SRL_ERR_UNSUPPORTED = -4
+SRL_ERR_NO_MAP = -5
 SRL_ERR_COMM = -7
 SRL_ERR_NAN_PLANARITY = -8
 SRL_ERR_NOT_ENOUGH_RESIDUALS = -9
@@ -202,6 +203,12 @@ class ConsensusResult(C.Structure):
         return np.array(self.sample[:], dtype=np.int32)
 
 
+class DebugConsensusInfo(C.Structure):
+    """srl_debug_consensus_info (include/srlivo_hip_debug.h): the shape of the last consensus call and its normalisation"""
+    _fields_ = [("model", C.c_int32), ("hypotheses", C.c_int32), ("n", C.c_int32), ("slots", C.c_int32), ("usable", C.c_int32),
+                ("reserved", C.c_int32), ("norm", C.c_double * 6)]
+
+
 SRL_CONSENSUS_FUNDAMENTAL, SRL_CONSENSUS_PNP = 0, 1
 SRL_CONSENSUS_MAX_POINTS = 4096
 SRL_CONSENSUS_MAX_HYPOTHESES = 4096
@@ -345,6 +352,7 @@ def load_library():
         "srl_consensus_pnp": ([p, p, p, C.c_int, dp, C.POINTER(ConsensusOpts), p, C.POINTER(C.c_int), C.POINTER(ConsensusResult)], C.c_int),
         "srl_oft_use_device_consensus": ([p, dp, C.POINTER(ConsensusOpts), C.POINTER(ConsensusOpts)], C.c_int),
         "srl_oft_last_consensus": ([p, C.c_int, C.POINTER(ConsensusResult)], C.c_int),
+        "srl_debug_consensus_download": ([p, C.POINTER(DebugConsensusInfo), p, C.c_int64, p, p, p, C.c_int64], C.c_int),
         "srl_oft_create": ([p, C.POINTER(p)], C.c_int),
         "srl_oft_destroy": ([p], C.c_int),
         "srl_oft_set_maximum_tracked_points": ([p, C.c_int], C.c_int),
@@ -943,6 +951,21 @@ class Context:
         self._chk(self.lib.srl_consensus_pnp(self.h, _ptr(x) if n else None, _ptr(u) if n else None, n, _dptr(K), C.byref(o), _ptr(idx) if n else None,
                                              C.byref(cnt), C.byref(res)), "srl_consensus_pnp")
         return idx[:cnt.value].copy(), res
+
+    def debug_consensus_download(self):
+        """srl_debug_consensus_download: the last consensus call's trace as a dict -- model, hypotheses, n, slots, usable (ascending int32),
+        norm (6,) float64, samples (H, 8) int32, models (H, slots, 12) float64, counts (H, slots) int32 (-1: no model)"""
+        info = DebugConsensusInfo()
+        usable = np.zeros(SRL_CONSENSUS_MAX_POINTS, dtype=np.int32)
+        H = SRL_CONSENSUS_MAX_HYPOTHESES
+        samples = np.zeros((H, 8), dtype=np.int32)
+        models = np.zeros(H * 4 * 12, dtype=np.float64)
+        counts = np.zeros(H * 4, dtype=np.int32)
+        self._chk(self.lib.srl_debug_consensus_download(self.h, C.byref(info), _ptr(usable), len(usable), _ptr(samples), _ptr(models), _ptr(counts), H),
+                  "srl_debug_consensus_download")
+        H, S = info.hypotheses, info.slots
+        return dict(model=info.model, hypotheses=H, n=info.n, slots=S, usable=usable[:info.usable].copy(), norm=np.array(info.norm[:], dtype=np.float64),
+                    samples=samples[:H].copy(), models=models[:H * S * 12].reshape(H, S, 12).copy(), counts=counts[:H * S].reshape(H, S).copy())
 
     def color_map_track_update(self, camera, rows, cols, tracked, candidates, opts=None, with_outcomes=True, totals_only=False):
         """srl_color_map_track_update: camera = ColorCamera, tracked = COLOR_TRACK_POINT_DTYPE records in the caller's order, candidates =

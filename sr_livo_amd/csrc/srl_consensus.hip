@@ -29,6 +29,7 @@
 // models.  The compactions write at most as many entries as points flagged, <= n <= SRL_CONSENSUS_MAX_POINTS.  LDS of k_cons_hyp<F>:
 // 64 lanes x 81 doubles, lane-interleaved (element e of lane l at [e * 64 + l]).
 #include "srl_ctx.h"
+#include "../../include/srlivo_hip_debug.h"
 #include "srl_consensus_math.h"
 
 #include <cmath>
@@ -57,6 +58,8 @@ struct SrlConsensus {
     unsigned char *h_mask = nullptr;
     int *h_list = nullptr;
     srl_consensus_result *h_res = nullptr;
+    // the last call that ran on the workspace (srl_debug_consensus_download): its model (-1: none yet), hypotheses and points
+    int last_model = -1, last_H = 0, last_n = 0;
 };
 
 namespace {
@@ -333,6 +336,7 @@ int cons_run(srl_ctx *ctx, int n, const srl_consensus_opts *o, const double *K) 
     ConsArgs A;
     A.pts = c->d_pts; A.n = n; A.H = o->hypotheses; A.seed = o->seed; A.thr2 = o->threshold * o->threshold; A.confidence = o->confidence;
     for (int k = 0; k < 4; k++) A.K[k] = K ? K[k] : 0.0;
+    c->last_model = -1;                    // a call that fails half way leaves nothing to read back
     HIPCHK(ctx, hipMemcpyAsync(c->d_pts, c->h_pts, (size_t)n * FPP * sizeof(float), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_cons_prep<MODEL>, dim3(1), dim3(256), 0, st, A, c->d_usable, c->d_nusable, c->d_norm);
     hipLaunchKernelGGL(k_cons_hyp<MODEL>, dim3((unsigned)((A.H + 63) / 64)), dim3(64), 0, st, A, (const int *)c->d_usable, (const int *)c->d_nusable,
@@ -345,10 +349,36 @@ int cons_run(srl_ctx *ctx, int n, const srl_consensus_opts *o, const double *K) 
     HIPCHK(ctx, hipMemcpyAsync(c->h_list, c->d_list, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(c->h_res, c->d_res, sizeof(srl_consensus_result), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    c->last_model = MODEL; c->last_H = A.H; c->last_n = n;
     return SRL_OK;
 }
 
 }  // namespace
+
+extern "C" int srl_debug_consensus_download(srl_ctx *ctx, srl_debug_consensus_info *info, int32_t *usable, int64_t point_capacity, int32_t *samples,
+                                            double *models, int32_t *counts, int64_t hypothesis_capacity) {
+    if (!ctx || !info || !usable || !samples || !models || !counts) return SRL_ERR_BAD_ARG;
+    SrlConsensus *c = ctx->consensus;
+    if (!c || c->last_model < 0) return SRL_ERR_NO_MAP;
+    if (point_capacity < (int64_t)c->last_n || hypothesis_capacity < (int64_t)c->last_H) return SRL_ERR_BAD_ARG;
+    const int slots = c->last_model == CONS_F ? ConsTraits<CONS_F>::SLOTS : ConsTraits<CONS_P>::SLOTS;
+    const size_t M = (size_t)c->last_H * slots;
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    int nusable = 0;
+    HIPCHK(ctx, hipMemcpy(&nusable, c->d_nusable, sizeof(int), hipMemcpyDeviceToHost));
+    if (nusable < 0 || nusable > c->last_n) { ctx->err = "consensus: the device holds a usable count outside 0 ... n"; return SRL_ERR_HIP; }
+    std::memset(info, 0, sizeof *info);
+    info->model = c->last_model; info->hypotheses = c->last_H; info->n = c->last_n; info->slots = slots; info->usable = nusable;
+    // a PnP call computes no normalisation: its six values read 0, whatever a fundamental call before it left in the workspace
+    if (c->last_model == CONS_F) HIPCHK(ctx, hipMemcpy(info->norm, c->d_norm, 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (nusable > 0) HIPCHK(ctx, hipMemcpy(usable, c->d_usable, (size_t)nusable * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(samples, c->d_samples, (size_t)c->last_H * 8 * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(models, c->d_models, M * 12 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(counts, c->d_flags, M * sizeof(int), hipMemcpyDeviceToHost));
+    return SRL_OK;
+}
 
 extern "C" void srl_consensus_opts_default(srl_consensus_opts *o, int model) {
     if (!o) return;

@@ -78,14 +78,11 @@ SRL_CONS_FN double cons_polish(const double *c, int degree, double x) {      // 
 }
 // Roots come in FIXED slots, an absent one as NaN: nothing is appended at a run-time index, so the slots stay in registers.
 #define SRL_CONS_NO_ROOT (std::nan(""))
-// c[0] + c[1] x + c[2] x^2 + c[3] x^3 into r[0 .. 2]; the number of roots, 0 for a vanishing (or non-finite) leading coefficient
-SRL_CONS_FN int cons_cubic(const double *c, double *r) {
-    for (int k = 0; k < 3; k++) r[k] = SRL_CONS_NO_ROOT;
-    if (!(std::fabs(c[3]) > 1e-14 * (std::fabs(c[2]) + std::fabs(c[1]) + std::fabs(c[0])))) return 0;
-    const double a = c[2] / c[3], b = c[1] / c[3], d = c[0] / c[3];
+// the real roots of x^3 + a x^2 + b x + d in closed form into x[0 .. 2], unpolished: no test of the coefficients' scale, whatever they are
+SRL_CONS_FN void cons_cubic_monic(double a, double b, double d, double *x) {
+    for (int k = 0; k < 3; k++) x[k] = SRL_CONS_NO_ROOT;
     const double Q = (a * a - 3.0 * b) / 9.0, R = (2.0 * a * a * a - 9.0 * a * b + 27.0 * d) / 54.0;
     const double Q3 = Q * Q * Q, R2 = R * R;
-    double x[3] = {SRL_CONS_NO_ROOT, SRL_CONS_NO_ROOT, SRL_CONS_NO_ROOT};
     if (R2 < Q3) {
         double q = R / std::sqrt(Q3);
         q = q > 1.0 ? 1.0 : (q < -1.0 ? -1.0 : q);
@@ -98,6 +95,15 @@ SRL_CONS_FN int cons_cubic(const double *c, double *r) {
         const double B = A != 0.0 ? Q / A : 0.0;
         x[0] = (A + B) - a / 3.0;
     }
+}
+// c[0] + c[1] x + c[2] x^2 + c[3] x^3 into r[0 .. 2]; the number of roots, 0 for a non-finite coefficient or a leading coefficient that
+// vanishes against the others (the 7-point cubic of a degenerate sample)
+SRL_CONS_FN int cons_cubic(const double *c, double *r) {
+    for (int k = 0; k < 3; k++) r[k] = SRL_CONS_NO_ROOT;
+    if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(c[3]))) return 0;
+    if (!(std::fabs(c[3]) > 1e-14 * (std::fabs(c[2]) + std::fabs(c[1]) + std::fabs(c[0])))) return 0;
+    double x[3];
+    cons_cubic_monic(c[2] / c[3], c[1] / c[3], c[0] / c[3], x);
     int kept = 0;
     for (int k = 0; k < 3; k++) {
         const double p = std::isfinite(x[k]) ? cons_polish(c, 3, x[k]) : SRL_CONS_NO_ROOT;
@@ -109,17 +115,22 @@ SRL_CONS_FN int cons_cubic(const double *c, double *r) {
 // c[0] + ... + c[4] x^4 by Ferrari's resolvent cubic into r[0 .. 3]; up to 4 real roots, each polished on the quartic itself
 SRL_CONS_FN int cons_quartic(const double *c, double *r) {
     for (int k = 0; k < 4; k++) r[k] = SRL_CONS_NO_ROOT;
+    if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(c[3]) && std::isfinite(c[4]))) return 0;
     if (!(std::fabs(c[4]) > 1e-14 * (std::fabs(c[3]) + std::fabs(c[2]) + std::fabs(c[1]) + std::fabs(c[0])))) return 0;
     const double b3 = c[3] / c[4], b2 = c[2] / c[4], b1 = c[1] / c[4], b0 = c[0] / c[4];
     const double p = b2 - 0.375 * b3 * b3;
     const double q = b1 - 0.5 * b3 * b2 + 0.125 * b3 * b3 * b3;
     const double s = b0 - 0.25 * b3 * b1 + 0.0625 * b3 * b3 * b2 - (3.0 / 256.0) * b3 * b3 * b3 * b3;
     // (y^2 + p/2 + m)^2 = 2 m (y - q / (4 m))^2 where 8 m^3 + 8 p m^2 + (2 p^2 - 8 s) m - q^2 = 0
+    // Its leading coefficient never vanishes, however large q^2 is beside it (roots spread over decades): no test of the scale here.
     const double rc[4] = {-q * q, 2.0 * p * p - 8.0 * s, 8.0 * p, 8.0};
     double mr[3];
-    cons_cubic(rc, mr);
+    cons_cubic_monic(p, 0.25 * p * p - s, -0.125 * q * q, mr);
     double m = 0.0;
-    for (int k = 0; k < 3; k++) if (mr[k] > m) m = mr[k];
+    for (int k = 0; k < 3; k++) {
+        const double mk = std::isfinite(mr[k]) ? cons_polish(rc, 3, mr[k]) : SRL_CONS_NO_ROOT;
+        if (mk > m) m = mk;
+    }
     double y[4] = {SRL_CONS_NO_ROOT, SRL_CONS_NO_ROOT, SRL_CONS_NO_ROOT, SRL_CONS_NO_ROOT};
     if (m > 1e-14 * (std::fabs(p) + 1.0)) {
         const double w = std::sqrt(2.0 * m), t = q / (2.0 * w), h = 0.5 * p + m;

@@ -1,7 +1,8 @@
 """An independent NumPy restatement of what srl_consensus_fundamental / srl_consensus_pnp (include/srlivo_hip.h) promise -- not a port of
 the kernels: the two error functions in the header's operation order (float64, so the device's masks can be recomputed bit for bit from
 the returned model), a 7-point solver by SVD null space and np.roots, a linear six-point pose and a Gauss-Newton pose refinement that
-share nothing with the device's P3P, a plain sequential RANSAC on NumPy's own generator (used only to validate scenes), and the scene
+share nothing with the device's P3P, a plain sequential RANSAC on NumPy's own generator (used only to validate scenes), the contract's
+counter-based sampler restated from the header's text in Python integers (what every hypothesis must have drawn), and the scene
 generators of the tests: camera fx = fy = 400, cx, cy = 320, 240, image 640 x 480; points x in [-4, 4], y in [-3, 3], depth 4 ... 12 m;
 the second view rotated by 0.04 rad and moved by (0.3, 0.05, 0.1); every coordinate rounded to float32."""
 import numpy as np
@@ -75,6 +76,18 @@ def _hartley(x):
 
 def seven_point(x1, x2):
     """the up to three unit-norm fundamental matrices (3 x 3) through seven correspondences: SVD null space, np.roots"""
+    return seven_point_with_roots(x1, x2)[0]
+
+
+def close_roots(roots, rel=1e-6):
+    """whether two of the (complex) roots lie within rel of each other, relative to the larger magnitude (1 at least): a cubic so close
+    to a double root has a number of REAL roots that rounding decides"""
+    r = np.asarray(roots, dtype=np.complex128)
+    return any(abs(r[i] - r[j]) <= rel * max(1.0, abs(r[i]), abs(r[j])) for i in range(len(r)) for j in range(i + 1, len(r)))
+
+
+def seven_point_with_roots(x1, x2):
+    """(the matrices of seven_point, all three complex roots of its cubic)"""
     x1 = np.asarray(x1).astype(np.float64).reshape(7, 2)
     x2 = np.asarray(x2).astype(np.float64).reshape(7, 2)
     T1, T2 = _hartley(x1), _hartley(x2)
@@ -87,12 +100,13 @@ def seven_point(x1, x2):
     ls = np.array([-1.0, 0.0, 1.0, 2.0])
     coef = np.polyfit(ls, [np.linalg.det(l * F1 + (1 - l) * F2) for l in ls], 3)
     out = []
-    for r in np.roots(coef):
+    roots = np.roots(coef)
+    for r in roots:
         if abs(r.imag) > 1e-9 * max(1.0, abs(r.real)):
             continue
         F = T2.T @ (r.real * F1 + (1 - r.real) * F2) @ T1
         out.append(F / np.linalg.norm(F))
-    return out
+    return out, roots
 
 
 def _project(R, t, Kc, X):
@@ -262,6 +276,174 @@ def scene_all_outliers(seed, n):
     return px(), px(), X, px()
 
 
+# ------------------------------------------------------------------------------------------------ the contract's sampler
+# Written from the text of include/srlivo_hip.h in Python integers (unbounded, hence the masks): not a port of the library's code.
+_M64 = (1 << 64) - 1
+MAX_DRAWS = 64
+
+
+def draw(seed, h, k, m):
+    """draw(seed, h, k, m) of the header: a position in [0, m)"""
+    z = ((((seed & 0xFFFFFFFF) << 32) | (h & 0xFFFFFFFF)) * 0x9E3779B97F4A7C15 + (k + 1) * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return ((z >> 32) * m) >> 32
+
+
+def sample(seed, h, m, S):
+    """the S distinct positions in [0, m) of hypothesis h in the order drawn, or None: draws k = 0, 1, ..., a repeated position is rejected,
+    no sample after 64 draws (or with m < S)"""
+    if m < S:
+        return None
+    got = []
+    for k in range(MAX_DRAWS):
+        c = draw(seed, h, k, m)
+        if c not in got:
+            got.append(c)
+            if len(got) == S:
+                return got
+    return None
+
+
+def sample_indices(seed, h, usable, S):
+    """the row of eight the contract reports for hypothesis h: the sample positions mapped through the usable list, padded with -1"""
+    row = np.full(8, -1, np.int32)
+    pos = sample(seed, h, len(usable), S)
+    if pos is not None:
+        row[:S] = np.asarray(usable)[pos]
+    return row
+
+
+def usable_points(*arrays):
+    """ascending indices of the points whose coordinates are all finite"""
+    ok = np.ones(len(arrays[0]), bool)
+    for a in arrays:
+        ok &= np.isfinite(np.asarray(a, dtype=np.float64).reshape(len(a), -1)).all(axis=1)
+    return np.flatnonzero(ok).astype(np.int32)
+
+
+def hartley_values(x1, x2, usable):
+    """mx1, my1, s1, mx2, my2, s2 of the header: centroid and sqrt 2 / mean distance of the usable points of each view, float64"""
+    out = []
+    for x in (x1, x2):
+        p = np.asarray(x).astype(np.float64)[usable]
+        m = p.mean(axis=0)
+        out += [m[0], m[1], np.sqrt(2.0) / np.mean(np.sqrt(((p - m) ** 2).sum(axis=1)))]
+    return np.array(out)
+
+
+def confidence_reached(inliers, n, S, H, confidence):
+    """1 - (1 - w^S)^H >= confidence, w = inliers / n, powers by repeated multiplication in float64"""
+    w = float(inliers) / float(n) if n > 0 else 0.0
+    ws = 1.0
+    for _ in range(S):
+        ws *= w
+    miss = 1.0
+    for _ in range(H):
+        miss *= 1.0 - ws
+    return 1 if 1.0 - miss >= confidence else 0
+
+
 # the scene shapes of tests/test_gpu_consensus.py: name -> (generator, arguments); truth-mask scenes first
 FUNDAMENTAL_SCENES = {"f120": (11, 120, 42, 0.0), "f40": (12, 40, 10, 0.0), "f120_noise": (13, 120, 42, 0.05)}
 PNP_SCENES = {"p120": (21, 120, 48, 0.0), "p12": (22, 12, 2, 0.0), "p120_noise": (23, 120, 48, 0.05)}
+
+
+# ------------------------------------------------------------------------------------------------ tests/test_gpu_consensus_trace.py
+# Every hypothesis of a call is held against the contract there; what the cases need of the SAMPLES (which depend on the seed, the
+# hypothesis and the number of usable points alone) is checked on the CPU by tests/test_consensus_checker.py.
+TRACE_H = (1, 21, 22, 85, 86, 200, 512)
+TRACE_SEEDS = (0, 1, 0xFFFFFFFF)
+TRACE_FUNDAMENTAL = ("f120", "f120_noise", "f_planar", "f_random", "f120_holes")
+TRACE_PNP = ("p120", "p120_noise", "p_planar", "p_random", "p120_holes")
+TRACE_EXACT = ("f120", "f120_holes", "p120", "p120_holes")          # noise-free and not planar: one consensus, the truth mask
+# (scene, seed, H) where a LATER hypothesis sampled inside the truth inliers has all its model indices at a lower index % 256 than the first
+# such hypothesis has: a pick that broke ties by thread (256 of them stride over the models) would take the later one
+TRACE_TIE_CASES = (("f120", 0, 200), ("f120", 0, 512), ("p120", 0, 200), ("p120", 0, 512))
+
+
+def trace_scene(name):
+    """(first array, second array, truth mask or None) of a scene of the trace tests; *_holes: f120 / p120 with three true inliers made
+    non-finite (and taken out of the truth mask)"""
+    if name in ("f_random", "p_random"):
+        a, b, X, uv = scene_all_outliers(31, 90)
+        return (a, b, None) if name == "f_random" else (X, uv, None)
+    if name == "f_planar":
+        return scene_fundamental(14, 120, 42, 0.0, planar=True)
+    if name == "p_planar":
+        return scene_pnp(24, 120, 48, 0.0, planar=True)
+    if name == "f120_holes":
+        x1, x2, truth = scene_fundamental(*FUNDAMENTAL_SCENES["f120"])
+        hurt = np.flatnonzero(truth)[[0, 17, 40]]
+        x1[hurt[0], 0] = np.nan
+        x2[hurt[1], 1] = np.inf
+        x1[hurt[2]] = np.nan
+        x2[hurt[2]] = np.nan
+        truth[hurt] = 0
+        return x1, x2, truth
+    if name == "p120_holes":
+        X, uv, truth = scene_pnp(*PNP_SCENES["p120"])
+        hurt = np.flatnonzero(truth)[[1, 20, 50]]
+        X[hurt[0], 2] = np.nan
+        uv[hurt[1], 0] = -np.inf
+        X[hurt[2]] = np.nan
+        truth[hurt] = 0
+        return X, uv, truth
+    if name in FUNDAMENTAL_SCENES:
+        return scene_fundamental(*FUNDAMENTAL_SCENES[name])
+    return scene_pnp(*PNP_SCENES[name])
+
+
+_TRACE_CACHE = {}
+
+
+def trace_samples(name, seed, H=512):
+    """(usable list, rows (H, 8) of sample indices padded with -1) the contract fixes for a scene and a seed: computed once"""
+    key = ("samples", name, seed)
+    if key not in _TRACE_CACHE:
+        a, b, _ = trace_scene(name)
+        usable = usable_points(a, b)
+        S = 7 if name.startswith("f") else 3
+        _TRACE_CACHE[key] = (usable, np.array([sample_indices(seed, h, usable, S) for h in range(max(TRACE_H))]))
+    usable, rows = _TRACE_CACHE[key]
+    return usable, rows[:H]
+
+
+def trace_seven_point(name, seed, H=512):
+    """per hypothesis of a fundamental scene: (the number of real solutions the checker's seven_point finds, whether its cubic has two
+    roots within 1e-6 of each other -- the hypothesis is then excused from the comparison of that number)"""
+    key = ("seven", name, seed)
+    if key not in _TRACE_CACHE:
+        a, b, _ = trace_scene(name)
+        _, rows = trace_samples(name, seed)
+        out = []
+        for row in rows:
+            if row[0] < 0:
+                out.append((0, False))
+                continue
+            sols, roots = seven_point_with_roots(a[row[:7]], b[row[:7]])
+            out.append((len(sols), close_roots(roots)))
+        _TRACE_CACHE[key] = out
+    return _TRACE_CACHE[key][:H]
+
+
+# Sampled inside the truth inliers and still without the true matrix: the seven float32-rounded points of this one hypothesis leave a
+# cubic whose two roots near 1.5535 have become a complex pair (imaginary part 0.023), so NO 7-point solver finds the scene's matrix from
+# them -- the checker's own does not (tests/test_consensus_checker.py asserts that this is the whole list).
+TRACE_INCOMPLETE = {("f120_holes", 1): (328,)}
+
+
+def trace_complete(name, seed, H=512):
+    """the hypotheses that must hold a model with the truth mask: sampled inside the truth inliers, less TRACE_INCOMPLETE"""
+    return [h for h in trace_inside_truth(name, seed, H) if h not in TRACE_INCOMPLETE.get((name, seed), ())]
+
+
+def trace_inside_truth(name, seed, H=512):
+    """the hypotheses whose whole sample lies in the scene's truth inliers"""
+    truth = trace_scene(name)[2]
+    S = 7 if name.startswith("f") else 3
+    _, rows = trace_samples(name, seed, H)
+    return [h for h, row in enumerate(rows) if row[0] >= 0 and truth[row[:S]].all()]

@@ -14,6 +14,9 @@ def test_library_exports_every_declared_symbol():
     lib = srl.load_library()
     missing = [n for n in declared if not hasattr(lib, n)]
     assert missing == []
+    # the debug header's read-backs are declared like the rest: the parser must see them, and the library must export them
+    for name in ("srl_flow_download_level", "srl_image_prep_download_stage", "srl_debug_consensus_download"):
+        assert name in declared and hasattr(lib, name), name
 
 
 def test_struct_layouts_match_the_header():

@@ -14,11 +14,12 @@ from sr_livo_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRL_OK, SRL_ERR_NO_DEVICE, SRL_ERR_BAD_ARG = 0, -1, -3
 SIZES = {"double": 8, "int32_t": 4, "uint32_t": 4}
-NEW = ("srl_consensus_opts_default", "srl_consensus_fundamental", "srl_consensus_pnp", "srl_oft_use_device_consensus", "srl_oft_last_consensus")
+NEW = ("srl_consensus_opts_default", "srl_consensus_fundamental", "srl_consensus_pnp", "srl_oft_use_device_consensus", "srl_oft_last_consensus",
+       "srl_debug_consensus_download")
 
 
-def _header_fields(name):
-    text = open(os.path.join(ROOT, "include", "srlivo_hip.h")).read()
+def _header_fields(name, header="srlivo_hip.h"):
+    text = open(os.path.join(ROOT, "include", header)).read()
     body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
     fields = []
     for decl in body.split(";"):
@@ -44,6 +45,10 @@ def test_structs_agree_with_the_header():
         assert [f for f, _ in fields] == [f for f, _ in cls._fields_], name
         assert [s for _, s in fields] == [C.sizeof(t) for _, t in cls._fields_], name
         assert sum(s for _, s in fields) == C.sizeof(cls) == size, name
+    fields = _header_fields("srl_debug_consensus_info", "srlivo_hip_debug.h")
+    assert [f for f, _ in fields] == [f for f, _ in capi.DebugConsensusInfo._fields_]
+    assert [s for _, s in fields] == [C.sizeof(t) for _, t in capi.DebugConsensusInfo._fields_]
+    assert sum(s for _, s in fields) == C.sizeof(capi.DebugConsensusInfo) == 72
     text = open(os.path.join(ROOT, "include", "srlivo_hip.h")).read()
     assert int(re.search(r"#define SRL_CONSENSUS_MAX_POINTS (\d+)", text).group(1)) == capi.SRL_CONSENSUS_MAX_POINTS == 4096
     assert int(re.search(r"#define SRL_CONSENSUS_MAX_HYPOTHESES (\d+)", text).group(1)) == capi.SRL_CONSENSUS_MAX_HYPOTHESES == 4096
@@ -119,6 +124,19 @@ def test_every_refusal_on_a_null_context_zeroes_the_result_and_leaves_the_output
     # NULL options are the defaults and a NULL result is allowed: still refused for the context, nothing written
     status = np.full(n, 7, np.uint8)
     assert lib.srl_consensus_fundamental(None, ptr(a), ptr(b), n, None, ptr(status), None) == SRL_ERR_BAD_ARG and (status == 7).all()
+
+
+def test_the_read_back_refuses_a_null_context_and_writes_nothing():
+    lib = srl.load_library()
+    info = capi.DebugConsensusInfo()
+    C.memset(C.byref(info), 0xFF, C.sizeof(info))
+    before = bytes(info)
+    usable, samples, models, counts = np.full(16, 7, np.int32), np.full((4, 8), 7, np.int32), np.full(4 * 4 * 12, 7.0), np.full(4 * 4, 7, np.int32)
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)      # noqa: E731
+    rc = lib.srl_debug_consensus_download(None, C.byref(info), ptr(usable), 16, ptr(samples), ptr(models), ptr(counts), 4)
+    assert rc == SRL_ERR_BAD_ARG and bytes(info) == before
+    assert (usable == 7).all() and (samples == 7).all() and (models == 7).all() and (counts == 7).all()
+    assert lib.srl_debug_consensus_download(None, None, None, 0, None, None, None, 0) == SRL_ERR_BAD_ARG
 
 
 def test_a_refused_opt_in_leaves_the_providers_set_before_it_alive():

@@ -81,3 +81,63 @@ def test_a_planar_scene_has_no_single_consensus_for_the_fundamental_model():
     x1, x2, truth = ck.scene_fundamental(14, 120, 42, 0.0, planar=True)
     same = [np.array_equal(ck.ransac_fundamental(x1, x2, 1.0, 512, s), truth) for s in range(10)]
     assert not all(same), same
+
+
+# ------------------------------------------------------------------------------------------------ what tests/test_gpu_consensus_trace.py relies on
+def test_the_sampler_of_the_checker_draws_distinct_positions_and_fails_as_the_contract_says():
+    for S in (7, 3):
+        assert ck.sample(0, 0, S - 1, S) is None
+        for seed in ck.TRACE_SEEDS:
+            for m in (S, S + 1, 90, 117, 120, 1025):
+                for h in (0, 1, 85, 511):
+                    pos = ck.sample(seed, h, m, S)
+                    # (with m = S a hypothesis may exhaust its 64 draws: tests/test_consensus_math.py pins some that do)
+                    assert pos is None and m == S or len(set(pos)) == S and 0 <= min(pos) and max(pos) < m
+    usable = np.array([2, 3, 5, 7, 11, 13, 17, 19, 23], np.int32)
+    row = ck.sample_indices(1, 4, usable, 3)
+    assert row.dtype == np.int32 and (row[3:] == -1).all() and row[:3].tolist() == [int(usable[p]) for p in ck.sample(1, 4, 9, 3)]
+    assert (ck.sample_indices(1, 4, usable[:2], 3) == -1).all()
+    assert ck.usable_points(np.float32([[1, 2], [np.nan, 1], [3, 4]]), np.float32([[1, 2], [0, 1], [np.inf, 4]])).tolist() == [0]
+    # the confidence formula on values worked by hand: w = 1 / 2, S = 3: w^S = 1 / 8; H = 2: 1 - (7 / 8)^2 = 15 / 64
+    assert ck.confidence_reached(60, 120, 3, 2, 15.0 / 64.0) == 1 and ck.confidence_reached(60, 120, 3, 2, 0.235) == 0
+    assert ck.confidence_reached(0, 120, 7, 512, 0.5) == 0 and ck.confidence_reached(120, 120, 7, 1, 0.999) == 1
+
+
+@pytest.mark.parametrize("name", ck.TRACE_FUNDAMENTAL)
+def test_few_trace_hypotheses_sit_at_a_double_root(name):
+    """a hypothesis whose cubic has two roots within 1e-6 is excused from the comparison of the number of solutions: at most 2 % of any
+    case (scene, seed, H) may be, and every hypothesis of these scenes has a sample"""
+    for seed in ck.TRACE_SEEDS:
+        ref = ck.trace_seven_point(name, seed)
+        _, rows = ck.trace_samples(name, seed)
+        assert (rows[:, :7] >= 0).all() and (rows[:, 7] == -1).all()
+        for H in ck.TRACE_H:
+            excused = sum(1 for h in range(H) if ref[h][1])
+            assert excused <= 0.02 * H, (name, seed, H, excused)
+
+
+@pytest.mark.parametrize("name", ck.TRACE_EXACT)
+def test_the_trace_cases_exercise_ties_both_confidence_values_and_completeness(name):
+    a, b, truth = ck.trace_scene(name)
+    is_f = name.startswith("f")
+    S, slots, conf = (7, 3, 0.997) if is_f else (3, 4, 0.99)
+    n, inl = len(truth), int(truth.sum())
+    assert 0.35 <= 1.0 - inl / n <= 0.45
+    # one hypothesis never reaches the confidence, whatever it finds (the truth inliers bound every model's count), 512 do with the truth
+    assert max(ck.confidence_reached(k, n, S, 1, conf) for k in range(inl + 1)) == 0 and ck.confidence_reached(inl, n, S, 512, conf) == 1
+    for seed in ck.TRACE_SEEDS:
+        inside = ck.trace_inside_truth(name, seed)
+        for H in (200, 512):                                          # at least two hypotheses that must tie at the maximum
+            assert len(ck.trace_complete(name, seed, H)) >= 2, (name, seed, H)
+        if is_f:
+            # the checker's own solver finds the truth mask from every such sample -- but for the one listed
+            lost = [h for h in inside if not any(np.array_equal(ck.mask_fundamental(F, a, b, 1.0), truth)
+                                                 for F in ck.seven_point(a[ck.trace_samples(name, seed)[1][h, :7]], b[ck.trace_samples(name, seed)[1][h, :7]]))]
+            assert tuple(lost) == ck.TRACE_INCOMPLETE.get((name, seed), ()), (name, seed, lost)
+    for tname, seed, H in ck.TRACE_TIE_CASES:
+        if tname != name:
+            continue
+        must = ck.trace_complete(name, seed, H)
+        first = min((must[0] * slots + s) % 256 for s in range(slots))
+        assert must[0] * slots // 256 == (must[0] * slots + slots - 1) // 256          # (its slots do not straddle a stride)
+        assert any(max((h * slots + s) % 256 for s in range(slots)) < first and h * slots // 256 == (h * slots + slots - 1) // 256 for h in must[1:]), (name, seed, H)

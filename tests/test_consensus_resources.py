@@ -3,7 +3,7 @@ tests/test_color_track_resources.py; it reads the compiler's resource remarks an
 
 Recorded (VGPRs / scratch bytes per lane / LDS bytes per block), fundamental then PnP:
   k_cons_prep    38 / 0 / 8208      19 / 0 / 16        (the four-value block sum of Hartley's normalisation; the wave counts alone)
-  k_cons_hyp     92 / 0 / 41472    126 / 0 / 0         (64 lanes x 81 doubles of lane-interleaved 7 x 9 systems; P3P keeps its roots in
+  k_cons_hyp     92 / 0 / 41472    122 / 0 / 0         (64 lanes x 81 doubles of lane-interleaved 7 x 9 systems; P3P keeps its roots in
                                                          fixed slots and writes each accepted pose straight to its global slot, so
                                                          nothing is indexed at run time in a per-lane array)
   k_cons_score   64 / 0 / 16384     66 / 0 / 20480     (= the staged chunk: 1024 points x 4 or 5 floats)

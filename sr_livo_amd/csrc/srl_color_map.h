@@ -35,10 +35,9 @@ struct SrlColorMap {
     SrlColorState *d_state = nullptr;  size_t state_cap = 0;      // parallel to d_pool; entries >= num_points are zero
     unsigned *d_mark = nullptr;        unsigned mark_cap = 0;     // per voxel: (render epoch << 16) | occurrences in the list of that render
     unsigned render_epoch = 0;                                    // 1 ... 65535 (0: the value of a word nobody has marked)
-    unsigned char *d_img = nullptr;    size_t img_cap = 0;        // rows x cols x 3 bytes, rows packed
-    unsigned char *h_img = nullptr;    size_t h_img_cap = 0;      // page-locked staging of the upload
+    SrlImagePair img;                                             // rows x cols x 3 bytes, rows packed, and the upload's page-locked staging
     int img_rows = 0, img_cols = 0;                               // 0: no image uploaded
-    hipEvent_t img_ev = nullptr;       bool img_pending = false;  // the DMA out of h_img
+    hipEvent_t img_ev = nullptr;       bool img_pending = false;  // the DMA out of img.h
     SrlWgTotals render_tot;                                       // k_render_points: [0..5] totals of the last render, [6] the ticket, [7] unknown keys
                                                                   // and [8] overflowing marks (both since allocation: never reset)
     unsigned long long unknown_seen = 0, overflow_seen = 0;       // host copies of [7] and [8] as of the previous render

@@ -173,10 +173,9 @@ void srl_color_render_free(SrlColorMap *cm) {
     if (cm->img_pending && cm->img_ev) hipEventSynchronize(cm->img_ev);
     if (cm->d_state) hipFree(cm->d_state);
     if (cm->d_mark) hipFree(cm->d_mark);
-    if (cm->d_img) hipFree(cm->d_img);
-    if (cm->h_img) hipHostFree(cm->h_img);
+    cm->img.release();
     if (cm->img_ev) hipEventDestroy(cm->img_ev);
-    cm->d_state = nullptr; cm->d_mark = nullptr; cm->d_img = nullptr; cm->h_img = nullptr; cm->img_ev = nullptr;
+    cm->d_state = nullptr; cm->d_mark = nullptr; cm->img_ev = nullptr;
 }
 
 extern "C" int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows, int cols, int64_t row_stride_bytes) {
@@ -188,20 +187,9 @@ extern "C" int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows
     const size_t row_bytes = (size_t)cols * 3, bytes = row_bytes * (size_t)rows;
     if (!cm->img_ev) HIPCHK(ctx, hipEventCreateWithFlags(&cm->img_ev, hipEventDisableTiming));
     if (cm->img_pending) { HIPCHK(ctx, hipEventSynchronize(cm->img_ev)); cm->img_pending = false; }      // the staging block is free again
-    if (bytes > cm->h_img_cap) {
-        if (cm->h_img) { HIPCHK(ctx, hipHostFree(cm->h_img)); cm->h_img = nullptr; cm->h_img_cap = 0; }
-        HIPCHK(ctx, hipHostMalloc((void **)&cm->h_img, bytes, hipHostMallocDefault));
-        cm->h_img_cap = bytes;
-    }
-    if (bytes > cm->img_cap) {
-        if (cm->d_img) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(cm->d_img)); cm->d_img = nullptr; cm->img_cap = 0; }
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_img, bytes));
-        cm->img_cap = bytes;
-    }
+    { const int rc = cm->img.reserve(ctx, bytes, bytes); if (rc) return rc; }
     cm->img_rows = 0; cm->img_cols = 0;
-    if (row_stride_bytes == (int64_t)row_bytes) std::memcpy(cm->h_img, bgr, bytes);
-    else for (int r = 0; r < rows; r++) std::memcpy(cm->h_img + (size_t)r * row_bytes, bgr + (size_t)r * (size_t)row_stride_bytes, row_bytes);
-    HIPCHK(ctx, hipMemcpyAsync(cm->d_img, cm->h_img, bytes, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = cm->img.upload(ctx, bgr, rows, row_bytes, row_stride_bytes); if (rc) return rc; }
     HIPCHK(ctx, hipEventRecord(cm->img_ev, ctx->stream));
     cm->img_pending = true;
     cm->render_on = true;                 // from here on the colour state exists and follows the pool
@@ -215,13 +203,9 @@ extern "C" int srl_color_image_upload(srl_ctx *ctx, const uint8_t *bgr, int rows
 int srl_color_image_install(srl_ctx *ctx, const unsigned char *d_bgr, int rows, int cols) {
     SrlColorMap *cm = ctx->color;
     const size_t bytes = (size_t)cols * 3 * (size_t)rows;
-    if (bytes > cm->img_cap) {
-        if (cm->d_img) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(cm->d_img)); cm->d_img = nullptr; cm->img_cap = 0; }
-        HIPCHK(ctx, hipMalloc((void **)&cm->d_img, bytes));
-        cm->img_cap = bytes;
-    }
+    { const int rc = cm->img.reserve(ctx, 0, bytes); if (rc) return rc; }
     cm->img_rows = 0; cm->img_cols = 0;
-    HIPCHK(ctx, hipMemcpyAsync(cm->d_img, d_bgr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cm->img.d, d_bgr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     cm->render_on = true;
     { const int rc = srl_color_state_reserve(ctx, cm); if (rc) return rc; }
     cm->img_rows = rows; cm->img_cols = cols;
@@ -274,7 +258,7 @@ extern "C" int srl_color_map_render(srl_ctx *ctx, const srl_color_camera *cam, c
                        cm->render_epoch, cm->render_tot.d_tot);
     HIPCHK(ctx, hipGetLastError());
     if (nblocks > 0) {
-        hipLaunchKernelGGL(k_render_points, dim3(nblocks), dim3(256), 0, st, P, cm->d_pool, cm->d_mark, cm->render_epoch, cm->d_state, cm->d_img, A,
+        hipLaunchKernelGGL(k_render_points, dim3(nblocks), dim3(256), 0, st, P, cm->d_pool, cm->d_mark, cm->render_epoch, cm->d_state, cm->img.d, A,
                            cm->overflow_seen, cm->render_tot.d_rows, cm->render_tot.d_tot);
         HIPCHK(ctx, hipGetLastError());
     }

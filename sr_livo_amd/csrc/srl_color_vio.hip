@@ -275,7 +275,7 @@ extern "C" int srl_color_map_vio_rows(srl_ctx *ctx, const srl_color_vio_args *ar
     if (outcome) HIPCHK(ctx, b_outcome.alloc(ctx, (size_t)n));
     std::memcpy(ctx->h_scratch + at_points, points, (size_t)n * sizeof(srl_color_vio_point));
     HIPCHK(ctx, hipMemcpyAsync(b_points.p, ctx->h_scratch + at_points, (size_t)n * sizeof(srl_color_vio_point), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_vio_rows, dim3(nblocks), dim3(256), 0, st, b_points.as<srl_color_vio_point>(), cm->d_pool, cm->d_state, cm->d_img, A,
+    hipLaunchKernelGGL(k_vio_rows, dim3(nblocks), dim3(256), 0, st, b_points.as<srl_color_vio_point>(), cm->d_pool, cm->d_state, cm->img.d, A,
                        rows ? b_rows.as<double>() : nullptr, outcome ? b_outcome.as<unsigned char>() : nullptr, cm->vio_tot.d_rows, cm->vio_tot.d_tot);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch, cm->vio_tot.d_tot, VIO_ROW_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));

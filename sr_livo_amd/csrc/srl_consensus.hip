@@ -286,19 +286,22 @@ __global__ void __launch_bounds__(256) k_cons_pick(ConsArgs A, const double *mod
     }
 }
 
-size_t cons_align(size_t v) { return (v + 255) / 256 * 256; }
+// the pieces of the two blocks, sized for the limits (blocks not allocated yet: the pieces are null, and the sizes are all there is)
+void cons_layout(SrlConsensus *c, size_t *d_bytes, size_t *h_bytes) {
+    const size_t P = SRL_CONSENSUS_MAX_POINTS, H = SRL_CONSENSUS_MAX_HYPOTHESES, HM = H * CONS_MAX_SLOTS;
+    SrlCarve v{c->d_block}, w{c->h_block};
+    c->d_pts = v.take<float>(P * 5); c->d_usable = v.take<int>(P); c->d_norm = v.take<double>(8); c->d_nusable = v.take<int>(2);
+    c->d_models = v.take<double>(HM * 12); c->d_flags = v.take<int>(HM); c->d_samples = v.take<int>(H * 8);
+    c->d_mask = v.take<unsigned char>(P); c->d_list = v.take<int>(P); c->d_res = v.take<srl_consensus_result>(1);
+    c->h_pts = w.take<float>(P * 5); c->h_mask = w.take<unsigned char>(P); c->h_list = w.take<int>(P); c->h_res = w.take<srl_consensus_result>(1);
+    *d_bytes = v.at; *h_bytes = w.at;
+}
 
 int cons_workspace(srl_ctx *ctx) {
     if (ctx->consensus) return SRL_OK;
-    const size_t P = SRL_CONSENSUS_MAX_POINTS, HM = (size_t)SRL_CONSENSUS_MAX_HYPOTHESES * CONS_MAX_SLOTS;
-    const size_t o_pts = 0, o_usable = o_pts + cons_align(P * 5 * sizeof(float)), o_norm = o_usable + cons_align(P * sizeof(int)),
-                 o_nusable = o_norm + cons_align(8 * sizeof(double)), o_models = o_nusable + cons_align(2 * sizeof(int)),
-                 o_flags = o_models + cons_align(HM * 12 * sizeof(double)), o_samples = o_flags + cons_align(HM * sizeof(int)),
-                 o_mask = o_samples + cons_align((size_t)SRL_CONSENSUS_MAX_HYPOTHESES * 8 * sizeof(int)), o_list = o_mask + cons_align(P),
-                 o_res = o_list + cons_align(P * sizeof(int)), d_bytes = o_res + cons_align(sizeof(srl_consensus_result));
-    const size_t p_pts = 0, p_mask = cons_align(P * 5 * sizeof(float)), p_list = p_mask + cons_align(P), p_res = p_list + cons_align(P * sizeof(int)),
-                 h_bytes = p_res + cons_align(sizeof(srl_consensus_result));
     SrlConsensus *c = new SrlConsensus();
+    size_t d_bytes, h_bytes;
+    cons_layout(c, &d_bytes, &h_bytes);
     hipError_t e = hipMalloc((void **)&c->d_block, d_bytes);
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_block, h_bytes, hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -306,12 +309,7 @@ int cons_workspace(srl_ctx *ctx) {
         delete c;
         HIPCHK(ctx, e);
     }
-    c->d_pts = (float *)(c->d_block + o_pts); c->d_usable = (int *)(c->d_block + o_usable); c->d_norm = (double *)(c->d_block + o_norm);
-    c->d_nusable = (int *)(c->d_block + o_nusable); c->d_models = (double *)(c->d_block + o_models); c->d_flags = (int *)(c->d_block + o_flags);
-    c->d_samples = (int *)(c->d_block + o_samples); c->d_mask = (unsigned char *)(c->d_block + o_mask); c->d_list = (int *)(c->d_block + o_list);
-    c->d_res = (srl_consensus_result *)(c->d_block + o_res);
-    c->h_pts = (float *)(c->h_block + p_pts); c->h_mask = (unsigned char *)(c->h_block + p_mask); c->h_list = (int *)(c->h_block + p_list);
-    c->h_res = (srl_consensus_result *)(c->h_block + p_res);
+    cons_layout(c, &d_bytes, &h_bytes);
     ctx->consensus = c;
     return SRL_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/srlivo_hip.h"
 #include "srl_device.h"
+#include "srl_carve.h"
 #include "host/tr1_relation.h"
 
 #include <hip/hip_runtime.h>
@@ -402,4 +403,31 @@ struct DevBuf {
         return e;
     }
     template <class T> T *as() { return reinterpret_cast<T *>(p); }
+};
+
+// An uploaded image's two blocks: page-locked staging (h) and its place on the device (d), both grow-only.  Whoever uploads waits until
+// the staging block is free again before the next upload -- by ending its call synchronised, or behind an event of its own.
+struct SrlImagePair {
+    unsigned char *h = nullptr, *d = nullptr;
+    size_t h_cap = 0, d_cap = 0;
+    int reserve(srl_ctx *ctx, size_t host_bytes, size_t device_bytes) {
+        if (host_bytes > h_cap) {
+            if (h) { HIPCHK(ctx, hipHostFree(h)); h = nullptr; h_cap = 0; }
+            HIPCHK(ctx, hipHostMalloc((void **)&h, host_bytes, hipHostMallocDefault));
+            h_cap = host_bytes;
+        }
+        if (device_bytes > d_cap) {
+            if (d) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(d)); d = nullptr; d_cap = 0; }
+            HIPCHK(ctx, hipMalloc((void **)&d, device_bytes));
+            d_cap = device_bytes;
+        }
+        return SRL_OK;
+    }
+    // the caller's rows packed into h, and the DMA from there enqueued on the context's stream
+    int upload(srl_ctx *ctx, const uint8_t *src, int rows, size_t row_bytes, int64_t stride) {
+        srl_pack_rows(h, src, (size_t)rows, row_bytes, (size_t)stride);
+        HIPCHK(ctx, hipMemcpyAsync(d, h, (size_t)rows * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+        return SRL_OK;
+    }
+    void release() { if (h) hipHostFree(h); if (d) hipFree(d); *this = SrlImagePair(); }
 };

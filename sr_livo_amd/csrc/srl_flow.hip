@@ -46,12 +46,16 @@ struct SrlFlow {
     int nlev = 0;
     SrlFlowLevel lev[FLOW_MAX_LEVELS];
     size_t img_bytes = 0, der_pairs = 0;
-    unsigned char *d_img[2] = {nullptr, nullptr};      // [prev], [cur]: swapped by pointer
-    short *d_der[2] = {nullptr, nullptr};
-    unsigned char *d_gray = nullptr, *h_gray = nullptr;
-    float *d_prev = nullptr, *d_next = nullptr;
-    unsigned char *d_status = nullptr;
-    int pts_cap = 0;
+    struct Mem {                       // what the tracker's storage owns: freed by flow_free, and a fresh one ({}) is a tracker without storage
+        char *d_sets = nullptr;                            // one block, laid out by flow_layout_sets
+        unsigned char *d_img[2] = {nullptr, nullptr};      // [prev], [cur]: swapped by pointer
+        short *d_der[2] = {nullptr, nullptr};
+        SrlImagePair gray;                                 // the upload of srl_flow_track_image: comes with the first uploaded image
+        char *d_pts = nullptr;                             // one growable block, laid out by flow_layout_pts
+        float *d_prev = nullptr, *d_next = nullptr;
+        unsigned char *d_status = nullptr;
+        int pts_cap = 0;
+    } mem;
 };
 
 namespace {
@@ -257,16 +261,24 @@ __global__ void __launch_bounds__(64) k_flow_track(const float2 *prev, float2 *n
     if (lane == 0) { next[p] = make_float2(nx, ny); status[p] = st; }
 }
 
+// the two image sets and the two derivative sets of a plan out of d_sets (null: only measured); returns the block's size
+size_t flow_layout_sets(SrlFlow *f) {
+    SrlCarve c{f->mem.d_sets};
+    for (int k = 0; k < 2; k++) { f->mem.d_img[k] = c.take<unsigned char>(f->img_bytes); f->mem.d_der[k] = c.take<short>(f->der_pairs * 2); }
+    return c.at;
+}
+// ... and cap points out of d_pts
+size_t flow_layout_pts(SrlFlow::Mem *m, size_t cap) {
+    SrlCarve c{m->d_pts};
+    m->d_prev = c.take<float>(cap * 2); m->d_next = c.take<float>(cap * 2); m->d_status = c.take<unsigned char>(cap);
+    return c.at;
+}
+
 void flow_free(SrlFlow *f) {
-    for (int k = 0; k < 2; k++) {
-        if (f->d_img[k]) hipFree(f->d_img[k]);
-        if (f->d_der[k]) hipFree(f->d_der[k]);
-    }
-    if (f->d_gray) hipFree(f->d_gray);
-    if (f->h_gray) hipHostFree(f->h_gray);
-    if (f->d_prev) hipFree(f->d_prev);
-    if (f->d_next) hipFree(f->d_next);
-    if (f->d_status) hipFree(f->d_status);
+    if (f->mem.d_sets) hipFree(f->mem.d_sets);
+    if (f->mem.d_pts) hipFree(f->mem.d_pts);
+    f->mem.gray.release();
+    f->mem = {};
 }
 
 // opencvBuildOpticalFlowPyramid's level rule (:609-619): building stops after the level whose successor would be no larger than the window
@@ -285,6 +297,12 @@ int flow_plan(SrlFlow *f, int rows, int cols) {
     }
     f->img_bytes = img; f->der_pairs = der;
     return L;
+}
+
+// the refusal every entry point behind srl_flow_create makes
+int srl_flow_need(srl_ctx *ctx) {
+    if (!ctx->flow) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
+    return SRL_OK;
 }
 
 }  // namespace
@@ -330,56 +348,41 @@ static int flow_track(srl_ctx *ctx, SrlFlow *f, const uint8_t *gray, const unsig
     SRL_DISARM(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t gray_bytes = (size_t)rows * (size_t)cols;
+    SrlFlow::Mem &m = f->mem;
+    // the upload's blocks come with the first uploaded image, which need not be the tracker's first; a failure leaves the tracker as it was
+    if (gray) { const int rc = m.gray.reserve(ctx, (size_t)rows * (size_t)cols, (size_t)rows * (size_t)cols); if (rc) return rc; }
     if (!f->rows) {
         const int L = flow_plan(f, rows, cols);
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < 2 && e == hipSuccess; k++) {
-            e = hipMalloc((void **)&f->d_img[k], f->img_bytes);
-            if (e == hipSuccess) e = hipMalloc((void **)&f->d_der[k], f->der_pairs * 2 * sizeof(short));
-            // a set that has not seen an image reads as zeros (srl_flow_download_level)
-            if (e == hipSuccess) e = hipMemsetAsync(f->d_img[k], 0, f->img_bytes, st);
-            if (e == hipSuccess) e = hipMemsetAsync(f->d_der[k], 0, f->der_pairs * 2 * sizeof(short), st);
-        }
-        if (e == hipSuccess && gray) e = hipMalloc((void **)&f->d_gray, gray_bytes);
-        if (e == hipSuccess && gray) e = hipHostMalloc((void **)&f->h_gray, gray_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            flow_free(f);
-            f->d_img[0] = f->d_img[1] = f->d_gray = f->h_gray = nullptr; f->d_der[0] = f->d_der[1] = nullptr;
-            f->d_prev = f->d_next = nullptr; f->d_status = nullptr; f->pts_cap = 0;
-            f->max_level = f->opts.max_level;
-            HIPCHK(ctx, e);
-        }
+        const size_t bytes = flow_layout_sets(f);
+        hipError_t e = hipMalloc((void **)&m.d_sets, bytes);
+        // a set that has not seen an image reads as zeros (srl_flow_download_level)
+        if (e == hipSuccess) e = hipMemsetAsync(m.d_sets, 0, bytes, st);
+        if (e != hipSuccess) { flow_free(f); f->max_level = f->opts.max_level; HIPCHK(ctx, e); }
+        flow_layout_sets(f);
         f->max_level = L; f->rows = rows; f->cols = cols;
     }
-    if (n > f->pts_cap) {
+    if (n > m.pts_cap) {
         HIPCHK(ctx, hipStreamSynchronize(st));
-        if (f->d_prev) { hipFree(f->d_prev); hipFree(f->d_next); hipFree(f->d_status); f->d_prev = f->d_next = nullptr; f->d_status = nullptr; f->pts_cap = 0; }
+        if (m.d_pts) { hipFree(m.d_pts); m.d_pts = nullptr; m.pts_cap = 0; }
         const int cap = n < 512 ? 512 : n + n / 2;
-        HIPCHK(ctx, hipMalloc((void **)&f->d_prev, (size_t)cap * 2 * sizeof(float)));
-        HIPCHK(ctx, hipMalloc((void **)&f->d_next, (size_t)cap * 2 * sizeof(float)));
-        HIPCHK(ctx, hipMalloc((void **)&f->d_status, (size_t)cap));
-        f->pts_cap = cap;
+        HIPCHK(ctx, hipMalloc((void **)&m.d_pts, flow_layout_pts(&m, (size_t)cap)));
+        flow_layout_pts(&m, (size_t)cap);
+        m.pts_cap = cap;
     }
     // the current image's pyramid and derivatives into set 1 (every call ends synchronised, so the staging block is free)
     const unsigned char *d_level0 = d_prepared;
     if (gray) {
-        // (a tracker whose first image was a prepared one has no upload buffers yet)
-        if (!f->d_gray) HIPCHK(ctx, hipMalloc((void **)&f->d_gray, gray_bytes));
-        if (!f->h_gray) HIPCHK(ctx, hipHostMalloc((void **)&f->h_gray, gray_bytes, hipHostMallocDefault));
-        if (row_stride_bytes == (int64_t)cols) std::memcpy(f->h_gray, gray, gray_bytes);
-        else for (int r = 0; r < rows; r++) std::memcpy(f->h_gray + (size_t)r * cols, gray + (size_t)r * (size_t)row_stride_bytes, (size_t)cols);
-        HIPCHK(ctx, hipMemcpyAsync(f->d_gray, f->h_gray, gray_bytes, hipMemcpyHostToDevice, st));
-        d_level0 = f->d_gray;
+        { const int rc = m.gray.upload(ctx, gray, rows, (size_t)cols, row_stride_bytes); if (rc) return rc; }
+        d_level0 = m.gray.d;
     }
     for (int level = 0; level <= f->max_level; level++) {
         const SrlFlowLevel &V = f->lev[level];
         const size_t padded = (size_t)(V.rows + 2 * FLOW_WIN) * (size_t)(V.cols + 2 * FLOW_WIN);
         const unsigned nb = (unsigned)((padded + 255) / 256);
-        if (level == 0) hipLaunchKernelGGL(k_flow_level0, dim3(nb), dim3(256), 0, st, d_level0, f->d_img[1] + V.img_at, V.rows, V.cols);
-        else hipLaunchKernelGGL(k_flow_down, dim3(nb), dim3(256), 0, st, f->d_img[1] + f->lev[level - 1].img_at, f->lev[level - 1].rows, f->lev[level - 1].cols,
-                                f->d_img[1] + V.img_at, V.rows, V.cols);
-        hipLaunchKernelGGL(k_flow_scharr, dim3(nb), dim3(256), 0, st, f->d_img[1] + V.img_at, reinterpret_cast<short2 *>(f->d_der[1] + V.der_at * 2), V.rows, V.cols);
+        if (level == 0) hipLaunchKernelGGL(k_flow_level0, dim3(nb), dim3(256), 0, st, d_level0, m.d_img[1] + V.img_at, V.rows, V.cols);
+        else hipLaunchKernelGGL(k_flow_down, dim3(nb), dim3(256), 0, st, m.d_img[1] + f->lev[level - 1].img_at, f->lev[level - 1].rows, f->lev[level - 1].cols,
+                                m.d_img[1] + V.img_at, V.rows, V.cols);
+        hipLaunchKernelGGL(k_flow_scharr, dim3(nb), dim3(256), 0, st, m.d_img[1] + V.img_at, reinterpret_cast<short2 *>(m.d_der[1] + V.der_at * 2), V.rows, V.cols);
     }
     HIPCHK(ctx, hipGetLastError());
     const bool first = !f->have_prev;
@@ -387,23 +390,23 @@ static int flow_track(srl_ctx *ctx, SrlFlow *f, const uint8_t *gray, const unsig
     if (!first && n > 0) {
         { const int rc = ensure_host_scratch(ctx, at_prev + (size_t)n * 2 * sizeof(float)); if (rc) return rc; }
         std::memcpy(ctx->h_scratch + at_prev, prev_xy, (size_t)n * 2 * sizeof(float));
-        HIPCHK(ctx, hipMemcpyAsync(f->d_prev, ctx->h_scratch + at_prev, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(m.d_prev, ctx->h_scratch + at_prev, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, st));
         FlowTrackArgs A;
         for (int level = 0; level < FLOW_MAX_LEVELS; level++) {
             const SrlFlowLevel &V = f->lev[level <= f->max_level ? level : 0];
-            A.lv[level] = {f->d_img[0] + V.img_at, f->d_der[0] + V.der_at * 2, f->d_img[1] + V.img_at, V.rows, V.cols};
+            A.lv[level] = {m.d_img[0] + V.img_at, m.d_der[0] + V.der_at * 2, m.d_img[1] + V.img_at, V.rows, V.cols};
         }
         A.L = f->max_level; A.n = n; A.max_count = f->opts.max_count; A.epsilon = f->opts.epsilon; A.min_eig = (float)f->opts.min_eig_threshold;
-        hipLaunchKernelGGL(k_flow_track, dim3((unsigned)n), dim3(64), 0, st, reinterpret_cast<const float2 *>(f->d_prev), reinterpret_cast<float2 *>(f->d_next),
-                           f->d_status, A);
+        hipLaunchKernelGGL(k_flow_track, dim3((unsigned)n), dim3(64), 0, st, reinterpret_cast<const float2 *>(m.d_prev), reinterpret_cast<float2 *>(m.d_next),
+                           m.d_status, A);
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + at_next, f->d_next, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + at_status, f->d_status, (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + at_next, m.d_next, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_scratch + at_status, m.d_status, (size_t)n, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     // swapImageBuffer (:744-753): the image just given is the previous one of the next call
-    std::swap(f->d_img[0], f->d_img[1]);
-    std::swap(f->d_der[0], f->d_der[1]);
+    std::swap(m.d_img[0], m.d_img[1]);
+    std::swap(m.d_der[0], m.d_der[1]);
     f->have_prev = true;
     if (first) {                          // :762-773: curr_tracked_pts = last_tracked_pts, status untouched, 0 returned
         if (n > 0) std::memcpy(next_xy, prev_xy, (size_t)n * 2 * sizeof(float));
@@ -425,8 +428,8 @@ extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows,
     if (!ctx || !gray || rows < 2 || cols < 2 || rows > SRL_FLOW_MAX_EXTENT || cols > SRL_FLOW_MAX_EXTENT || row_stride_bytes < (int64_t)cols || n < 0 ||
         n > SRL_FLOW_MAX_POINTS || (n > 0 && (!prev_xy || !next_xy || !status)))
         return SRL_ERR_BAD_ARG;
+    { const int rc = srl_flow_need(ctx); if (rc) return rc; }
     SrlFlow *f = ctx->flow;
-    if (!f) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
     if (f->rows && (rows != f->rows || cols != f->cols)) { ctx->err = "flow: the image size differs from the tracker's first image"; return SRL_ERR_BAD_ARG; }
     return flow_track(ctx, f, gray, nullptr, rows, cols, row_stride_bytes, prev_xy, n, next_xy, status, n_tracked);
 }
@@ -434,11 +437,10 @@ extern "C" int srl_flow_track_image(srl_ctx *ctx, const uint8_t *gray, int rows,
 extern "C" int srl_flow_track_prepared(srl_ctx *ctx, const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked) {
     if (n_tracked) *n_tracked = 0;
     if (!ctx || n < 0 || n > SRL_FLOW_MAX_POINTS || (n > 0 && (!prev_xy || !next_xy || !status))) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_flow_need(ctx); if (rc) return rc; }
     SrlFlow *f = ctx->flow;
-    if (!f) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
+    { const int rc = srl_prep_need(ctx, true); if (rc) return rc; }
     const SrlImagePrep *p = ctx->prep;
-    if (!p) { ctx->err = "no image preparer (srl_image_prep_create)"; return SRL_ERR_NO_MAP; }
-    if (!p->have_image) { ctx->err = "image preparer: no image yet (srl_image_prepare)"; return SRL_ERR_NO_SWEEP; }
     if (f->rows && (p->rows != f->rows || p->cols != f->cols)) { ctx->err = "flow: the image size differs from the tracker's first image"; return SRL_ERR_BAD_ARG; }
     return flow_track(ctx, f, nullptr, p->d_gray_eq, p->rows, p->cols, p->cols, prev_xy, n, next_xy, status, n_tracked);
 }
@@ -446,7 +448,7 @@ extern "C" int srl_flow_track_prepared(srl_ctx *ctx, const float *prev_xy, int n
 extern "C" int srl_flow_levels(srl_ctx *ctx, int *L) {
     if (L) *L = 0;
     if (!ctx || !L) return SRL_ERR_BAD_ARG;
-    if (!ctx->flow) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
+    { const int rc = srl_flow_need(ctx); if (rc) return rc; }
     *L = ctx->flow->max_level;
     return SRL_OK;
 }
@@ -455,8 +457,8 @@ extern "C" int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8
     if (rows) *rows = 0;
     if (cols) *cols = 0;
     if (!ctx || (which != SRL_FLOW_PREV && which != SRL_FLOW_CUR) || level < 0) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_flow_need(ctx); if (rc) return rc; }
     SrlFlow *f = ctx->flow;
-    if (!f) { ctx->err = "no flow tracker (srl_flow_create)"; return SRL_ERR_NO_MAP; }
     if (!f->rows) { ctx->err = "flow: no image yet"; return SRL_ERR_NO_SWEEP; }
     if (level > f->max_level) return SRL_ERR_BAD_ARG;
     const SrlFlowLevel &V = f->lev[level];
@@ -466,7 +468,7 @@ extern "C" int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t padded = (size_t)(V.rows + 2 * FLOW_WIN) * (size_t)(V.cols + 2 * FLOW_WIN);
-    if (image_padded) HIPCHK(ctx, hipMemcpy(image_padded, f->d_img[which] + V.img_at, padded, hipMemcpyDeviceToHost));
-    if (deriv_padded) HIPCHK(ctx, hipMemcpy(deriv_padded, f->d_der[which] + V.der_at * 2, padded * 2 * sizeof(short), hipMemcpyDeviceToHost));
+    if (image_padded) HIPCHK(ctx, hipMemcpy(image_padded, f->mem.d_img[which] + V.img_at, padded, hipMemcpyDeviceToHost));
+    if (deriv_padded) HIPCHK(ctx, hipMemcpy(deriv_padded, f->mem.d_der[which] + V.der_at * 2, padded * 2 * sizeof(short), hipMemcpyDeviceToHost));
     return SRL_OK;
 }

@@ -1,6 +1,5 @@
 // srl_image_prep.h -- internal: the image preparer's state (srl_image_prep.hip), read by srl_flow.hip (srl_flow_track_prepared takes
-// d_gray_eq as its image).  Every plane is allocated for the pixel count rounded up to a multiple of 4: the per-pixel kernels load and
-// store four pixels per lane, the last lane's surplus lands in that slack and is never downloaded.
+// d_gray_eq as its image).  Every plane has room for the pixel count rounded up to a multiple of 4 (k_prep_pixel, k_prep_apply).
 #pragma once
 #include "srl_ctx.h"
 
@@ -10,14 +9,25 @@ struct SrlImagePrep {
     int T = 0, tw = 0, th = 0, ext_rows = 0, ext_cols = 0;      // tiles per side, tile size, the (possibly) extended plane
     int limit[2] = {0, 0};                                      // clip limit of a tile's bins: [0] gray, [1] Y
     bool have_image = false;
-    unsigned char *h_raw = nullptr;                             // page-locked staging of the upload, rows packed
-    unsigned char *d_raw = nullptr;                             // rows x cols x 3
+    SrlImagePair raw;                                           // the upload: rows x cols x 3, rows packed
+    char *d_block = nullptr;                                    // everything below: one block, laid out by prep_layout (srl_image_prep.hip)
     short *d_map1 = nullptr;                                    // (sx, sy) per pixel
     unsigned short *d_map2 = nullptr;                           // ay * 32 + ax per pixel
     unsigned char *d_undist = nullptr, *d_gray = nullptr, *d_y = nullptr, *d_crcb = nullptr;      // 3, 1, 1, 2 bytes per pixel
     unsigned char *d_lut = nullptr;                             // [plane][ty][tx][256]: plane 0 gray, 1 Y
     unsigned char *d_gray_eq = nullptr, *d_bgr_eq = nullptr;    // the two results
 };
+
+// the refusals of the preparer's entry points and of srl_flow_track_prepared: no preparer, no image yet; more than one rank
+inline int srl_prep_need(srl_ctx *ctx, bool image) {
+    if (!ctx->prep) { ctx->err = "no image preparer (srl_image_prep_create)"; return SRL_ERR_NO_MAP; }
+    if (image && !ctx->prep->have_image) { ctx->err = "image preparer: no image yet (srl_image_prepare)"; return SRL_ERR_NO_SWEEP; }
+    return SRL_OK;
+}
+inline int srl_prep_one_rank(srl_ctx *ctx) {
+    if (ctx->nranks > 1) { ctx->err = "the image preparer is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    return SRL_OK;
+}
 
 // srl_color_render.hip: d_bgr (rows x cols x 3, packed, device) becomes the colour map's image as srl_color_image_upload would leave it
 int srl_color_image_install(srl_ctx *ctx, const unsigned char *d_bgr, int rows, int cols);

@@ -228,22 +228,26 @@ __global__ void __launch_bounds__(256) k_prep_apply(const unsigned *__restrict__
     bgr_eq[3 * (size_t)g + 2] = ub[8] | ub[9] << 8 | ub[10] << 16 | ub[11] << 24;
 }
 
+// the maps, the five intermediate planes, the LUT and the two results out of d_block (null: only measured); returns the block's size
+size_t prep_layout(SrlImagePrep *p) {
+    const size_t npix4 = ((size_t)p->rows * (size_t)p->cols + 3) / 4 * 4;
+    SrlCarve c{p->d_block};
+    p->d_map1 = c.take<short>(npix4 * 2); p->d_map2 = c.take<unsigned short>(npix4);
+    p->d_undist = c.take<unsigned char>(npix4 * 3); p->d_gray = c.take<unsigned char>(npix4); p->d_y = c.take<unsigned char>(npix4);
+    p->d_crcb = c.take<unsigned char>(npix4 * 2); p->d_lut = c.take<unsigned char>((size_t)2 * p->T * p->T * 256);
+    p->d_gray_eq = c.take<unsigned char>(npix4); p->d_bgr_eq = c.take<unsigned char>(npix4 * 3);
+    return c.at;
+}
+
 void prep_free(SrlImagePrep *p) {
-    if (p->h_raw) hipHostFree(p->h_raw);
-    void *dev[] = {p->d_raw, p->d_map1, p->d_map2, p->d_undist, p->d_gray, p->d_y, p->d_crcb, p->d_lut, p->d_gray_eq, p->d_bgr_eq};
-    for (void *d : dev) if (d) hipFree(d);
+    p->raw.release();
+    if (p->d_block) hipFree(p->d_block);
 }
 
 void prep_info(const SrlImagePrep *p, int installed, srl_image_prep_info *info) {
     if (!info) return;
     info->tiles = p->T; info->tile_w = p->tw; info->tile_h = p->th; info->ext_rows = p->ext_rows; info->ext_cols = p->ext_cols;
     info->limit_gray = p->limit[0]; info->limit_color = p->limit[1]; info->installed_color = installed;
-}
-
-int prep_need(srl_ctx *ctx, bool image) {
-    if (!ctx->prep) { ctx->err = "no image preparer (srl_image_prep_create)"; return SRL_ERR_NO_MAP; }
-    if (image && !ctx->prep->have_image) { ctx->err = "image preparer: no image yet (srl_image_prepare)"; return SRL_ERR_NO_SWEEP; }
-    return SRL_OK;
 }
 
 }  // namespace
@@ -293,7 +297,7 @@ extern "C" int srl_image_prep_create(srl_ctx *ctx, const srl_image_prep_opts *o)
         return SRL_ERR_BAD_ARG;
     }
     if (ctx->prep) { ctx->err = "an image preparer exists: its options hold for its life (srl_image_prep_destroy first)"; return SRL_ERR_BAD_ARG; }
-    if (ctx->nranks > 1) { ctx->err = "the image preparer is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    { const int rc = srl_prep_one_rank(ctx); if (rc) return rc; }
     SRL_DISARM(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)o->rows * (size_t)o->cols, npix4 = (npix + 3) / 4 * 4;
@@ -304,20 +308,11 @@ extern "C" int srl_image_prep_create(srl_ctx *ctx, const srl_image_prep_opts *o)
     p->opts = *o; p->rows = o->rows; p->cols = o->cols;
     p->T = plan.T; p->tw = plan.tw; p->th = plan.th; p->ext_rows = plan.ext_rows; p->ext_cols = plan.ext_cols;
     p->limit[0] = plan.limit[0]; p->limit[1] = plan.limit[1];
-    const size_t lut_bytes = (size_t)2 * plan.T * plan.T * 256;
-    hipError_t e = hipHostMalloc((void **)&p->h_raw, npix * 3, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_raw, npix4 * 3);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_map1, npix4 * 2 * sizeof(short));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_map2, npix4 * sizeof(unsigned short));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_undist, npix4 * 3);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_gray, npix4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_y, npix4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_crcb, npix4 * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_lut, lut_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_gray_eq, npix4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_bgr_eq, npix4 * 3);
+    // (the upload's device side has the planes' slack of up to three pixels)
+    { const int rc = p->raw.reserve(ctx, npix * 3, npix4 * 3); if (rc) { prep_free(p); delete p; return rc; } }
+    hipError_t e = hipMalloc((void **)&p->d_block, prep_layout(p));
     // the maps once per preparer (a pageable source: the copies are made before the calls return)
-    if (e == hipSuccess) e = hipMemcpy(p->d_map1, m1.data(), npix4 * 2 * sizeof(short), hipMemcpyHostToDevice);
+    if (e == hipSuccess) { prep_layout(p); e = hipMemcpy(p->d_map1, m1.data(), npix4 * 2 * sizeof(short), hipMemcpyHostToDevice); }
     if (e == hipSuccess) e = hipMemcpy(p->d_map2, m2.data(), npix4 * sizeof(unsigned short), hipMemcpyHostToDevice);
     if (e != hipSuccess) { prep_free(p); delete p; HIPCHK(ctx, e); }
     ctx->prep = p;
@@ -340,23 +335,21 @@ extern "C" int srl_image_prep_destroy(srl_ctx *ctx) {
 extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_image_prep_info *info) {
     if (info) std::memset(info, 0, sizeof *info);
     if (!ctx || !raw_bgr) return SRL_ERR_BAD_ARG;
-    { const int rc = prep_need(ctx, false); if (rc) return rc; }
+    { const int rc = srl_prep_need(ctx, false); if (rc) return rc; }
     SrlImagePrep *p = ctx->prep;
     if (rows != p->rows || cols != p->cols) { ctx->err = "image preparer: the image size differs from the preparer's"; return SRL_ERR_BAD_ARG; }
     if (row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
-    if (ctx->nranks > 1) { ctx->err = "the image preparer is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
+    { const int rc = srl_prep_one_rank(ctx); if (rc) return rc; }
     SRL_DISARM(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t row_bytes = (size_t)cols * 3, npix = (size_t)rows * (size_t)cols;
+    const size_t npix = (size_t)rows * (size_t)cols;
     // every call ends synchronised, so the staging block is free
-    if (row_stride_bytes == (int64_t)row_bytes) std::memcpy(p->h_raw, raw_bgr, npix * 3);
-    else for (int r = 0; r < rows; r++) std::memcpy(p->h_raw + (size_t)r * row_bytes, raw_bgr + (size_t)r * (size_t)row_stride_bytes, row_bytes);
-    HIPCHK(ctx, hipMemcpyAsync(p->d_raw, p->h_raw, npix * 3, hipMemcpyHostToDevice, st));
+    { const int rc = p->raw.upload(ctx, raw_bgr, rows, (size_t)cols * 3, row_stride_bytes); if (rc) return rc; }
     const int ngroups = (int)((npix + 3) / 4);
     const unsigned nb = (unsigned)((ngroups + 255) / 256);
     const PrepDims D = {rows, cols, (int)npix};
-    hipLaunchKernelGGL(k_prep_pixel, dim3(nb), dim3(256), 0, st, p->d_raw, reinterpret_cast<const uint4 *>(p->d_map1), reinterpret_cast<const uint2 *>(p->d_map2),
+    hipLaunchKernelGGL(k_prep_pixel, dim3(nb), dim3(256), 0, st, p->raw.d, reinterpret_cast<const uint4 *>(p->d_map1), reinterpret_cast<const uint2 *>(p->d_map2),
                        reinterpret_cast<unsigned *>(p->d_undist), reinterpret_cast<unsigned *>(p->d_gray), reinterpret_cast<unsigned *>(p->d_y),
                        reinterpret_cast<uint2 *>(p->d_crcb), D, ngroups);
     PrepTileArgs TA;
@@ -384,7 +377,7 @@ extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows,
 
 extern "C" int srl_image_prep_download(srl_ctx *ctx, int which, uint8_t *out, int64_t row_stride_bytes) {
     if (!ctx || !out || (which != 0 && which != 1)) return SRL_ERR_BAD_ARG;
-    { const int rc = prep_need(ctx, true); if (rc) return rc; }
+    { const int rc = srl_prep_need(ctx, true); if (rc) return rc; }
     SrlImagePrep *p = ctx->prep;
     const size_t row_bytes = (size_t)p->cols * (which ? 3 : 1);
     if (row_stride_bytes < (int64_t)row_bytes) return SRL_ERR_BAD_ARG;
@@ -397,7 +390,7 @@ extern "C" int srl_image_prep_download(srl_ctx *ctx, int which, uint8_t *out, in
 
 extern "C" int srl_image_prep_download_stage(srl_ctx *ctx, int stage, uint8_t *out, int64_t capacity) {
     if (!ctx || !out || stage < SRL_PREP_STAGE_UNDIST || stage > SRL_PREP_STAGE_LUT_Y) return SRL_ERR_BAD_ARG;
-    { const int rc = prep_need(ctx, true); if (rc) return rc; }
+    { const int rc = srl_prep_need(ctx, true); if (rc) return rc; }
     SrlImagePrep *p = ctx->prep;
     const size_t npix = (size_t)p->rows * (size_t)p->cols, lut_bytes = (size_t)p->T * p->T * 256;
     const size_t need = stage == SRL_PREP_STAGE_GRAY ? npix : (stage >= SRL_PREP_STAGE_LUT_GRAY ? lut_bytes : npix * 3);

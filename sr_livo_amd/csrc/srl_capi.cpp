@@ -49,6 +49,7 @@ int ensure_work(srl_ctx *ctx, int n) {
     // small passes use 16 or 32 keypoints per workgroup (srl_keypoints_per_block): size for whichever gives more workgroups
     const int nblocks = std::max((cap + SRL_KPB - 1) / SRL_KPB, 1024 + 8);
     int rc;
+    ctx->work_cap = 0; ctx->block_cap = 0;      // (nothing fits until every block below is there)
     if ((rc = ensure(ctx, ctx->d_rec, (size_t)cap * 8))) return rc;
     if ((rc = ensure(ctx, ctx->d_status, (size_t)cap))) return rc;
     if ((rc = ensure(ctx, ctx->d_bound, (size_t)cap * 4))) return rc;
@@ -67,10 +68,10 @@ bool srl_is_pinned(const void *p) {
     return attr.type == hipMemoryTypeHost;
 }
 
-int srl_ring_init(srl_ctx *ctx) {
-    if (ctx->h_ring) return SRL_OK;
-    HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_ring, (size_t)srl_ctx::RING_SLOTS * srl_ctx::RING_SLOT_BYTES, hipHostMallocDefault));
-    for (int i = 0; i < srl_ctx::RING_SLOTS; i++) { HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ring_ev[i], hipEventDisableTiming)); ctx->ring_busy[i] = false; }
+int upload_chunks_init(srl_ctx *ctx) {
+    if (ctx->h_chunks) return SRL_OK;
+    HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_chunks, (size_t)srl_ctx::CHUNK_SLOTS * srl_ctx::CHUNK_BYTES, hipHostMallocDefault));
+    for (int i = 0; i < srl_ctx::CHUNK_SLOTS; i++) { HIPCHK(ctx, hipEventCreateWithFlags(&ctx->chunk_ev[i], hipEventDisableTiming)); ctx->chunk_busy[i] = false; }
     return SRL_OK;
 }
 
@@ -78,6 +79,7 @@ int ensure_taps(srl_ctx *ctx, int n, int K) {
     if (n <= ctx->tap_cap && K <= ctx->tap_K) return SRL_OK;
     const int cap = std::max(n, ctx->tap_cap), kk = std::max(K, ctx->tap_K);
     int rc;
+    ctx->tap_cap = 0; ctx->tap_K = 0;
     if ((rc = ensure(ctx, ctx->d_tap_ids, (size_t)cap * kk))) return rc;
     if ((rc = ensure(ctx, ctx->d_tap_ncand, (size_t)cap))) return rc;
     if ((rc = ensure(ctx, ctx->d_tap_normal, (size_t)cap * 3))) return rc;
@@ -147,20 +149,20 @@ int srl_ctx_create(int device, srl_ctx **out) {
     srl_ctx *ctx = new srl_ctx();
     ctx->device = device;
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) ctx->num_cu = cu; }
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return SRL_ERR_NO_DEVICE; }
+    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { srl_ctx_destroy(ctx); return SRL_ERR_NO_DEVICE; }
     if (hipMalloc((void **)&ctx->d_out, sizeof(SrlDevOut)) != hipSuccess ||
         hipHostMalloc((void **)&ctx->h_out, sizeof(SrlDevOut)) != hipSuccess ||
         hipMalloc((void **)&ctx->d_count, sizeof(long long)) != hipSuccess ||
         hipHostMalloc((void **)&ctx->h_count, sizeof(long long)) != hipSuccess) {
-        delete ctx;
+        srl_ctx_destroy(ctx);
         return SRL_ERR_HIP;
     }
     {
         const size_t row_bytes = (size_t)(SRL_FUSED_MAX_BLOCKS + SRL_FUSED_MAX_GROUPS) * SRL_ROW_GRANULES * 8;     // rows + super rows
-        if (hipMalloc((void **)&ctx->d_granules, row_bytes) != hipSuccess || hipMemset(ctx->d_granules, 0, row_bytes) != hipSuccess) { delete ctx; return SRL_ERR_HIP; }
+        if (hipMalloc((void **)&ctx->d_granules, row_bytes) != hipSuccess || hipMemset(ctx->d_granules, 0, row_bytes) != hipSuccess) { srl_ctx_destroy(ctx); return SRL_ERR_HIP; }
     }
     if (hipHostMalloc((void **)&ctx->h_mail, sizeof(SrlMailbox), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-        delete ctx;
+        srl_ctx_destroy(ctx);
         return SRL_ERR_HIP;
     }
     std::memset(ctx->h_mail, 0, sizeof(SrlMailbox));
@@ -175,7 +177,7 @@ int srl_ctx_destroy(srl_ctx *ctx) {
     if (!ctx) return SRL_OK;
     hipSetDevice(ctx->device);
     if (ctx->counted && ctx->device < SRL_MAX_DEVICES) g_live_ctx[ctx->device].fetch_sub(1, std::memory_order_relaxed);
-    if (ctx->armed) srl_ctx_disarm(ctx);
+    if (ctx->armed.on) srl_ctx_disarm(ctx);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
     if (ctx->color) srl_color_map_destroy(ctx);
@@ -189,8 +191,8 @@ int srl_ctx_destroy(srl_ctx *ctx) {
     if (ctx->parked_comm && srl_rccl()) srl_rccl()->CommDestroy(ctx->parked_comm);
     if (ctx->d_sub_kept) hipFree(ctx->d_sub_kept);
     if (ctx->d_sub_seen) hipFree(ctx->d_sub_seen);
-    void *bufs[] = {ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_imu, ctx->d_corr_raw, ctx->d_corr_seg, ctx->d_frame_raw, ctx->d_frame_world, ctx->d_table, ctx->d_slabs, ctx->d_raw, ctx->d_rec, ctx->d_status, ctx->d_partials, ctx->d_binfo,
-                    ctx->d_out, ctx->d_count, ctx->d_bound, ctx->d_granules, ctx->d_rec_granules, ctx->d_raw_next, ctx->d_stage_next, ctx->d_stage_cur, ctx->d_tap_ids, ctx->d_tap_ncand, ctx->d_tap_normal, ctx->d_tap_a2d,
+    void *bufs[] = {ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_imu, ctx->d_corr_raw, ctx->d_corr_seg, ctx->d_frame_raw, ctx->d_frame_world, ctx->d_table, ctx->d_slabs, ctx->cur.soa, ctx->d_rec, ctx->d_status, ctx->d_partials, ctx->d_binfo,
+                    ctx->d_out, ctx->d_count, ctx->d_bound, ctx->d_granules, ctx->d_rec_granules, ctx->next.soa, ctx->next.stage, ctx->cur.stage, ctx->d_tap_ids, ctx->d_tap_ncand, ctx->d_tap_normal, ctx->d_tap_a2d,
                     ctx->d_tap_offset, ctx->d_gather, ctx->d_peer, ctx->d_mail};
     for (int r = 0; r < SRL_MAX_PEERS; r++) if (ctx->peer_mapped[r]) hipIpcCloseMemHandle(ctx->peer_mapped[r]);
     if (ctx->d_inbox) hipFree(ctx->d_inbox);
@@ -208,11 +210,11 @@ int srl_ctx_destroy(srl_ctx *ctx) {
     if (ctx->ev_insert) hipEventDestroy(ctx->ev_insert);
     if (ctx->ev_world) hipEventDestroy(ctx->ev_world);
     if (ctx->ev_frame_read) hipEventDestroy(ctx->ev_frame_read);
-    if (ctx->h_ring) { hipHostFree(ctx->h_ring); for (int i = 0; i < srl_ctx::RING_SLOTS; i++) if (ctx->ring_ev[i]) hipEventDestroy(ctx->ring_ev[i]); }
+    if (ctx->h_chunks) { hipHostFree(ctx->h_chunks); for (int i = 0; i < srl_ctx::CHUNK_SLOTS; i++) if (ctx->chunk_ev[i]) hipEventDestroy(ctx->chunk_ev[i]); }
     for (auto &b : ctx->pool_free) hipFree(b.p);
     ctx->pool_free.clear();
     for (int i = 0; i < 4; i++) if (ctx->ev[i]) hipEventDestroy(ctx->ev[i]);
-    for (int i = 0; i < srl_ctx::PROF_RING; i++) for (int k = 0; k < 2; k++) if (ctx->ring[i][k]) hipEventDestroy(ctx->ring[i][k]);
+    for (SrlProfRing::Entry &e : ctx->prof.e) for (int k = 0; k < 2; k++) if (e.ev[k]) hipEventDestroy(e.ev[k]);
     for (int sl = 0; sl < 2; sl++) for (int k = 0; k < 2; k++) if (ctx->up_ev[sl][k]) hipEventDestroy(ctx->up_ev[sl][k]);
     if (ctx->upload_ev) hipEventDestroy(ctx->upload_ev);
     if (ctx->copy_stream) { hipStreamSynchronize(ctx->copy_stream); hipStreamDestroy(ctx->copy_stream); }
@@ -342,27 +344,27 @@ int upload_aos(srl_ctx *ctx, const char *src, size_t bytes, double *d_stage, hip
         }
         return SRL_OK;
     }
-    int rc2 = srl_ring_init(ctx);
+    int rc2 = upload_chunks_init(ctx);
     if (rc2) return rc2;
     size_t off = 0;
     while (off < bytes) {
-        const size_t len = std::min(bytes - off, (size_t)srl_ctx::RING_SLOT_BYTES);
-        const int slot = ctx->ring_next++ % srl_ctx::RING_SLOTS;
-        if (ctx->ring_busy[slot]) { HIPCHK(ctx, hipEventSynchronize(ctx->ring_ev[slot])); ctx->ring_busy[slot] = false; }
-        std::memcpy(ctx->h_ring + (size_t)slot * srl_ctx::RING_SLOT_BYTES, src + off, len);
+        const size_t len = std::min(bytes - off, (size_t)srl_ctx::CHUNK_BYTES);
+        const int slot = ctx->chunk_next++ % srl_ctx::CHUNK_SLOTS;
+        char *chunk = ctx->h_chunks + (size_t)slot * srl_ctx::CHUNK_BYTES;
+        if (ctx->chunk_busy[slot]) { HIPCHK(ctx, hipEventSynchronize(ctx->chunk_ev[slot])); ctx->chunk_busy[slot] = false; }
+        std::memcpy(chunk, src + off, len);
         {
-            hipError_t e__ = hipMemcpyAsync(reinterpret_cast<char *>(d_stage) + off, ctx->h_ring + (size_t)slot * srl_ctx::RING_SLOT_BYTES, len,
-                                            hipMemcpyHostToDevice, st);
+            hipError_t e__ = hipMemcpyAsync(reinterpret_cast<char *>(d_stage) + off, chunk, len, hipMemcpyHostToDevice, st);
             if (e__ != hipSuccess) {
                 char buf[256];
                 std::snprintf(buf, sizeof buf, "ring upload: %s (dst %p + %zu, ring %p slot %d, len %zu, stream %p, main stream %p)", hipGetErrorString(e__),
-                              (void *)d_stage, off, (void *)ctx->h_ring, slot, len, (void *)st, (void *)ctx->stream);
+                              (void *)d_stage, off, (void *)ctx->h_chunks, slot, len, (void *)st, (void *)ctx->stream);
                 ctx->err = buf;
                 return SRL_ERR_HIP;
             }
         }
-        HIPCHK(ctx, hipEventRecord(ctx->ring_ev[slot], st));
-        ctx->ring_busy[slot] = true;
+        HIPCHK(ctx, hipEventRecord(ctx->chunk_ev[slot], st));
+        ctx->chunk_busy[slot] = true;
         off += len;
     }
     return SRL_OK;
@@ -375,22 +377,10 @@ int srl_sweep_upload(srl_ctx *ctx, const double *raw_xyz, int n) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int b = 0, cnt = 0;
     srl_shard_range(n, ctx->nranks, ctx->rank, &b, &cnt);
-    ctx->total_n = n;
-    ctx->shard_begin = b;
-    ctx->n = cnt;
-    ctx->sweep_loaded = true;
-    ctx->taps_valid = false;
-    ctx->passes_in_solve = 0;
-    ctx->tail_pending = false;
-    ctx->bound_n = 0;
-    if (cnt > ctx->sweep_cap) {
-        const int cap = std::max(cnt, 1024);
-        int rc = ensure(ctx, ctx->d_raw, (size_t)cap * 3);
-        if (rc) return rc;
-        ctx->sweep_cap = cap;
-    }
-    int rc = ensure_work(ctx, cnt);
+    srl_sweep_becomes_current(ctx, cnt, b, n, cnt, false);      // (every plane is filled by the transpose below)
+    int rc = ctx->cur.reserve_soa(ctx, cnt);
     if (rc) return rc;
+    if ((rc = ensure_work(ctx, cnt))) return rc;
     if (cnt > 0) {
         // stage AoS in the rec buffer (>= 8 doubles per keypoint), transpose to SoA on the device.  Everything is
         // stream-ordered with the solve that follows: no synchronisation here.
@@ -398,9 +388,8 @@ int srl_sweep_upload(srl_ctx *ctx, const double *raw_xyz, int n) {
         //  must leave it untouched until the next call that returns results; pageable: through the context's pinned ring)
         int rcu = upload_aos(ctx, reinterpret_cast<const char *>(raw_xyz + (size_t)b * 3), (size_t)cnt * 3 * sizeof(double), ctx->d_rec, ctx->stream);
         if (rcu) return rcu;
-        HIPCHK(ctx, srl_launch_aos_to_soa(ctx->d_rec, cnt, ctx->d_raw, ctx->d_raw + ctx->sweep_cap, ctx->d_raw + 2 * (size_t)ctx->sweep_cap, ctx->stream));
+        HIPCHK(ctx, srl_launch_aos_to_soa(ctx->d_rec, cnt, ctx->cur.x(), ctx->cur.y(), ctx->cur.z(), ctx->stream));
     }
-    ctx->soa_valid_n = cnt;
     return SRL_OK;
 }
 
@@ -433,13 +422,15 @@ int srl_sweep_prefetch(srl_ctx *ctx, const double *raw_xyz, int n) {
     }
     int b = 0, cnt = 0;
     srl_shard_range(n, ctx->nranks, ctx->rank, &b, &cnt);
-    if (cnt > ctx->next_cap || cnt > ctx->stage_next_cap) {
-        const int cap = std::max(cnt, 1024);
+    SrlSweepSlot &nx = ctx->next;
+    if (cnt > nx.soa_cap || cnt > nx.stage_cap) {
         SRL_DISARM(ctx);                                                // the buffers move (hipFree waits for the whole device)
         HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
+        const bool planes_move = cnt > nx.soa_cap;
         int rc;
-        if (cnt > ctx->next_cap) { if ((rc = ensure(ctx, ctx->d_raw_next, (size_t)cap * 3))) return rc; ctx->next_cap = cap; HIPCHK(ctx, hipMemsetAsync(ctx->d_raw_next, 0, (size_t)cap * 3 * sizeof(double), ctx->copy_stream)); }
-        if (cnt > ctx->stage_next_cap) { if ((rc = ensure(ctx, ctx->d_stage_next, (size_t)cap * 3))) return rc; ctx->stage_next_cap = cap; }
+        if ((rc = nx.reserve_soa(ctx, cnt))) return rc;
+        if (planes_move) HIPCHK(ctx, hipMemsetAsync(nx.soa, 0, (size_t)nx.soa_cap * 3 * sizeof(double), ctx->copy_stream));
+        if ((rc = nx.reserve_stage(ctx, cnt))) return rc;
     }
     // DMA only: the points stay AoS in the staging buffer and are transposed by the first pass that reads them (SrlAssocArgs::aos) --
     // a transpose kernel on the copy stream would wait for compute units the association kernels (resident back to back, armed
@@ -453,15 +444,15 @@ int srl_sweep_prefetch(srl_ctx *ctx, const double *raw_xyz, int n) {
         if (pre < cnt && pinned) {
             // two DMAs side by side: the prefix on its own stream (its event: up_ev[slot][0]), the rest on the copy stream
             if (!ctx->prefix_stream) { SRL_DISARM(ctx); HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->prefix_stream, hipStreamNonBlocking)); }
-            int rcu = upload_aos(ctx, src, (size_t)pre * 3 * sizeof(double), ctx->d_stage_next, ctx->prefix_stream, false, 1);
+            int rcu = upload_aos(ctx, src, (size_t)pre * 3 * sizeof(double), nx.stage, ctx->prefix_stream, false, 1);
             if (rcu) return rcu;
             HIPCHK(ctx, hipEventRecord(ctx->up_ev[slot][0], ctx->prefix_stream));
-            rcu = upload_aos(ctx, src + (size_t)pre * 3 * sizeof(double), (size_t)(cnt - pre) * 3 * sizeof(double), ctx->d_stage_next + (size_t)pre * 3, ctx->copy_stream, true, 1);
+            rcu = upload_aos(ctx, src + (size_t)pre * 3 * sizeof(double), (size_t)(cnt - pre) * 3 * sizeof(double), nx.stage + (size_t)pre * 3, ctx->copy_stream, true, 1);
             if (rcu) return rcu;
             ctx->up_one_dma[slot] = false;
         } else {
             // (pageable memory goes through the one pinned ring, chunk by chunk, on one stream)
-            int rcu = upload_aos(ctx, src, (size_t)cnt * 3 * sizeof(double), ctx->d_stage_next, ctx->copy_stream, true, pinned);
+            int rcu = upload_aos(ctx, src, (size_t)cnt * 3 * sizeof(double), nx.stage, ctx->copy_stream, true, pinned);
             if (rcu) return rcu;
             ctx->up_one_dma[slot] = true;
         }
@@ -470,15 +461,14 @@ int srl_sweep_prefetch(srl_ctx *ctx, const double *raw_xyz, int n) {
     }
     // (one DMA: its event is both the prefix's and the tail's -- every event record is ~1.5 us of the host's time beside the first kernel)
     HIPCHK(ctx, hipEventRecord(ctx->up_ev[slot][1], ctx->copy_stream));
-    ctx->next_ready = ctx->up_ev[slot][1];
     ctx->next_slot = slot; ctx->next_prefix_n = ctx->up_one_dma[slot] ? cnt : pre;
-    ctx->next_n = cnt; ctx->next_begin = b; ctx->next_total = n;
+    nx.n = cnt; nx.begin = b; nx.total = n;
     return SRL_OK;
 }
 
 int srl_sweep_swap(srl_ctx *ctx) {
     if (!ctx) return SRL_ERR_BAD_ARG;
-    if (ctx->next_n < 0) { SRL_DISARM(ctx); ctx->err = "srl_sweep_swap: nothing prefetched"; return SRL_ERR_NO_SWEEP; }
+    if (ctx->next.n < 0) { SRL_DISARM(ctx); ctx->err = "srl_sweep_swap: nothing prefetched"; return SRL_ERR_NO_SWEEP; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // A launch armed behind the last pass of the sweep that ends here carries BOTH sweep buffers: if the upload has already landed (the
     // usual case: it was issued a whole solve ago) the launch stays and becomes the first pass of the sweep swapped in -- fired through
@@ -491,7 +481,7 @@ int srl_sweep_swap(srl_ctx *ctx) {
     hipEvent_t ev_full = ctx->up_ev[ctx->next_slot][1], ev_pre = ctx->up_ev[ctx->next_slot][one_dma ? 1 : 0];
     hipError_t up_pre = hipEventQuery(ev_pre);                           // (the prefix travels on a stream of its own: asked first)
     hipError_t up = (one_dma || up_pre != hipSuccess) ? up_pre : hipEventQuery(ev_full);
-    if (up_pre == hipErrorNotReady && ctx->armed && ctx->next_n <= ctx->work_cap) {
+    if (up_pre == hipErrorNotReady && ctx->armed.on && ctx->next.n <= ctx->work_cap) {
         // the prefix itself is still on its way (a 100 KB DMA behind the tail of the sweep before it) and a launch is waiting that could
         // serve the new sweep: cancelling it and launching afresh costs ~8 us -- give the DMA up to 25 us first
         const long long t_give_up = steady_ns() + 25000;
@@ -499,27 +489,19 @@ int srl_sweep_swap(srl_ctx *ctx) {
     }
     for (hipError_t e : {up, up_pre})
         if (e != hipSuccess && e != hipErrorNotReady) { ctx->err = std::string("hipEventQuery: ") + hipGetErrorString(e); return SRL_ERR_HIP; }
-    if (up_pre != hipSuccess || ctx->next_n > ctx->work_cap) SRL_DISARM(ctx);   // (growing the work buffers frees them: never under a waiting launch)
+    if (up_pre != hipSuccess || ctx->next.n > ctx->work_cap) SRL_DISARM(ctx);   // (growing the work buffers frees them: never under a waiting launch)
     if (up_pre != hipSuccess) {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ev_full, 0));       // compute waits for the upload; the host does not
         if (!one_dma) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ev_pre, 0));
         up = hipSuccess;                                               // (the stream is ordered behind everything)
     }
-    ctx->tail_pending = up != hipSuccess;
-    ctx->bound_n = 0;                                       // another sweep: the bounds of the old one say nothing about it
     ctx->cur_slot = ctx->next_slot;
-    ctx->cur_prefix_n = up == hipSuccess ? ctx->next_n : ctx->next_prefix_n;
-    ctx->passes_in_solve = 0;
-    std::swap(ctx->d_raw, ctx->d_raw_next);
-    std::swap(ctx->sweep_cap, ctx->next_cap);
-    std::swap(ctx->d_stage_cur, ctx->d_stage_next);
-    std::swap(ctx->stage_cur_cap, ctx->stage_next_cap);
-    ctx->soa_valid_n = 0;                                   // the planes of d_raw are filled by the first pass over the sweep
-    ctx->n = ctx->next_n; ctx->shard_begin = ctx->next_begin; ctx->total_n = ctx->next_total;
-    ctx->next_n = -1;
-    ctx->sweep_loaded = true;
-    ctx->taps_valid = false;
-    return ensure_work(ctx, ctx->n);
+    ctx->cur_prefix_n = up == hipSuccess ? ctx->next.n : ctx->next_prefix_n;
+    std::swap(ctx->cur, ctx->next);
+    ctx->next.n = -1;
+    // (no plane is filled yet: the first pass over the sweep transposes its points out of the staging buffer)
+    srl_sweep_becomes_current(ctx, ctx->cur.n, ctx->cur.begin, ctx->cur.total, 0, up != hipSuccess);
+    return ensure_work(ctx, ctx->cur.n);
 }
 
 int srl_thread_pin_to_gpu_numa(srl_ctx *ctx, int *numa_node) {
@@ -577,9 +559,9 @@ int srl_host_unregister(void *p) {
 
 int srl_sweep_shard(srl_ctx *ctx, int *begin, int *count, int *total) {
     if (!ctx) return SRL_ERR_BAD_ARG;
-    if (begin) *begin = ctx->shard_begin;
-    if (count) *count = ctx->n;
-    if (total) *total = ctx->total_n;
+    if (begin) *begin = ctx->cur.begin;
+    if (count) *count = ctx->cur.n;
+    if (total) *total = ctx->cur.total;
     return SRL_OK;
 }
 
@@ -594,25 +576,24 @@ int srl_set_taps(srl_ctx *ctx, int enable) {
 namespace {
 // light profiling: read the (start, end) event pairs of association launches that have completed by now
 int drain_ring(srl_ctx *ctx, bool all) {
-    while (ctx->ring_tail != ctx->ring_head) {
-        hipEvent_t *e = ctx->ring[ctx->ring_tail % srl_ctx::PROF_RING];
-        if (!all && hipEventQuery(e[1]) != hipSuccess) break;
-        if (all) HIPCHK(ctx, hipEventSynchronize(e[1]));
-        const unsigned slot = ctx->ring_tail % srl_ctx::PROF_RING;
-        if (ctx->ring_void[slot] || ctx->ring_marker[slot]) {      // a cancelled armed launch / an entry that was only the next launch's start
-            ctx->ring_void[slot] = false; ctx->ring_marker[slot] = false; ctx->ring_tail++;
+    SrlProfRing &ring = ctx->prof;
+    for (; ring.tail != ring.head; ring.tail++) {
+        SrlProfRing::Entry &e = ring.at(ring.tail);
+        if (!all && hipEventQuery(e.ev[1]) != hipSuccess) break;
+        if (all) HIPCHK(ctx, hipEventSynchronize(e.ev[1]));
+        if (e.voided || e.marker) {      // a cancelled armed launch / an entry that was only the next launch's start
+            e.voided = false; e.marker = false;
             continue;
         }
-        if (ctx->ring_gen[slot] != ctx->timing_gen) { ctx->ring_tail++; continue; }      // enqueued before the last srl_timing_mark
+        if (e.gen != ring.gen) continue;      // enqueued before the last srl_timing_mark
         float ms = 0.f;
         // an armed launch has no start event of its own: it is enqueued behind the launch of the pass before it and the stream turns
         // to it the moment that one completes -- its start IS the end event of its predecessor in the ring
-        hipEvent_t start = ctx->ring_prev[slot] >= 0 ? ctx->ring[ctx->ring_prev[slot]][1] : e[0];
-        HIPCHK(ctx, hipEventElapsedTime(&ms, start, e[1]));
+        hipEvent_t start = e.prev >= 0 ? ring.e[e.prev].ev[1] : e.ev[0];
+        HIPCHK(ctx, hipEventElapsedTime(&ms, start, e.ev[1]));
         ctx->timing.assoc_ms = ms;
         ctx->timing.sum_assoc_ms += ms;
         ctx->timing.calls += 1;
-        ctx->ring_tail++;
     }
     return SRL_OK;
 }
@@ -626,24 +607,24 @@ int srl_set_profiling(srl_ctx *ctx, int enable) {
     if (ctx->profiling) std::memset(&ctx->timing, 0, sizeof ctx->timing);
     if (ctx->profiling == 2) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        for (int i = 0; i < srl_ctx::PROF_RING; i++)
-            for (int k = 0; k < 2; k++) if (!ctx->ring[i][k]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ring[i][k], hipEventReleaseToDevice));   // (device-scope release: a timing marker between two kernels must not write the L2 back)
-        ctx->ring_head = ctx->ring_tail = 0;
-        std::memset(ctx->ring_void, 0, sizeof ctx->ring_void);
-        std::memset(ctx->ring_marker, 0, sizeof ctx->ring_marker);
-        ctx->prof_count = 0; ctx->ring_last_count = -2; ctx->armed_measured = false; ctx->cur_measured = true;
+        for (SrlProfRing::Entry &e : ctx->prof.e) {
+            for (int k = 0; k < 2; k++) if (!e.ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&e.ev[k], hipEventReleaseToDevice));   // (device-scope release: a timing marker between two kernels must not write the L2 back)
+            e.voided = false; e.marker = false;
+        }
+        ctx->prof.head = ctx->prof.tail = 0;
+        ctx->prof.restart(); ctx->armed.measured = false; ctx->cur_measured = true;
     }
     return SRL_OK;
 }
 
 int srl_timing_mark(srl_ctx *ctx) {
     if (!ctx) return SRL_ERR_BAD_ARG;
-    ctx->timing_gen++;
+    ctx->prof.gen++;
     std::memset(&ctx->timing, 0, sizeof ctx->timing);
     // with a period, the first timed launch behind the mark is the FOURTH (then every period-th): the launches of the first step behind a
     // barrier -- an un-armed launch into an idle GPU and the pass behind it -- would otherwise be one sample in eight of a 20-step region
-    ctx->prof_count = ctx->prof_period > 1 ? (unsigned long long)(ctx->prof_period - 2) : 0ull;
-    ctx->ring_last_count = -2;
+    ctx->prof.count = ctx->prof.period > 1 ? (unsigned long long)(ctx->prof.period - 2) : 0ull;
+    ctx->prof.last_count = -2;
     return SRL_OK;
 }
 
@@ -651,8 +632,8 @@ int srl_set_profiling_period(srl_ctx *ctx, int period) {
     if (!ctx || period < 1 || period > 64) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);
     if (ctx->profiling == 2) { int rc = drain_ring(ctx, true); if (rc) return rc; }
-    ctx->prof_period = period;
-    ctx->prof_count = 0; ctx->ring_last_count = -2; ctx->armed_measured = false; ctx->cur_measured = true;
+    ctx->prof.period = period;
+    ctx->prof.restart(); ctx->armed.measured = false; ctx->cur_measured = true;
     return SRL_OK;
 }
 
@@ -770,12 +751,12 @@ inline void pose_box_write(srl_ctx *ctx, const double *Rn, const double *R, cons
 }  // namespace
 
 int srl_ctx_disarm(srl_ctx *ctx) {
-    if (!ctx || !ctx->armed) return SRL_OK;
-    pose_box_write(ctx, nullptr, nullptr, nullptr, (unsigned)ctx->armed_sig.seq, SRL_ARM_CANCEL);
-    if (ctx->seq < ctx->armed_sig.seq) ctx->seq = ctx->armed_sig.seq;      // the cancelled launch's sequence number is spent
-    ctx->armed = false;
-    if (ctx->armed_ring >= 0) ctx->ring_void[ctx->armed_ring] = true;
-    ctx->armed_ring = -1;
+    if (!ctx || !ctx->armed.on) return SRL_OK;
+    pose_box_write(ctx, nullptr, nullptr, nullptr, (unsigned)ctx->armed.sig.seq, SRL_ARM_CANCEL);
+    if (ctx->seq < ctx->armed.sig.seq) ctx->seq = ctx->armed.sig.seq;      // the cancelled launch's sequence number is spent
+    ctx->armed.on = false;
+    if (ctx->armed.ring >= 0) ctx->prof.e[ctx->armed.ring].voided = true;
+    ctx->armed.ring = -1;
     ctx->arm_stats[2]++;
     return SRL_OK;
 }
@@ -879,7 +860,7 @@ int srl_get_arm_stats(srl_ctx *ctx, uint64_t out[4]) {
 }
 
 // ------------------------------------------------------------------------------------------ hot path
-// one association + reduction pass over the first n_eff keypoints of this rank's shard (n_eff == ctx->n: all of them)
+// one association + reduction pass over the first n_eff keypoints of this rank's shard (n_eff == ctx->cur.n: all of them)
 #define SRL_INTERNAL_FUSED_TIMEOUT 1      // build_residuals_pass only: never leaves srl_build_residuals
 #define SRL_INTERNAL_PEER_TIMEOUT 3       // ... a peer's row had not arrived within the kernel's bounded spin: the HOST decides what follows
 #define SRL_INTERNAL_ARM_EXPIRED 2        // the armed launch this pass fired had given up waiting: the pass is repeated with a normal launch
@@ -887,7 +868,7 @@ int srl_get_arm_stats(srl_ctx *ctx, uint64_t out[4]) {
 // Can the ordered cut-off (optimize.cpp:107) trigger?  Only when max_num_residuals <= number of keypoints; max_num_residuals <= 0:
 // the loop stops at the first keypoint with a plane, wherever (in whichever shard) that is.
 static bool cut_possible(const srl_ctx *ctx, const srl_icp_opts *o) {
-    return o->max_num_residuals <= 0 || (long long)o->max_num_residuals <= (long long)ctx->total_n;
+    return o->max_num_residuals <= 0 || (long long)o->max_num_residuals <= (long long)ctx->cur.total;
 }
 
 // How this rank's result meets the other ranks': one rank; direct peer exchange (srl_peer_attach); RCCL on the context's stream
@@ -979,11 +960,11 @@ static int plan_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, in
 // the kernel arguments of one pass (all but its sequence number and exchange tag)
 static void prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o, int n_eff, const PassPlan &p, SrlAssocArgs &a) {
     std::memset(&a, 0, sizeof a);
-    a.raw_x = ctx->d_raw;
-    a.raw_y = ctx->d_raw + ctx->sweep_cap;
-    a.raw_z = ctx->d_raw + 2 * (size_t)ctx->sweep_cap;
+    a.raw_x = ctx->cur.x();
+    a.raw_y = ctx->cur.y();
+    a.raw_z = ctx->cur.z();
     a.n = n_eff;
-    a.aos = (n_eff > ctx->soa_valid_n) ? ctx->d_stage_cur : nullptr;     // the pass reads (all of) its points AoS and files the SoA planes
+    a.aos = (n_eff > ctx->soa_valid_n) ? ctx->cur.stage : nullptr;     // the pass reads (all of) its points AoS and files the SoA planes
     a.table = ctx->d_table;
     a.table_mask = ctx->table_cap - 1;
     a.slabs = ctx->d_slabs;
@@ -1058,24 +1039,27 @@ static int grow_pass_buffers(srl_ctx *ctx, const PassPlan &p) {
     int rc;
     ctx->taps_valid = false;
     if (ctx->taps) {
-        if ((rc = ensure_taps(ctx, ctx->n, p.K))) return rc;
-        if (ctx->n > 0) {
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_ids, 0xFF, (size_t)ctx->n * p.K * sizeof(int), ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_normal, 0, (size_t)ctx->n * 3 * sizeof(double), ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_a2d, 0, (size_t)ctx->n * sizeof(double), ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_offset, 0, (size_t)ctx->n * sizeof(double), ctx->stream));
+        const size_t n = (size_t)ctx->cur.n;
+        if ((rc = ensure_taps(ctx, ctx->cur.n, p.K))) return rc;
+        if (n > 0) {
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_ids, 0xFF, n * p.K * sizeof(int), ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_normal, 0, n * 3 * sizeof(double), ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_a2d, 0, n * sizeof(double), ctx->stream));
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_tap_offset, 0, n * sizeof(double), ctx->stream));
         }
     }
     ctx->last_nblocks = p.nblocks;
     if (p.nblocks > ctx->block_cap) {  // a forced launch shape can need more workgroups than ensure_work provided for
+        ctx->block_cap = 0;
         if ((rc = ensure(ctx, ctx->d_partials, (size_t)p.nblocks * SRL_PART_STRIDE))) return rc;
         if ((rc = ensure(ctx, ctx->d_binfo, (size_t)p.nblocks))) return rc;
         ctx->block_cap = p.nblocks;
     }
-    if (ctx->profiling == 2 && ctx->ring_head - ctx->ring_tail >= (unsigned)srl_ctx::PROF_RING && (rc = drain_ring(ctx, true))) return rc;
+    if (ctx->profiling == 2 && ctx->prof.pending() >= (unsigned)SrlProfRing::SLOTS && (rc = drain_ring(ctx, true))) return rc;
     if (p.fused && p.transport == Transport::rccl && !ctx->d_mail && (rc = ensure(ctx, ctx->d_mail, 1))) return rc;
     const size_t need = (size_t)p.nblocks * p.kpb * 16;
     if (p.fuse_cut && need > ctx->rec_granule_cap) {
+        ctx->rec_granule_cap = 0;
         if ((rc = ensure(ctx, ctx->d_rec_granules, need))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->d_rec_granules, 0, need * sizeof(unsigned long long), ctx->stream));   // no stale tag can match
         ctx->rec_granule_cap = need;
@@ -1117,26 +1101,24 @@ static int fire_or_cancel(srl_ctx *ctx, const PassPlan &p, SrlAssocArgs &a, unsi
     // anything else is launched normally BEHIND the full upload (a resident kernel cannot be made to wait for an event)
     bool needs_tail = false;
     if (ctx->tail_pending) {
-        if (hipEventQuery(ctx->up_ev[ctx->cur_slot][1]) == hipSuccess) { ctx->tail_pending = false; ctx->cur_prefix_n = ctx->n; }
+        if (hipEventQuery(ctx->up_ev[ctx->cur_slot][1]) == hipSuccess) { ctx->tail_pending = false; ctx->cur_prefix_n = ctx->cur.n; }
         else needs_tail = a.n > ctx->cur_prefix_n;
         (void)hipGetLastError();
     }
-    if (!ctx->armed) return SRL_OK;
+    SrlArmedLaunch &armed = ctx->armed;
+    if (!armed.on) return SRL_OK;
     const SrlAssocArgs sg = arm_signature(a);
-    const double age_us = (double)(steady_ns() - ctx->armed_at_ns) * 1e-3;
+    const double age_us = (double)(steady_ns() - armed.at_ns) * 1e-3;
     // which of the launch's two sweep buffers holds this pass's sweep (the one it was armed on, or -- after srl_sweep_swap -- the other)
-    // (on the buffer it was armed on the launch reads the SoA planes: they must be valid; on the other one it reads the staging buffer)
-    const bool on_raw = a.raw_x == ctx->armed_raw && ctx->sweep_cap == ctx->armed_raw_cap && a.aos == nullptr;
-    const bool on_alt = !on_raw && ctx->armed_alt != nullptr && a.raw_x == ctx->armed_alt && ctx->sweep_cap == ctx->armed_alt_cap &&
-                        a.aos != nullptr && a.aos == ctx->armed_alt_aos;
-    if (p.arm_ok && !needs_tail && age_us < ctx->arm_host_linger_us && p.nb == ctx->armed_nb && p.kpw == ctx->armed_kpw &&
-        p.nblocks <= ctx->armed_nblocks && (on_raw || on_alt) && std::memcmp(&sg, &ctx->armed_sig, sizeof sg) == 0) {
-        pose_box_write(ctx, a.Rn, a.R, a.t, (unsigned)seq_now, SRL_ARM_GO | (on_alt ? SRL_ARM_ALT : 0u), (unsigned)a.n, a.t_last);
-        ctx->armed = false;
-        ctx->armed_ring = -1;
+    const SrlArmedLaunch::Serves serves = armed.serves(ctx->cur, a);
+    if (p.arm_ok && !needs_tail && age_us < ctx->arm_host_linger_us && p.nb == armed.nb && p.kpw == armed.kpw &&
+        p.nblocks <= armed.nblocks && serves != SrlArmedLaunch::none && std::memcmp(&sg, &armed.sig, sizeof sg) == 0) {
+        pose_box_write(ctx, a.Rn, a.R, a.t, (unsigned)seq_now, SRL_ARM_GO | (serves == SrlArmedLaunch::alternate ? SRL_ARM_ALT : 0u), (unsigned)a.n, a.t_last);
+        armed.on = false;
+        armed.ring = -1;
         ctx->arm_stats[1]++;
-        ctx->cur_measured = ctx->armed_measured;
-        ctx->cur_gen = ctx->armed_gen;
+        ctx->cur_measured = armed.measured;
+        ctx->cur_gen = armed.gen;
         fired = true;
         return SRL_OK;
     }
@@ -1150,8 +1132,8 @@ static int fire_or_cancel(srl_ctx *ctx, const PassPlan &p, SrlAssocArgs &a, unsi
 // leaves its end event as the second's start; the others carry no event at all (an event record costs ~2.5 us of the loop).
 // 2 = timed, 1 = start marker of the next launch, 0 = no events
 static int prof_role(const srl_ctx *ctx) {
-    if (ctx->prof_period <= 1) return 2;
-    const unsigned long long r = ctx->prof_count % (unsigned long long)ctx->prof_period;
+    if (ctx->prof.period <= 1) return 2;
+    const unsigned long long r = ctx->prof.count % (unsigned long long)ctx->prof.period;
     return r == 1 ? 2 : (r == 0 ? 1 : 0);
 }
 
@@ -1160,34 +1142,36 @@ static int prof_role(const srl_ctx *ctx) {
 static int launch_assoc(srl_ctx *ctx, const PassPlan &p, const SrlAssocArgs &args, bool armed) {
     if (!armed && ctx->tail_pending) {       // a normal launch reads whatever it likes of the sweep: behind the whole upload
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->up_ev[ctx->cur_slot][1], 0));
-        ctx->tail_pending = false; ctx->cur_prefix_n = ctx->n;
+        ctx->tail_pending = false; ctx->cur_prefix_n = ctx->cur.n;
     }
+    SrlProfRing &ring = ctx->prof;
     const bool prof = ctx->profiling == 1, prof_light = ctx->profiling == 2;
     const int role = prof_light ? prof_role(ctx) : 0;
     int prev = -1;
     if (armed && role != 0) {
         int rc;
-        if (ctx->ring_head - ctx->ring_tail >= (unsigned)srl_ctx::PROF_RING - 2 && (rc = drain_ring(ctx, true))) return rc;
+        if (ring.pending() >= (unsigned)SrlProfRing::SLOTS - 2 && (rc = drain_ring(ctx, true))) return rc;
         // the launch before this one is the ring entry before (if it left one): its end event is the armed launch's start (an event
         // record between the two kernels would sit on the path the armed launch is there to shorten: measured +5 us per iteration)
-        if (ctx->ring_head != 0 && !ctx->ring_void[(ctx->ring_head - 1) % srl_ctx::PROF_RING] && ctx->ring_last_count == (long long)ctx->prof_count - 1)
-            prev = (int)((ctx->ring_head - 1) % srl_ctx::PROF_RING);
+        if (ring.head != 0 && !ring.at(ring.head - 1).voided && ring.last_count == (long long)ring.count - 1)
+            prev = (int)((ring.head - 1) % SrlProfRing::SLOTS);
     }
-    const unsigned slot = ctx->ring_head % srl_ctx::PROF_RING;
+    const unsigned slot = ring.head % SrlProfRing::SLOTS;
+    SrlProfRing::Entry &entry = ring.e[slot];
     if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (role == 2 && prev < 0) HIPCHK(ctx, hipEventRecord(ctx->ring[slot][0], ctx->stream));
+    if (role == 2 && prev < 0) HIPCHK(ctx, hipEventRecord(entry.ev[0], ctx->stream));
     HIPCHK(ctx, srl_launch_assoc(args, p.nb, p.kpw, p.wpb, ctx->stream));
     if (prof) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     if (role != 0) {
-        HIPCHK(ctx, hipEventRecord(ctx->ring[slot][1], ctx->stream));
-        ctx->ring_prev[slot] = prev; ctx->ring_marker[slot] = role == 1; ctx->ring_void[slot] = false; ctx->ring_gen[slot] = ctx->timing_gen;
-        ctx->ring_last_count = (long long)ctx->prof_count;
-        ctx->ring_head++;
+        HIPCHK(ctx, hipEventRecord(entry.ev[1], ctx->stream));
+        entry.prev = prev; entry.marker = role == 1; entry.voided = false; entry.gen = ring.gen;
+        ring.last_count = (long long)ring.count;
+        ring.head++;
     }
-    if (prof_light) ctx->prof_count++;
+    if (prof_light) ring.count++;
     const bool measured = !prof_light || role == 2;       // one of the timed launches?
-    if (armed) { ctx->armed_ring = role != 0 ? (int)slot : -1; ctx->armed_measured = measured; ctx->armed_gen = ctx->timing_gen; }
-    else { ctx->cur_measured = measured; ctx->cur_gen = ctx->timing_gen; }
+    if (armed) { ctx->armed.ring = role != 0 ? (int)slot : -1; ctx->armed.measured = measured; ctx->armed.gen = ring.gen; }
+    else { ctx->cur_measured = measured; ctx->cur_gen = ring.gen; }
     return SRL_OK;
 }
 
@@ -1198,7 +1182,7 @@ static int launch_assoc(srl_ctx *ctx, const PassPlan &p, const SrlAssocArgs &arg
 static bool arm_wanted(const srl_ctx *ctx) {
     return ctx->arm_mode == 2 ||
            (live_contexts(ctx->device) <= 1 && !ctx->peer_shares_device && !ctx->comm_shares_device &&
-            (ctx->next_n >= 0 || ctx->expected_passes == 0 || ctx->passes_in_solve + 1 < ctx->expected_passes));
+            (ctx->next.n >= 0 || ctx->expected_passes == 0 || ctx->passes_in_solve + 1 < ctx->expected_passes));
 }
 
 // Arm the next pass now, while this one runs: this pass's arguments, the sequence number this context hands out next, the pose to come
@@ -1210,12 +1194,13 @@ static int arm_next(srl_ctx *ctx, const PassPlan &p, const SrlAssocArgs &a) {
     nx.bound_use = a.bound_in ? a.n : 0;              // this pass writes the bounds of its a.n keypoints; the kernel drops them if fired for another sweep
     // the context's other sweep buffer, if it exists: the launch can then be fired for the sweep srl_sweep_swap makes current
     // (sharded ranks too: every rank prefetches and swaps its own point range, the launch learns its count with the pose)
-    const bool has_alt = ctx->d_raw_next != nullptr && ctx->next_cap > 0 && ctx->d_stage_next != nullptr;
+    const SrlSweepSlot &alt = ctx->next;
+    const bool has_alt = alt.has_buffers();
     nx.aos = nullptr;                                  // (its own buffer's planes are valid once this pass has run)
-    nx.alt_aos = has_alt ? ctx->d_stage_next : nullptr;
-    nx.alt_x = has_alt ? ctx->d_raw_next : nullptr;
-    nx.alt_y = has_alt ? ctx->d_raw_next + ctx->next_cap : nullptr;
-    nx.alt_z = has_alt ? ctx->d_raw_next + 2 * (size_t)ctx->next_cap : nullptr;
+    nx.alt_aos = has_alt ? alt.stage : nullptr;
+    nx.alt_x = has_alt ? alt.x() : nullptr;
+    nx.alt_y = has_alt ? alt.y() : nullptr;
+    nx.alt_z = has_alt ? alt.z() : nullptr;
     if (p.transport == Transport::peer) {             // the exchange this launch will take part in: the one after this pass's
         const ExchangeTag t = exchange_tag(ctx->peer_seq + 1);
         nx.peer_epoch = t.epoch;
@@ -1227,12 +1212,13 @@ static int arm_next(srl_ctx *ctx, const PassPlan &p, const SrlAssocArgs &a) {
     nx.pose_epoch = (unsigned)nx.seq;
     nx.arm_linger_ticks = ctx->arm_linger_ticks;
     if ((rc = launch_assoc(ctx, p, nx, true))) return rc;
-    ctx->armed_sig = arm_signature(nx);
-    ctx->armed_nb = p.nb; ctx->armed_kpw = p.kpw; ctx->armed_nblocks = p.nblocks;
-    ctx->armed_raw = nx.raw_x; ctx->armed_raw_cap = ctx->sweep_cap;
-    ctx->armed_alt = nx.alt_x; ctx->armed_alt_cap = has_alt ? ctx->next_cap : 0; ctx->armed_alt_aos = nx.alt_aos;
-    ctx->armed_at_ns = steady_ns();
-    ctx->armed = true;
+    SrlArmedLaunch &armed = ctx->armed;      // (ring, measured, gen: filed by launch_assoc)
+    armed.sig = arm_signature(nx);
+    armed.nb = p.nb; armed.kpw = p.kpw; armed.nblocks = p.nblocks;
+    armed.raw = nx.raw_x; armed.raw_cap = ctx->cur.soa_cap;
+    armed.alt = nx.alt_x; armed.alt_cap = has_alt ? alt.soa_cap : 0; armed.alt_aos = nx.alt_aos;
+    armed.at_ns = steady_ns();
+    armed.on = true;
     ctx->arm_stats[0]++;
     return SRL_OK;
 }
@@ -1393,7 +1379,7 @@ static int finish_pass(srl_ctx *ctx, const PassPlan &p, const srl_icp_opts *o, c
     if (p.fused && !p.fuse_cut) {
         // a fused pass without a cut visits every keypoint it was given, on every rank: anything else means workgroups ran on another
         // keypoint count than the host fired them with (a relayed pose box once lost the count of a swapped-in sweep)
-        const long long expect = ctx->nranks > 1 ? (long long)ctx->total_n : (long long)n_eff;
+        const long long expect = ctx->nranks > 1 ? (long long)ctx->cur.total : (long long)n_eff;
         if (visited_total != expect) {
             char buf[256];
             std::snprintf(buf, sizeof buf, "fused pass visited %lld of %lld keypoints (fired %d, seq %llu; residuals %.0f, time-out flag %.0f, marker %lld)", visited_total, expect,
@@ -1453,10 +1439,10 @@ static int account_pass(srl_ctx *ctx, const PassPlan &p, int n_eff, const PassCl
     const double sum_pk = ctx->h_out->d_sum_pk;
     const long long side = 2 * p.nb + 1;
     const long long per_kp = 24 + 12 * side * side * side;
-    const double pk_share = (ctx->nranks > 1 && ctx->total_n > 0) ? sum_pk * ((double)ctx->n / (double)ctx->total_n) : sum_pk;
+    const double pk_share = (ctx->nranks > 1 && ctx->cur.total > 0) ? sum_pk * ((double)ctx->cur.n / (double)ctx->cur.total) : sum_pk;
     ctx->timing.algorithmic_bytes = per_kp * (long long)n_eff + (long long)(12.0 * pk_share);
     // (light profiling with a period: only the passes whose launch is one of the timed ones count, so bytes and durations pair up)
-    if (prof || (prof_light && ctx->cur_measured && ctx->cur_gen == ctx->timing_gen)) {
+    if (prof || (prof_light && ctx->cur_measured && ctx->cur_gen == ctx->prof.gen)) {
         ctx->timing.sum_algorithmic_bytes += ctx->timing.algorithmic_bytes; ctx->timing.sum_keypoints += prof_light ? n_eff : 0; ctx->timing.sum_passes += 1;
     }
     if (ctx->profiling == 3) {
@@ -1519,7 +1505,7 @@ static int build_residuals_pass(srl_ctx *ctx, const srl_frame *f, const srl_icp_
     if ((rc = wait_result(ctx, p, seq_now, fired, last_visited_local))) return rc;
     if (ctx->profiling == 1) HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     clk.res = std::chrono::steady_clock::now();
-    if (ctx->armed) ctx->armed_at_ns = steady_ns();      // the armed launch starts waiting about now (when this pass ends): its age counts from here
+    if (ctx->armed.on) ctx->armed.at_ns = steady_ns();      // the armed launch starts waiting about now (when this pass ends): its age counts from here
     if (stamps) stamps[2] = clock_ns(clk.res);
     if ((rc = finish_pass(ctx, p, o, a, n_eff, last_visited_local, seq_now, fired, out))) return rc;
     if ((rc = account_pass(ctx, p, n_eff, clk))) return rc;
@@ -1532,7 +1518,7 @@ int srl_fetch_neighbors(srl_ctx *ctx, int32_t *ids, uint8_t *status, int32_t *nu
     SRL_DISARM(ctx);
     if (!ctx->taps_valid) { ctx->err = "taps were not enabled for the last srl_build_residuals"; return SRL_ERR_BAD_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int n = ctx->n, K = ctx->last_K;
+    const int n = ctx->cur.n, K = ctx->last_K;
     if (n == 0) return SRL_OK;
     if (ids) HIPCHK(ctx, hipMemcpyAsync(ids, ctx->d_tap_ids, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (status) HIPCHK(ctx, hipMemcpyAsync(status, ctx->d_status, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1548,7 +1534,7 @@ int srl_fetch_residuals(srl_ctx *ctx, double *normal, double *a2D, double *weigh
     SRL_DISARM(ctx);
     if (!ctx->taps_valid) { ctx->err = "taps were not enabled for the last srl_build_residuals"; return SRL_ERR_BAD_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int n = ctx->n;
+    const int n = ctx->cur.n;
     if (n == 0) return SRL_OK;
     std::vector<double> rec((size_t)n * 8);
     HIPCHK(ctx, hipMemcpyAsync(rec.data(), ctx->d_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1731,7 +1717,7 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
     if (!ctx || !f || !o || !out) return SRL_ERR_BAD_ARG;
     if (!ctx->d_table) return SRL_ERR_NO_MAP;
     if (!ctx->sweep_loaded) return SRL_ERR_NO_SWEEP;
-    if (ctx->total_n == 0) {
+    if (ctx->cur.total == 0) {
         // an empty keypoint set is a valid pass: the loop of optimize.cpp:68 does not run, num_residuals = 0 fails the
         // test at :110 and the caller gets summary.success = false (no exception, nothing visited)
         std::memset(out, 0, sizeof *out);
@@ -1745,12 +1731,12 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
     // keypoints than max, nothing can be concluded and the pass is repeated over the whole shard.  Same accepted set and
     // same cut as the full pass; the sums agree up to FP64 summation order (a short pass uses fewer keypoints per
     // workgroup, srl_keypoints_per_block).  Taps keep the full pass.
-    int n_eff = ctx->n;
+    int n_eff = ctx->cur.n;
     if (pass_transport(ctx) == Transport::single && !ctx->taps && o->max_num_residuals > 0) {
         const long long pre = ((4LL * o->max_num_residuals + 2048 + 63) / 64) * 64;
-        if (pre < (long long)ctx->n) n_eff = (int)pre;
+        if (pre < (long long)ctx->cur.n) n_eff = (int)pre;
     }
-    ctx->prefix_hint = n_eff < ctx->n ? n_eff : 0;      // what the next prefetch sends first (srl_sweep_prefetch)
+    ctx->prefix_hint = n_eff < ctx->cur.n ? n_eff : 0;      // what the next prefetch sends first (srl_sweep_prefetch)
     // One attempt at a pass = build_residuals_pass, repeated while a PEER's row has not arrived (direct peer exchange only).
     auto attempt = [&](int n_pass) -> int {
         const unsigned long long peer_seq0 = ctx->peer_seq;              // (a repeated pass re-polls the SAME exchanges)
@@ -1762,7 +1748,7 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
             // run again with the same tags until the late rank's row is there -- the late rank finds every row and returns SRL_OK as well.
             // No rank runs ahead meanwhile: the next exchange needs a row of THIS rank.  Past the deadline the session is given up for
             // everybody: the poison word of every inbox is set, and a rank that times out looks at its own word first.
-            const int rcd = ctx->armed ? srl_ctx_disarm(ctx) : SRL_OK;
+            const int rcd = ctx->armed.on ? srl_ctx_disarm(ctx) : SRL_OK;
             if (rcd) return rcd;
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             unsigned long long poisoned = 0;
@@ -1804,7 +1790,7 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
         if (r == SRL_INTERNAL_FUSED_TIMEOUT) {
             const bool fuse = ctx->fuse_reduce;
             ctx->fuse_reduce = false;
-            const int rcd = ctx->armed ? srl_ctx_disarm(ctx) : SRL_OK;      // (before waiting for the stream: nobody would fire it)
+            const int rcd = ctx->armed.on ? srl_ctx_disarm(ctx) : SRL_OK;      // (before waiting for the stream: nobody would fire it)
             const hipError_t es = rcd ? hipSuccess : hipStreamSynchronize(ctx->stream);
             if (rcd || es != hipSuccess) {
                 ctx->fuse_reduce = fuse;                                     // never leave the context un-fused behind an error
@@ -1819,8 +1805,8 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
         return r;
     };
     int rc = pass(n_eff);
-    if ((rc == SRL_OK || rc == SRL_ERR_NAN_PLANARITY) && n_eff < ctx->n && out->num_residuals < o->max_num_residuals)
-        rc = pass(ctx->n);
+    if ((rc == SRL_OK || rc == SRL_ERR_NAN_PLANARITY) && n_eff < ctx->cur.n && out->num_residuals < o->max_num_residuals)
+        rc = pass(ctx->cur.n);
     ctx->passes_in_solve++;
     return rc;
 }
@@ -1830,7 +1816,7 @@ int srl_solve_end(srl_ctx *ctx) {
     if (ctx->passes_in_solve > 0) ctx->expected_passes = ctx->passes_in_solve;
     ctx->passes_in_solve = 0;
     // a launch armed behind the last pass is only worth keeping when the next sweep is already on its way (it will be that sweep's first pass)
-    if (ctx->armed && ctx->next_n < 0 && ctx->arm_mode != 2) return srl_ctx_disarm(ctx);
+    if (ctx->armed.on && ctx->next.n < 0 && ctx->arm_mode != 2) return srl_ctx_disarm(ctx);
     return SRL_OK;
 }
 

@@ -29,7 +29,76 @@ struct SrlEpochTable {
 #define SRL_PEER_DEVICE_WORD (SRL_PEER_INBOX_GRANULES + 1)
 #define SRL_PEER_INBOX_ALLOC_GRANULES (SRL_PEER_INBOX_GRANULES + 8)
 
+struct srl_ctx;
+
+// One of the context's two sweep buffers (this rank's shard).  `cur` is the sweep the passes read; `next` is the one srl_sweep_prefetch
+// fills on the copy stream while `cur` is solved, and srl_sweep_swap exchanges the two.  Both blocks are grow-only, max(n, 1024) points.
+struct SrlSweepSlot {
+    double *soa = nullptr;             // SoA x|y|z, stride soa_cap
+    double *stage = nullptr;           // AoS staging: the DMA's target (no kernel runs on the copy stream); transposed into soa by the
+                                       // first pass that touches the points (SrlAssocArgs::aos)
+    int soa_cap = 0, stage_cap = 0;    // capacities (points)
+    int n = 0, begin = 0, total = 0;   // shard size, its first point, points of the whole sweep (next: n < 0 = nothing prefetched)
+    double *x() const { return soa; }
+    double *y() const { return soa + soa_cap; }
+    double *z() const { return soa + 2 * (size_t)soa_cap; }
+    bool has_buffers() const { return soa != nullptr && soa_cap > 0 && stage != nullptr; }   // an armed launch can carry it as its alternate
+    int reserve_soa(srl_ctx *ctx, int points) { return reserve(ctx, soa, soa_cap, points); }
+    int reserve_stage(srl_ctx *ctx, int points) { return reserve(ctx, stage, stage_cap, points); }
+private:
+    static int reserve(srl_ctx *ctx, double *&block, int &cap, int points);
+};
+
+// The ARMED launch (srl_capi.cpp: arm_next / fire_or_cancel / srl_ctx_disarm): the kernel of the NEXT pass, enqueued while the current
+// one runs and waiting, resident, for its pose.
+struct SrlArmedLaunch {
+    bool on = false;
+    SrlAssocArgs sig;                           // its arguments with the pose zeroed (arm_signature): a pass must equal them to fire it
+    int nb = 0, kpw = 0;
+    int nblocks = 0;                            // its grid (a pass over fewer keypoints may fire it: the surplus workgroups find empty tiles)
+    const double *raw = nullptr, *alt = nullptr;   // x planes of the sweep buffer it was armed on / of the context's other buffer
+    const double *alt_aos = nullptr;            // the staging buffer it reads when it is fired for the other buffer
+    int raw_cap = 0, alt_cap = 0;               // ... and their strides (capacity in points)
+    int ring = -1;                              // light profiling: ring slot of its event pair (-1: none)
+    long long at_ns = 0;                        // steady clock at arm time
+    bool measured = false;                      // light profiling: is it one of the timed launches ...
+    unsigned gen = 0;                           // ... and of which srl_timing_mark generation
+    // Which of its two sweep buffers holds the sweep of the pass with arguments `a` (cur: the context's current slot)?  On the buffer it
+    // was armed on it reads the SoA planes: they must be valid (no a.aos).  On the other one -- after srl_sweep_swap -- it reads the
+    // staging buffer.
+    enum Serves { none, own, alternate };
+    Serves serves(const SrlSweepSlot &cur, const SrlAssocArgs &a) const {
+        if (a.raw_x == raw && cur.soa_cap == raw_cap && a.aos == nullptr) return own;
+        if (alt != nullptr && a.raw_x == alt && cur.soa_cap == alt_cap && a.aos != nullptr && a.aos == alt_aos) return alternate;
+        return none;
+    }
+};
+
+// Light profiling (srl_set_profiling(ctx, 2)): the event pairs of association launches, read lazily (srl_capi.cpp: launch_assoc / drain_ring)
+struct SrlProfRing {
+    static constexpr int SLOTS = 512;
+    struct Entry {
+        hipEvent_t ev[2] = {};                  // start, end
+        int prev = -1;                          // slot whose END event is this launch's start (armed launches), -1 = own start event
+        unsigned gen = 0;                       // srl_timing_mark generation it was enqueued in
+        bool voided = false;                    // a cancelled armed launch (not counted)
+        bool marker = false;                    // with a period: only serves as the NEXT launch's start (not timed itself)
+    };
+    Entry e[SLOTS];
+    unsigned head = 0, tail = 0;                // [tail, head) recorded and not yet read
+    int period = 1;                             // srl_set_profiling_period: every period-th association launch is timed
+    unsigned long long count = 0;               // association launches seen (own and armed)
+    long long last_count = -2;                  // `count` of the launch behind the newest entry
+    // srl_timing_mark: "the sums start here" without a read-back -- launches enqueued before the mark carry an older generation and are
+    // left out when their events are read (their passes' bytes likewise)
+    unsigned gen = 0;
+    Entry &at(unsigned i) { return e[i % SLOTS]; }
+    unsigned pending() const { return head - tail; }
+    void restart() { count = 0; last_count = -2; }
+};
+
 struct srl_ctx {
+    srl_ctx() { next.n = -1; }
     int device = 0;
     bool counted = false;              // this context is in the per-device census (srl_capi.cpp: g_live_ctx)
     hipStream_t stream = nullptr;
@@ -43,31 +112,19 @@ struct srl_ctx {
     int num_voxels = 0;
     long long num_points = 0;
 
-    // sweep (this rank's shard)
-    double *d_raw = nullptr;           // SoA x|y|z, stride sweep_cap
-    int sweep_cap = 0;
-    int n = 0;                         // shard size
-    int shard_begin = 0;
-    int total_n = 0;
+    // the current sweep, and the NEXT one (srl_sweep_prefetch / srl_sweep_swap): uploaded on its own stream while the current one is solved
+    SrlSweepSlot cur, next;
     bool sweep_loaded = false;         // a sweep (possibly empty) has been uploaded / selected
+    int soa_valid_n = 0;               // leading keypoints of the current sweep whose SoA planes are filled
     int search_select_mode = 0;        // srl_debug_set_search_select_mode: selection path of srl_search_neighbors (tests)
     int select_mode = 0;               // srl_debug_set_select_mode: selection path of srl_build_residuals (tests; 0 = automatic)
     int ablate = 0;                    // srl_debug_set_ablate (profiling tools only; never set by the product)
     void (*overlap_fn)(void *) = nullptr;   // srl_build_residuals_overlap: host work to run while the kernels are in flight
     void *overlap_user = nullptr;
 
-    // the NEXT sweep (srl_sweep_prefetch / srl_sweep_swap): uploaded on its own stream while the current one is solved
-    double *d_raw_next = nullptr;      // SoA, stride next_cap
-    double *d_stage_next = nullptr;    // AoS staging of the prefetch: the DMA's target (no kernel runs on the copy stream)
-    double *d_stage_cur = nullptr;     // ... of the sweep that is current now (swapped with d_stage_next by srl_sweep_swap): its points are
-                                       // transposed into d_raw by the first pass that touches them (SrlAssocArgs::aos)
-    int soa_valid_n = 0;               // leading keypoints of the current sweep whose SoA planes in d_raw are filled
-    int next_cap = 0, stage_next_cap = 0, stage_cur_cap = 0;   // capacities (points) of d_raw_next / d_stage_next / d_stage_cur
-    int next_n = -1, next_begin = 0, next_total = 0;   // next_n < 0: nothing prefetched
     hipStream_t copy_stream = nullptr;
     hipStream_t prefix_stream = nullptr;  // the PREFIX of a prefix-first prefetch: a stream (and with it a DMA engine) of its own, beside the tail
     int num_cu = 256;                 // compute units of the device (launch-shape policy)
-    hipEvent_t next_ready = nullptr;      // the prefetched sweep has landed completely (the slot's FULL event: up_ev[next_slot][1])
     // PREFIX-FIRST upload.  With a finite max_num_residuals a solve visits only the first few thousand keypoints of
     // a sweep (srl_build_residuals: the prefix pass), yet the whole sweep had to cross PCIe before its first pass could fire.  The prefetch
     // therefore goes out as TWO DMAs -- the prefix the running solve's passes visit (prefix_hint) and the rest -- each with its own event and
@@ -75,10 +132,12 @@ struct srl_ctx {
     // engine and the stream's queue costs; side by side the prefix lands ~11 us after the call and the tail in the ~36 us one copy takes);
     // two event pairs alternating between consecutive prefetches.  srl_sweep_swap keeps a waiting launch once the PREFIX has landed; a
     // pass that needs more (the whole-shard repeat, other options, anything launched normally) first orders the stream behind the FULL event.
+    // (The pairs alternate per PREFETCH, the buffers per SWAP -- a prefetch that replaces one never swapped fills the same buffer behind the
+    // other pair -- so the pairs, their parity and what they cover belong to the context, not to a SrlSweepSlot.  "slot" below = pair.)
     hipEvent_t up_ev[2][2] = {};          // [slot][0 = prefix landed, 1 = everything landed]
     bool up_one_dma[2] = {true, true};    // the slot's upload went out as ONE DMA: only its full event was recorded
     int next_slot = 0;                    // slot of the prefetch in flight / last issued
-    int next_prefix_n = 0;                // points of it covered by the prefix event (== next_n: one DMA)
+    int next_prefix_n = 0;                // points of it covered by the prefix event (== next.n: one DMA)
     int prefix_hint = 0;                  // keypoints the passes of the running solve visit when that is a prefix of the shard (0: whole sweeps)
     // neighbourhood bounds (SrlAssocArgs::bound_in): 4 floats per keypoint, written by every pass; entries [0, bound_n) were written on the
     // CURRENT sweep and map with the options of bound_sig -- reset by whatever changes one of them
@@ -122,13 +181,13 @@ struct srl_ctx {
     hipEvent_t upload_ev = nullptr;
     bool upload_pending = false;
 
-    // pinned staging ring of srl_sweep_upload (pageable sources): CPU copy of one chunk overlaps the DMA of the previous
-    static constexpr int RING_SLOTS = 4;
-    static constexpr int RING_SLOT_BYTES = 256 * 1024;
-    char *h_ring = nullptr;
-    hipEvent_t ring_ev[RING_SLOTS] = {};
-    bool ring_busy[RING_SLOTS] = {};
-    unsigned ring_next = 0;
+    // pinned staging chunks of a sweep upload from pageable memory (upload_aos): CPU copy of one chunk overlaps the DMA of the previous
+    static constexpr int CHUNK_SLOTS = 4;
+    static constexpr int CHUNK_BYTES = 256 * 1024;
+    char *h_chunks = nullptr;
+    hipEvent_t chunk_ev[CHUNK_SLOTS] = {};
+    bool chunk_busy[CHUNK_SLOTS] = {};
+    unsigned chunk_next = 0;
 
     // pinned host scratch (grow-only) for the small D2H / H2D hops of the frame pipeline: pageable copies are staged
     // synchronously by the runtime and cost more than the kernels around them
@@ -184,32 +243,16 @@ struct srl_ctx {
     unsigned long long *pose_box_pinned = nullptr;   // kind 0 allocation (hipHostMalloc)
     unsigned long long *pose_box_dev = nullptr;      // kind 1 allocation (hipExtMallocWithFlags, fine-grained)
     unsigned long long *d_pose_relay = nullptr;
-    bool armed = false;
-    SrlAssocArgs armed_sig;                     // the armed launch's arguments with the pose zeroed: a pass must equal them to fire it
-    int armed_nb = 0, armed_kpw = 0;
-    int armed_nblocks = 0;                      // grid of the armed launch (a pass over fewer keypoints may fire it: the surplus workgroups find empty tiles)
-    const double *armed_raw = nullptr, *armed_alt = nullptr;   // x planes of the sweep buffer the launch was armed on / of the context's other buffer
-    const double *armed_alt_aos = nullptr;      // the staging buffer the launch reads when it is fired for the other buffer
-    int armed_raw_cap = 0, armed_alt_cap = 0;   // ... and their strides (capacity in points)
-    int armed_ring = -1;                        // light profiling: ring slot of the armed launch's event pair (-1: none)
-    long long armed_at_ns = 0;                  // steady clock at arm time
+    SrlArmedLaunch armed;
     double arm_host_linger_us = 150.0;          // an armed launch older than this is cancelled, never fired (the kernel's own bound is longer)
     unsigned arm_linger_ticks = 30000u;         // 300 us of the 100 MHz clock: after that a waiting launch leaves by itself (a device-wide
                                                 // synchronisation from outside this library waits that long at most)
     unsigned long long arm_stats[4] = {0, 0, 0, 0};   // armed, fired, cancelled, expired
-    bool ring_void[512] = {};
-    bool ring_marker[512] = {};                 // light profiling with a period: an entry that only serves as the NEXT launch's start (not timed itself)
-    int prof_period = 1;                        // srl_set_profiling_period: the light profiling times every prof_period-th association launch
-    unsigned long long prof_count = 0;          // association launches seen by the light profiling (own and armed)
-    long long ring_last_count = -2;             // prof_count of the launch behind the newest ring entry
-    bool armed_measured = false, cur_measured = true;     // is the armed launch / the launch of the pass now running one of the timed ones?
-    // srl_timing_mark: "the sums start here" without a read-back -- launches enqueued before the mark carry an older generation and are
-    // left out when their events are read (their passes' bytes likewise)
-    unsigned timing_gen = 0, armed_gen = 0, cur_gen = 0;
-    unsigned ring_gen[512] = {};
-    int ring_prev[512] = {};                    // light profiling: ring slot whose END event is this launch's start (armed launches), -1 = own start event
+    SrlProfRing prof;
+    bool cur_measured = true;                   // light profiling: is the launch of the pass now running one of the timed ones ...
+    unsigned cur_gen = 0;                       // ... and of which srl_timing_mark generation (an armed launch's: SrlArmedLaunch::measured, gen)
     long long *h_arm_stamps = nullptr;          // srl_debug_pass_stamps: 64 rows x 16 slots the armed kernels file (host-mapped)
-    long long arm_host_stamps[64][4] = {};      // per pass (row seq & 63), steady-clock ns: call entry, pose written / launch returned, result seen, fired?                   // light profiling: event pairs of cancelled armed launches (not counted)
+    long long arm_host_stamps[64][4] = {};      // per pass (row seq & 63), steady-clock ns: call entry, pose written / launch returned, result seen, fired?
 
     // taps
     bool taps = false;
@@ -255,11 +298,7 @@ struct srl_ctx {
     std::vector<PoolBlock> pool_free;
 
     int last_nblocks = 0;
-    int profiling = 0;                 // 0 off, 1 full (4 events + sync per call), 2 light (assoc kernel only, read lazily)
-    static constexpr int PROF_RING = 512;       // (= sizeof ring_void)
-    hipEvent_t ring[PROF_RING][2] = {};
-    unsigned ring_head = 0, ring_tail = 0;   // [tail, head) recorded and not yet read
-
+    int profiling = 0;                 // 0 off, 1 full (4 events + sync per call), 2 light (assoc kernel only, read lazily: prof)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     srl_timing timing = {};
     int last_nb = 1;
@@ -289,7 +328,7 @@ struct srl_ctx {
 // cancel an armed launch, if any (every entry point that touches the stream or waits for it calls this first: an armed launch
 // that nobody fires would hold the stream until its bound)
 extern "C" int srl_ctx_disarm(srl_ctx *ctx);
-#define SRL_DISARM(ctx) do { if ((ctx)->armed) { int rcd__ = srl_ctx_disarm(ctx); if (rcd__) return rcd__; } } while (0)
+#define SRL_DISARM(ctx) do { if ((ctx)->armed.on) { int rcd__ = srl_ctx_disarm(ctx); if (rcd__) return rcd__; } } while (0)
 // frees the consensus workspace (srl_consensus.hip); srl_ctx_destroy calls it
 extern "C" void srl_consensus_release(srl_ctx *ctx);
 
@@ -363,6 +402,33 @@ int ensure(srl_ctx *ctx, T *&p, size_t count) {
     if (count == 0) count = 1;
     HIPCHK(ctx, hipMalloc((void **)&p, count * sizeof(T)));
     return SRL_OK;
+}
+// ensure() frees first and allocates after: whoever grows blocks that share a capacity word sets the word to 0 before the first ensure
+// and to the new value behind the last one -- a growth that fails half-way then leaves "nothing fits", never a null block that "fits".
+
+inline int SrlSweepSlot::reserve(srl_ctx *ctx, double *&block, int &cap, int points) {
+    if (points <= cap) return SRL_OK;
+    const int grown = points > 1024 ? points : 1024;
+    cap = 0;
+    const int rc = ensure(ctx, block, (size_t)grown * 3);
+    if (rc) return rc;
+    cap = grown;
+    return SRL_OK;
+}
+
+// A sweep is current from now on: its counts, the leading keypoints whose SoA planes are filled already (the others are transposed out of
+// cur.stage by the first pass that reads them), and whether its tail may still be in flight (srl_sweep_swap only; cur_slot and
+// cur_prefix_n say how far it has landed).  Everything a pass has learnt about the sweep before it is void: its taps, its neighbourhood
+// bounds (a stale bound_n would cull against another sweep's distances: wrong neighbours, silently) and the solve's pass count.
+// srl_sweep_upload, srl_sweep_swap and srl_frame_select_keypoints call it; the three reset the same words.
+inline void srl_sweep_becomes_current(srl_ctx *ctx, int n, int begin, int total, int soa_valid_n, bool tail_pending) {
+    ctx->cur.n = n; ctx->cur.begin = begin; ctx->cur.total = total;
+    ctx->sweep_loaded = true;
+    ctx->soa_valid_n = soa_valid_n;
+    ctx->tail_pending = tail_pending;
+    ctx->taps_valid = false;
+    ctx->bound_n = 0;
+    ctx->passes_in_solve = 0;
 }
 
 // The per-rank counts of the ordered cut.  Grow-only and never re-allocated for a size that fits: hipFree waits for the WHOLE

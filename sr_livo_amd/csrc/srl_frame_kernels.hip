@@ -893,18 +893,13 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
     int m = 0;
     if (n > 0) {
         // the selection becomes the resident sweep (SoA, gathered on the device): at most n keypoints
-        if (n > ctx->sweep_cap) {
-            if (ctx->d_raw) { HIPCHK(ctx, hipFree(ctx->d_raw)); ctx->d_raw = nullptr; }
-            const int cap = std::max(n, 1024);
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_raw, (size_t)cap * 3 * sizeof(double)));
-            ctx->sweep_cap = cap;
-        }
-        int rc = srl_ctx_ensure_work(ctx, n);
+        int rc = ctx->cur.reserve_soa(ctx, n);
         if (rc) return rc;
+        if ((rc = srl_ctx_ensure_work(ctx, n))) return rc;
         Xf X;
         fill_xf(X, q, t, R_il, t_il);
         // the keypoints' raw points become the resident sweep: gathered by the chain's last kernel, or behind the host's replay
-        double *sx = ctx->d_raw, *sy = ctx->d_raw + ctx->sweep_cap, *sz = ctx->d_raw + 2 * (size_t)ctx->sweep_cap;
+        double *sx = ctx->cur.x(), *sy = ctx->cur.y(), *sz = ctx->cur.z();
         GridChain C;
         C.gather_raw = ctx->d_frame_raw; C.gx = sx; C.gy = sy; C.gz = sz;
         rc = grid_chain_enqueue(ctx, C, n, [&](const GroupArgs &G) {
@@ -942,8 +937,7 @@ int srl_frame_select_keypoints(srl_ctx *ctx, const double q[4], const double t[3
         srl_stage_end(ctx, 3);
     }
     if (num_keypoints) *num_keypoints = m;
-    ctx->total_n = m; ctx->shard_begin = 0; ctx->n = m; ctx->sweep_loaded = true; ctx->taps_valid = false; ctx->bound_n = 0; ctx->tail_pending = false;
-    ctx->soa_valid_n = m; ctx->passes_in_solve = 0;
+    srl_sweep_becomes_current(ctx, m, 0, m, m, false);      // (gathered straight into the planes)
     if (n > 0) { const int rcm = srl_mark_frame_read(ctx); if (rcm) return rcm; }
     srl_stage_end(ctx, 4);
     if (trace) {

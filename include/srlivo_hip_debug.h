@@ -64,8 +64,11 @@ int srl_debug_set_fused_reduce(srl_ctx *ctx, int enable);
 /* Neighbourhood bounds (default on): every pass leaves, per keypoint, its world position and the exact squared distance of its K-th
  * nearest neighbour; the next pass over the same sweep and map does not visit voxels that lie further from the keypoint than
  * sqrt(tau) + |movement| -- the same neighbours (searchNeighbors, optimize.cpp:365-426, keeps the K nearest whatever else it looked at),
- * fewer candidates evaluated.  0 switches the culling off (A/B in the tests: every bit must agree). */
-int srl_debug_set_bound_culling(srl_ctx *ctx, int enable);
+ * fewer candidates evaluated.  Where a keypoint's bound holds, that squared radius is also an upper bound of the K-th smallest FP32
+ * prefilter distance, so the prefilter takes its survivor threshold from it and searches for none.
+ * mode 1 (default): both.  2: the voxel cull only, every threshold searched.  0: the bounds are not used at all.  (A/B in the tests:
+ * every bit must agree between the three.)  Other values: SRL_ERR_BAD_ARG. */
+int srl_debug_set_bound_culling(srl_ctx *ctx, int mode);
 /* Where the pose box of the armed launches lives.  kind 1: fine-grained DEVICE memory the host writes through the PCIe BAR (every
  * workgroup polls it locally; SRL_ERR_UNSUPPORTED when device memory is not CPU-visible on this system).  kind 0: page-locked host
  * memory -- workgroup 0 of the waiting kernel polls it across PCIe and republishes the pose into device memory for the other

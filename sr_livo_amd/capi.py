@@ -1144,9 +1144,10 @@ class Context:
     def set_fused_reduce(self, on):
         self._chk(self.lib.srl_debug_set_fused_reduce(self.h, 1 if on else 0), "srl_debug_set_fused_reduce")
 
-    def set_bound_culling(self, on):
-        """test hook: 0 = every pass visits every found voxel (no use of the previous pass's neighbourhood bounds)"""
-        self._chk(self.lib.srl_debug_set_bound_culling(self.h, 1 if on else 0), "srl_debug_set_bound_culling")
+    def set_bound_culling(self, mode):
+        """test hook: 0 = every pass visits every found voxel (no use of the previous pass's neighbourhood bounds); 1 (default) = the
+        bounds cull voxels and give the prefilter its threshold; 2 = they cull voxels only, the threshold is searched"""
+        self._chk(self.lib.srl_debug_set_bound_culling(self.h, int(mode)), "srl_debug_set_bound_culling")
 
     def set_search_select_mode(self, mode):
         self._chk(self.lib.srl_debug_set_search_select_mode(self.h, int(mode)), "srl_debug_set_search_select_mode")

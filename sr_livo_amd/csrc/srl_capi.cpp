@@ -1022,6 +1022,7 @@ static void prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_o
         a.bound_out = ctx->d_bound;
         a.bound_in = ctx->bound_mode != 0 ? ctx->d_bound : nullptr;
         a.bound_use = a.bound_in ? std::min(ctx->bound_n, n_eff) : 0;
+        a.bound_thr = ctx->bound_mode == 1 ? 1 : 0;
     }
     if (p.fused) {
         a.granules = ctx->d_granules;
@@ -1624,10 +1625,10 @@ int srl_debug_set_launch_shape(srl_ctx *ctx, int keypoints_per_wave, int waves_p
     ctx->force_wpb = waves_per_workgroup;
     return SRL_OK;
 }
-int srl_debug_set_bound_culling(srl_ctx *ctx, int enable) {
-    if (!ctx) return SRL_ERR_BAD_ARG;
+int srl_debug_set_bound_culling(srl_ctx *ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return SRL_ERR_BAD_ARG;
     SRL_DISARM(ctx);
-    ctx->bound_mode = enable ? 1 : 0;
+    ctx->bound_mode = mode;
     ctx->bound_n = 0;
     return SRL_OK;
 }

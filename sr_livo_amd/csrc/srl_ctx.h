@@ -144,7 +144,7 @@ struct srl_ctx {
     float *d_bound = nullptr;
     int bound_n = 0;
     int bound_sig[4] = {0, 0, 0, 0};      // K, voxel neighbourhood, occupancy threshold, (float) voxel size bits
-    int bound_mode = 1;                   // srl_debug_set_bound_culling: 0 = never use them
+    int bound_mode = 1;                   // srl_debug_set_bound_culling: 0 = never use them, 1 = voxel cull and prefilter threshold, 2 = voxel cull only
     bool tail_pending = false;            // the CURRENT sweep's tail may still be in flight: stream not yet ordered behind up_ev[cur_slot][1]
     int cur_slot = 0, cur_prefix_n = 0;   // ... its slot, and how many of its points are known to have landed
 

@@ -238,7 +238,10 @@ struct SrlAssocArgs {
     const float *bound_in;
     float *bound_out;
     int bound_use;
-    int pad_bound;
+    // 1: where a keypoint's bound holds, its squared radius is the FP32 prefilter's threshold as well -- no per-lane minimum, no search
+    // (thr_from_bound); 0: the bounds cull voxels only and every threshold is searched (srl_debug_set_bound_culling(ctx, 2)).  Part of
+    // the armed signature: a launch armed under one value is not fired under the other.
+    int bound_thr;
     // outputs
     double *rec;            // n x 8
     unsigned char *status;  // n

@@ -459,7 +459,8 @@ struct LdsSink {
 // Only the ~25 survivors of a conservative FP32 threshold are ever evaluated in FP64:
 //   pass 1  : coalesced 12-B loads (all rounds in flight), d2f = |p - fl32(q)|^2 in FP32 (FMA allowed: it
 //             is a filter, never a result), per-lane minimum
-//   tau_f   : bisection (ballot/popcount) -> upper bound of the K-th smallest per-lane minimum
+//   tau_f   : bisection (ballot/popcount) -> upper bound of the K-th smallest per-lane minimum; a pass that starts from bounds
+//             has one before it loads a candidate (thr_from_bound) and skips the minimum and the search
 //   margin  : |d2f - d2| <= M for every candidate with d2 <= 2 tau_f (M from the FP32 rounding model below),
 //             so the true K nearest all satisfy d2f <= tau_f + 2M: these survivors are compacted (visit
 //             order) into LDS as {x, y, z, voxel/slot code}
@@ -573,17 +574,47 @@ __device__ __forceinline__ void cand_issue(const VoxEnt *vox, const unsigned cha
     total_out = total;
 }
 
-// FP32 distances of one keypoint's rounds and their per-lane minimum
+// FP32 distances of one keypoint's rounds ...
 template <int R>
-__device__ __forceinline__ float cand_d2f(const float (&px)[R], const float (&py)[R], const float (&pz)[R], const float *qf, float (&d2f)[R]) {
+__device__ __forceinline__ void cand_d2f(const float (&px)[R], const float (&py)[R], const float (&pz)[R], const float *qf, float (&d2f)[R]) {
     const float qxf = qf[0], qyf = qf[1], qzf = qf[2];      // FP32 query, prepared in phase 0
+#pragma unroll
+    for (int j = 0; j < R; ++j) d2f[j] = d2_f32(px[j], py[j], pz[j], qxf, qyf, qzf);
+}
+// ... and their per-lane minimum: only a keypoint whose threshold is SEARCHED needs it (one without a bound, or with too many survivors under it)
+template <int R>
+__device__ __forceinline__ float cand_min(const float (&d2f)[R]) {
     float lmin = __builtin_huge_valf();
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-        d2f[j] = d2_f32(px[j], py[j], pz[j], qxf, qyf, qzf);
-        lmin = fminf(lmin, d2f[j]);
-    }
+    for (int j = 0; j < R; ++j) lmin = fminf(lmin, d2f[j]);
     return lmin;
+}
+// Threshold search: bisection on the bit pattern of the per-lane minima.  Every pattern in [2^-15, 2) m^2 starts 0111 in bits 30..27, so with
+// the minima clamped into that band nine steps (bits 26..18) do what thirteen did -- the same lo whenever the K-th smallest minimum lies
+// inside the band (a minimum below it only ever makes the bound looser, never wrong).  If the K-th smallest is not below 2 m^2 (lo ends on
+// the band's last pattern: sparse voxels, fewer than K candidates) the full search runs, rolled.
+constexpr unsigned SRL_BAND_LO = 0x38000000u, SRL_BAND_HI = 0x40000000u, SRL_BAND_LAST = 0x3FFC0000u;
+__device__ __forceinline__ unsigned band_clamp(unsigned v) { return v < SRL_BAND_LO ? SRL_BAND_LO : (v > SRL_BAND_HI ? SRL_BAND_HI : v); }
+// one keypoint (the single-keypoint paths; select_pair_f32_r runs two of these chains interleaved)
+__device__ __forceinline__ unsigned search_lo(unsigned v, int K) {
+    const unsigned cv = band_clamp(v);
+    unsigned lo = SRL_BAND_LO;
+#pragma unroll
+    for (int bit = 26; bit >= 18; --bit) {
+        const unsigned trial = lo | (1u << bit);
+        const int cnt = __popcll(__ballot(cv < trial));
+        lo = (cnt < K) ? trial : lo;
+    }
+    if (lo == SRL_BAND_LAST) {
+        lo = 0;
+#pragma nounroll
+        for (int bit = 30; bit >= 18; --bit) {
+            const unsigned trial = lo | (1u << bit);
+            const int cnt = __popcll(__ballot(v < trial));
+            lo = (cnt < K) ? trial : lo;
+        }
+    }
+    return lo;
 }
 // FP32 error model: a = abs error of fl32(q) per axis; per-axis difference error <= a + u*|d|; sum of
 // squares (3 terms, FMA or not) adds <= 4u relative.  For d2, d2f <= T:  |d2f - d2| <= m(T) with
@@ -596,6 +627,14 @@ __device__ __forceinline__ float thr_from_bisection(unsigned lo, const float *qf
     if (tau_f < __builtin_huge_valf()) thr = qf[3] + qf[4] * tau_f;      // (tau + 2 m(2 tau + 1e-6)) (1 + eps), linear in tau
     return thr;
 }
+// A pass that starts from bounds knows an upper bound of the K-th smallest d2f before it loads a candidate: the squared cull radius r^2 of
+// phase 0 (qf[5]) -- the previous pass's K neighbours are candidates again and each has d2f <= r^2 (r's slack dominates the FP32
+// error of d2f).  The margin formula holds for ANY such bound, so thr = c0 + c1 r^2 needs no minimum, no clamp and no search.
+// Wave-uniform: r2 = the keypoint's qf[5] through readfirstlane, +inf where the keypoint has no bound (or the mode searches: bound_thr = 0).
+__device__ __forceinline__ float bound_r2(const float *qf, bool from_bound) {
+    return from_bound ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(qf[5]))) : __builtin_huge_valf();
+}
+__device__ __forceinline__ float thr_from_bound(float r2, const float *qf) { return qf[3] + qf[4] * r2; }
 // survivors of all rounds, compacted in visit order into recs[0 ..)
 template <int R>
 __device__ __forceinline__ void cand_compact(const float (&px)[R], const float (&py)[R], const float (&pz)[R], const float (&d2f)[R], float thr,
@@ -618,24 +657,31 @@ __device__ __forceinline__ void cand_compact(const float (&px)[R], const float (
 template <int R, class Sink>
 __device__ __forceinline__ int cand_select(const float (&px)[R], const float (&py)[R], const float (&pz)[R], double qx, double qy, double qz,
                                            const float *qf, const VoxEnt *vox, int K, void *scratch, int lane, const LaneRole &role, Sink &sink,
-                                           int ablate) {
+                                           int ablate, bool from_bound) {
     float d2f[R];
-    const unsigned v = __float_as_uint(cand_d2f<R>(px, py, pz, qf, d2f));
-    unsigned lo = 0;
-#pragma unroll
-    for (int bit = 30; bit >= 18; --bit) {
-        const unsigned trial = lo | (1u << bit);
-        const int cnt = __popcll(__ballot(v < trial));
-        lo = (cnt < K) ? trial : lo;
-    }
-    const float thr = thr_from_bisection(lo, qf);
+    cand_d2f<R>(px, py, pz, qf, d2f);
     SurvRec *recs = reinterpret_cast<SurvRec *>(__builtin_assume_aligned(scratch, 16));            // [64], 16-B aligned
     unsigned long long svm[R];
     int c = 0;
+    float thr = 0.0f;
+    auto survivors = [&]() {
+        c = 0;
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-        svm[j] = __ballot(d2f[j] <= thr);
-        c += __popcll(svm[j]);
+        for (int j = 0; j < R; ++j) {
+            svm[j] = __ballot(d2f[j] <= thr);
+            c += __popcll(svm[j]);
+        }
+    };
+    const float r2 = bound_r2(qf, from_bound);
+    bool have = false;
+    if (r2 < __builtin_huge_valf()) {          // threshold from the bound; more survivors than the finish takes: searched after all
+        thr = thr_from_bound(r2, qf);
+        survivors();
+        have = c <= 64;
+    }
+    if (!have) {
+        thr = thr_from_bisection(search_lo(__float_as_uint(cand_min<R>(d2f)), K), qf);
+        survivors();
     }
     if (c > 64) return SEL_OVERFLOW;       // checked before anything is written: the stores below need no clamp
     cand_compact<R>(px, py, pz, d2f, thr, svm, role, recs);
@@ -646,11 +692,11 @@ __device__ __forceinline__ int cand_select(const float (&px)[R], const float (&p
 template <int R, class Sink>
 __device__ __forceinline__ int select_topk_f32_r(double qx, double qy, double qz, const float *qf, int nv, const VoxEnt *vox,
                                                   const unsigned char *slabs, unsigned inf_off, int K, void *scratch, int lane,
-                                                  const LaneRole &role, Sink &sink, int &total_out, int ablate) {
+                                                  const LaneRole &role, Sink &sink, int &total_out, int ablate, bool from_bound) {
     (void)nv;
     float px[R], py[R], pz[R];
     cand_issue<R>(vox, slabs, inf_off, role, px, py, pz, total_out);
-    return cand_select<R>(px, py, pz, qx, qy, qz, qf, vox, K, scratch, lane, role, sink, ablate);
+    return cand_select<R>(px, py, pz, qx, qy, qz, qf, vox, K, scratch, lane, role, sink, ablate, from_bound);
 }
 
 // FP64 finish of a keypoint PAIR with at most 32 survivors each (the usual case: ~25): half-wave h works on keypoint h --
@@ -715,49 +761,64 @@ __device__ __forceinline__ int finish_pair(const double *qa, const double *qb, i
 template <int R>
 __device__ __forceinline__ int select_pair_f32_r(const double *qa, const double *qb, const float *qfa, const float *qfb, const VoxEnt *vox,
                                                  const unsigned char *slabs, unsigned inf_off, int K, void *scratch, int lane,
-                                                 const LaneRole &role, LdsSink &sink_a, LdsSink &sink_b, int &total_a, int &total_b, int ablate) {
+                                                 const LaneRole &role, LdsSink &sink_a, LdsSink &sink_b, int &total_a, int &total_b, int ablate, bool from_bound) {
     float ax[R], ay[R], az[R], bx[R], by[R], bz[R];
     cand_issue<R>(vox, slabs, inf_off, role, ax, ay, az, total_a);
     cand_issue<R>(vox + 32, slabs, inf_off, role, bx, by, bz, total_b);
     float da[R], db[R];
-    const unsigned va = __float_as_uint(cand_d2f<R>(ax, ay, az, qfa, da));
-    const unsigned vb = __float_as_uint(cand_d2f<R>(bx, by, bz, qfb, db));
-    // Bisection on the bit pattern of the per-lane minima.  Every pattern in [2^-15, 2) m^2 starts 0111 in bits 30..27, so with
-    // the minima clamped into that band nine steps (bits 26..18) do what thirteen did -- the same lo whenever the K-th smallest
-    // minimum lies inside the band (a minimum below it only ever makes the bound looser, never wrong).  If the K-th smallest
-    // is not below 2 m^2 (lo ends on the band's last pattern: sparse voxels, fewer than K candidates) the full search runs.
-    constexpr unsigned BAND_LO = 0x38000000u, BAND_HI = 0x40000000u, BAND_LAST = 0x3FFC0000u;
-    const unsigned ca_v = va < BAND_LO ? BAND_LO : (va > BAND_HI ? BAND_HI : va);
-    const unsigned cb_v = vb < BAND_LO ? BAND_LO : (vb > BAND_HI ? BAND_HI : vb);
-    unsigned lo_a = BAND_LO, lo_b = BAND_LO;
+    cand_d2f<R>(ax, ay, az, qfa, da);
+    cand_d2f<R>(bx, by, bz, qfb, db);
+    unsigned long long sa[R], sb[R];
+    int ca = 0, cb = 0;
+    float thr_a = -1.0f, thr_b = -1.0f;                     // (negative: no survivors -- every d2f is >= 0 or +inf)
+    auto survivors = [&]() {
+        ca = 0; cb = 0;
 #pragma unroll
-    for (int bit = 26; bit >= 18; --bit) {
-        const unsigned ta = lo_a | (1u << bit), tb = lo_b | (1u << bit);
-        const int cnt_a = __popcll(__ballot(ca_v < ta));
-        const int cnt_b = __popcll(__ballot(cb_v < tb));
-        lo_a = (cnt_a < K) ? ta : lo_a;
-        lo_b = (cnt_b < K) ? tb : lo_b;
+        for (int j = 0; j < R; ++j) {
+            sa[j] = __ballot(da[j] <= thr_a);
+            sb[j] = __ballot(db[j] <= thr_b);
+            ca += __popcll(sa[j]);
+            cb += __popcll(sb[j]);
+        }
+    };
+    // Threshold from the bound (thr_from_bound): a keypoint with a bound and at most 32 survivors under it keeps that threshold; when both
+    // do, nothing is searched.  Otherwise the search below runs as it always did -- for the pair: its two chains share one instruction
+    // stream, so the partner's costs nothing -- and a keypoint that kept its threshold ignores the result.
+    const float r2a = bound_r2(qfa, from_bound), r2b = bound_r2(qfb, from_bound);
+    bool keep_a = r2a < __builtin_huge_valf(), keep_b = r2b < __builtin_huge_valf();
+    if (keep_a || keep_b) {
+        if (keep_a) thr_a = thr_from_bound(r2a, qfa);
+        if (keep_b) thr_b = thr_from_bound(r2b, qfb);
+        survivors();
+        keep_a = keep_a && ca <= 32;
+        keep_b = keep_b && cb <= 32;
     }
-    if (lo_a == BAND_LAST || lo_b == BAND_LAST) {            // rare: the original 13 steps, rolled
-        lo_a = 0; lo_b = 0;
-#pragma nounroll
-        for (int bit = 30; bit >= 18; --bit) {
+    if (!(keep_a && keep_b)) {
+        const unsigned va = __float_as_uint(cand_min<R>(da)), vb = __float_as_uint(cand_min<R>(db));
+        const unsigned ca_v = band_clamp(va), cb_v = band_clamp(vb);
+        unsigned lo_a = SRL_BAND_LO, lo_b = SRL_BAND_LO;    // search_lo, two independent dependency chains
+#pragma unroll
+        for (int bit = 26; bit >= 18; --bit) {
             const unsigned ta = lo_a | (1u << bit), tb = lo_b | (1u << bit);
-            const int cnt_a = __popcll(__ballot(va < ta));
-            const int cnt_b = __popcll(__ballot(vb < tb));
+            const int cnt_a = __popcll(__ballot(ca_v < ta));
+            const int cnt_b = __popcll(__ballot(cb_v < tb));
             lo_a = (cnt_a < K) ? ta : lo_a;
             lo_b = (cnt_b < K) ? tb : lo_b;
         }
-    }
-    const float thr_a = thr_from_bisection(lo_a, qfa), thr_b = thr_from_bisection(lo_b, qfb);
-    unsigned long long sa[R], sb[R];
-    int ca = 0, cb = 0;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        sa[j] = __ballot(da[j] <= thr_a);
-        sb[j] = __ballot(db[j] <= thr_b);
-        ca += __popcll(sa[j]);
-        cb += __popcll(sb[j]);
+        if (lo_a == SRL_BAND_LAST || lo_b == SRL_BAND_LAST) {            // rare: the original 13 steps, rolled
+            lo_a = 0; lo_b = 0;
+#pragma nounroll
+            for (int bit = 30; bit >= 18; --bit) {
+                const unsigned ta = lo_a | (1u << bit), tb = lo_b | (1u << bit);
+                const int cnt_a = __popcll(__ballot(va < ta));
+                const int cnt_b = __popcll(__ballot(vb < tb));
+                lo_a = (cnt_a < K) ? ta : lo_a;
+                lo_b = (cnt_b < K) ? tb : lo_b;
+            }
+        }
+        if (!keep_a) thr_a = thr_from_bisection(lo_a, qfa);
+        if (!keep_b) thr_b = thr_from_bisection(lo_b, qfb);
+        survivors();
     }
     SurvRec *recs = reinterpret_cast<SurvRec *>(__builtin_assume_aligned(scratch, 16));
     if (ca <= 32 && cb <= 32 && K <= 31 && !(ablate & (2 | 512))) {
@@ -782,34 +843,32 @@ __device__ __forceinline__ int select_pair_f32_r(const double *qa, const double 
 template <class Sink>
 __device__ __forceinline__ int select_topk_f32(double qx, double qy, double qz, const float *qf, int nv, const VoxEnt *vox,
                                                 const unsigned char *slabs, unsigned inf_off, int K, void *scratch, int lane,
-                                                const LaneRole &role, Sink &sink, int &total_out, int ablate) {
+                                                const LaneRole &role, Sink &sink, int &total_out, int ablate, bool from_bound) {
     // straight-line instantiation per number of candidate rounds (3 voxels per round)
     switch ((nv + 2) / 3) {
         case 0: case 1: case 2: case 3:
-            return select_topk_f32_r<3>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate);
-        case 4: return select_topk_f32_r<4>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate);
-        case 5: return select_topk_f32_r<5>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate);
-        case 6: return select_topk_f32_r<6>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate);
-        case 7: return select_topk_f32_r<7>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate);
-        default: return select_topk_f32_r<9>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate);
+            return select_topk_f32_r<3>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate, from_bound);
+        case 4: return select_topk_f32_r<4>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate, from_bound);
+        case 5: return select_topk_f32_r<5>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate, from_bound);
+        case 6: return select_topk_f32_r<6>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate, from_bound);
+        case 7: return select_topk_f32_r<7>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate, from_bound);
+        default: return select_topk_f32_r<9>(qx, qy, qz, qf, nv, vox, slabs, inf_off, K, scratch, lane, role, sink, total_out, ablate, from_bound);
     }
 }
 
 // r = 2 (init mode, 125 voxels): the same FP32 prefilter + FP64 finish with the candidate rounds in a loop.  Up to 42
-// rounds do not fit in registers, so the FP32 distances are evaluated twice (threshold pass, survivor pass); the second
-// pass hits L1/L2.  The voxel list is the visit-order list of probe_voxels<2>, zero-filled to a multiple of 3 entries.
+// rounds do not fit in registers, so a keypoint whose threshold is searched evaluates the FP32 distances twice (threshold pass,
+// survivor pass; the second pass hits L1/L2).  The voxel list is the visit-order list of probe_voxels<2>, zero-filled to a multiple of 3 entries.
 template <class Sink>
 __device__ __forceinline__ int select_topk_f32_loop(double qx, double qy, double qz, const float *qf, int nv, const VoxEnt *vox,
                                                     const unsigned char *slabs, unsigned inf_off, int K, void *scratch, int lane,
-                                                    const LaneRole &role, Sink &sink, int &total_out) {
+                                                    const LaneRole &role, Sink &sink, int &total_out, bool from_bound) {
     const float kInfF = __builtin_huge_valf();
     const float qxf = qf[0], qyf = qf[1], qzf = qf[2];
     const int rounds = (nv + 2) / 3;
     const int cbase = role.c0 < 3 ? role.c0 : 0;
     const unsigned slot_eff = role.c0 < 3 ? (unsigned)role.slot : 31u;
     const unsigned slot_off = (unsigned)role.slot * 12u;
-    float lmin = kInfF;
-    int total = 0;
     constexpr int CH = 4;                 // rounds per chunk: their loads are all in flight before the first use
     // byte offset of this lane's candidate in round j (the all-inf slab when it has none, or when j is past the list)
     auto cand_off = [&](int j, bool &has) {
@@ -818,49 +877,58 @@ __device__ __forceinline__ int select_topk_f32_loop(double qx, double qy, double
         has = (j < rounds) && (slot_eff < ve.count);
         return has ? ve.slab * (unsigned)SRL_SLAB_BYTES + slot_off : inf_off;
     };
-    for (int j0 = 0; j0 < rounds; j0 += CH) {
-        unsigned off[CH];
+    total_out = 0;                        // (the caller's P_k comes from probe_voxels<2>: every found voxel, visited or not)
+    // threshold pass: per-lane minimum over all rounds, then the search
+    auto threshold_pass = [&]() -> float {
+        float lmin = kInfF;
+        int total = 0;
+        for (int j0 = 0; j0 < rounds; j0 += CH) {
+            unsigned off[CH];
 #pragma unroll
-        for (int u = 0; u < CH; ++u) { bool h; off[u] = cand_off(j0 + u, h); total += __popcll(__ballot(h)); }
-        float x[CH], y[CH], z[CH];
+            for (int u = 0; u < CH; ++u) { bool h; off[u] = cand_off(j0 + u, h); total += __popcll(__ballot(h)); }
+            float x[CH], y[CH], z[CH];
 #pragma unroll
-        for (int u = 0; u < CH; ++u) { const float *p = reinterpret_cast<const float *>(slabs + off[u]); x[u] = p[0]; y[u] = p[1]; z[u] = p[2]; }
+            for (int u = 0; u < CH; ++u) { const float *p = reinterpret_cast<const float *>(slabs + off[u]); x[u] = p[0]; y[u] = p[1]; z[u] = p[2]; }
 #pragma unroll
-        for (int u = 0; u < CH; ++u) lmin = fminf(lmin, d2_f32(x[u], y[u], z[u], qxf, qyf, qzf));
-    }
-    total_out = total;
-    const unsigned v = __float_as_uint(lmin);
-    unsigned lo = 0;
-#pragma unroll
-    for (int bit = 30; bit >= 18; --bit) {
-        const unsigned trial = lo | (1u << bit);
-        const int cnt = __popcll(__ballot(v < trial));
-        lo = (cnt < K) ? trial : lo;
-    }
-    const float tau_f = __uint_as_float(lo | 0x3FFFFu);
-    float thr = 3.4028235e38f;
-    if (tau_f < kInfF) thr = qf[3] + qf[4] * tau_f;      // same margin as select_topk_f32_r
-
+            for (int u = 0; u < CH; ++u) lmin = fminf(lmin, d2_f32(x[u], y[u], z[u], qxf, qyf, qzf));
+        }
+        total_out = total;
+        return thr_from_bisection(search_lo(__float_as_uint(lmin), K), qf);      // same margin as select_topk_f32_r
+    };
     SurvRec *recs = reinterpret_cast<SurvRec *>(__builtin_assume_aligned(scratch, 16));
     const int code0 = (role.c0 << 5) | role.slot;
-    int c = 0;
-    for (int j0 = 0; j0 < rounds; j0 += CH) {
-        unsigned off[CH];
+    // survivor pass: the survivors of thr in visit order into recs[0 .. 64); returns how many there are (may exceed 64)
+    auto survivor_pass = [&](float thr) -> int {
+        int c = 0;
+        for (int j0 = 0; j0 < rounds; j0 += CH) {
+            unsigned off[CH];
 #pragma unroll
-        for (int u = 0; u < CH; ++u) { bool h; off[u] = cand_off(j0 + u, h); }
-        float x[CH], y[CH], z[CH];
+            for (int u = 0; u < CH; ++u) { bool h; off[u] = cand_off(j0 + u, h); }
+            float x[CH], y[CH], z[CH];
 #pragma unroll
-        for (int u = 0; u < CH; ++u) { const float *p = reinterpret_cast<const float *>(slabs + off[u]); x[u] = p[0]; y[u] = p[1]; z[u] = p[2]; }
+            for (int u = 0; u < CH; ++u) { const float *p = reinterpret_cast<const float *>(slabs + off[u]); x[u] = p[0]; y[u] = p[1]; z[u] = p[2]; }
 #pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const bool sv = d2_f32(x[u], y[u], z[u], qxf, qyf, qzf) <= thr;
-            const unsigned long long m = __ballot(sv);
-            if (m != 0ull) {
-                const int pos = c + lanes_below(m);
-                if (sv && pos < 64) { SurvRec r; r.x = x[u]; r.y = y[u]; r.z = z[u]; r.code = code0 + ((3 * (j0 + u)) << 5); recs[pos] = r; }
-                c += __popcll(m);
+            for (int u = 0; u < CH; ++u) {
+                const bool sv = d2_f32(x[u], y[u], z[u], qxf, qyf, qzf) <= thr;
+                const unsigned long long m = __ballot(sv);
+                if (m != 0ull) {
+                    const int pos = c + lanes_below(m);
+                    if (sv && pos < 64) { SurvRec r; r.x = x[u]; r.y = y[u]; r.z = z[u]; r.code = code0 + ((3 * (j0 + u)) << 5); recs[pos] = r; }
+                    c += __popcll(m);
+                }
             }
         }
+        return c;
+    };
+    // With a bound the threshold is known up front (thr_from_bound): the survivor pass alone.  More than 64 survivors under it: the two
+    // passes as without a bound.
+    const float r2 = bound_r2(qf, from_bound);
+    bool bounded = r2 < kInfF;
+    int c;
+    for (;;) {
+        c = survivor_pass(bounded ? thr_from_bound(r2, qf) : threshold_pass());
+        if (c <= 64 || !bounded) break;
+        bounded = false;
     }
     if (c > 64) return SEL_OVERFLOW;
     return finish_survivors(qx, qy, qz, c, vox, K, scratch, lane, sink, reinterpret_cast<double *>(const_cast<float *>(qf) + 6));
@@ -1305,6 +1373,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
     // the context's other sweep buffer or for another keypoint count (srl_sweep_swap) -- the host vouches for everything else
     bool use_bounds = A.bound_in != nullptr && A.bound_use > 0;
     if constexpr (ARMED) use_bounds = use_bounds && reinterpret_cast<const int *>(s_pose + SRL_POSE_DOUBLES)[2] == 0 && n_pass() == A.n;
+    const bool thr_bound = use_bounds && A.bound_thr != 0;               // ... and their r^2 serves as the prefilter's threshold too (else: searched)
     const int bbase_kp = tile * KPB;                                      // first keypoint of this tile
     const int wbase_kp = bbase_kp + wave * KPW;                           // first keypoint of this wave's quarter (phases 0 and 2)
 
@@ -1465,9 +1534,9 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
                     LdsSink sink_a = make_sink(kl), sink_b = make_sink(kl + 1);
                     int total_a = 0, total_b = 0, done;
                     // (two rounds: what a pass that starts from the previous pass's bounds typically has left -- ~6 of ~12 occupied voxels)
-                    if (r_max <= 2) done = select_pair_f32_r<2>(s_pw + kl * 3, s_pw + kl * 3 + 3, s_qf + kl * 8, s_qf + kl * 8 + 8, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink_a, sink_b, total_a, total_b, abl);
-                    else if (r_max <= 3) done = select_pair_f32_r<3>(s_pw + kl * 3, s_pw + kl * 3 + 3, s_qf + kl * 8, s_qf + kl * 8 + 8, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink_a, sink_b, total_a, total_b, abl);
-                    else done = select_pair_f32_r<4>(s_pw + kl * 3, s_pw + kl * 3 + 3, s_qf + kl * 8, s_qf + kl * 8 + 8, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink_a, sink_b, total_a, total_b, abl);
+                    if (r_max <= 2) done = select_pair_f32_r<2>(s_pw + kl * 3, s_pw + kl * 3 + 3, s_qf + kl * 8, s_qf + kl * 8 + 8, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink_a, sink_b, total_a, total_b, abl, thr_bound);
+                    else if (r_max <= 3) done = select_pair_f32_r<3>(s_pw + kl * 3, s_pw + kl * 3 + 3, s_qf + kl * 8, s_qf + kl * 8 + 8, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink_a, sink_b, total_a, total_b, abl, thr_bound);
+                    else done = select_pair_f32_r<4>(s_pw + kl * 3, s_pw + kl * 3 + 3, s_qf + kl * 8, s_qf + kl * 8 + 8, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink_a, sink_b, total_a, total_b, abl, thr_bound);
                     // (candidate totals: accumulated by probe_finish; neighbour counts: derived from them in phase 2 -- a pair that
                     // finished on the fast path files nothing)
                     (void)total_a; (void)total_b;
@@ -1487,7 +1556,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
                         LdsSink sink = make_sink(kl);
                         int total = nv_fast;
                         int done = SEL_DONE;
-                        if (!(abl & 4)) done = select_topk_f32(qx, qy, qz, s_qf + kl * 8, nv_fast, vox + 32 * h, A.slabs, A.inf_off, Kn, surv, lane, role, sink, total, abl);
+                        if (!(abl & 4)) done = select_topk_f32(qx, qy, qz, s_qf + kl * 8, nv_fast, vox + 32 * h, A.slabs, A.inf_off, Kn, surv, lane, role, sink, total, abl, thr_bound);
                         if (lane == 0) file(kl, done, total);
                     }
                 }
@@ -1505,7 +1574,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
                 __builtin_amdgcn_wave_barrier();
                 LdsSink sink = make_sink(kl);
                 int total = 0;
-                const int done = select_topk_f32_loop(qx, qy, qz, s_qf + kl * 8, nv, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink, total);
+                const int done = select_topk_f32_loop(qx, qy, qz, s_qf + kl * 8, nv, vox, A.slabs, A.inf_off, Kn, surv, lane, role, sink, total, thr_bound);
                 total = total_all;           // P_k: every found voxel counts, also those the bounds let this pass skip
                 if (lane == 0) {
                     if (done == SEL_DONE) {

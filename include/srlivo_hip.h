@@ -111,7 +111,8 @@ int srl_map_insert(srl_ctx *ctx, const double *world_xyz, int n, double voxel_si
  * launch, folds a deferred insert in first and voids the neighbourhood bounds.  Always synchronous: it waits for the device once (the
  * record count) and then moves num_cloud records in one DMA.  NULL ctx or NULL points with n > 0: SRL_ERR_BAD_ARG with both counts
  * written as 0, before any device is touched; cap != 20: SRL_ERR_UNSUPPORTED; n == 0: SRL_OK, counts 0.  With a communicator the call
- * acts on this rank's map as srl_map_insert does (the map is replicated: every rank inserts the same batch); not tested on several ranks. */
+ * acts on this rank's map as srl_map_insert does (the map is replicated: every rank inserts the same batch); tests/test_gpu_sharded_stream.py takes three ranks through insertions, a
+ * prune and passes in between and holds outcome, cloud, counts, map and checksum bytewise equal on every rank and to an unsharded context. */
 typedef struct srl_cloud_point { float x, y, z, intensity; } srl_cloud_point;   /* the payload of pcl::PointXYZI */
 #define SRL_MAP_INSERT_REPORT_MAX_POINTS 2147483647      /* no limit of its own: INT_MAX, as srl_map_insert */
 int srl_map_insert_report(srl_ctx *ctx, const double *world_xyz, int n, double voxel_size, int cap,
@@ -822,7 +823,16 @@ int srl_transform_points(srl_ctx *ctx, const double *raw_xyz, int n, const doubl
                          const double R_il[9], const double t_il[3], double *out_xyz);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL over xGMI)
- * one context per process/GPU; the only exchange step is the all-reduce of the normal equations. */
+ * one context per process/GPU; the only exchange step is the all-reduce of the normal equations.
+ *
+ * SHARD LAYOUT.  A sweep is cut when it becomes current: srl_sweep_upload and srl_sweep_prefetch keep the range
+ * srl_shard_range(n, nranks, rank) of the layout in force at that call.  Every call that changes (nranks, rank) -- srl_comm_init_rank,
+ * srl_comm_destroy, srl_comm_suspend, srl_comm_set_host_callbacks, srl_peer_attach, srl_peer_detach, srl_debug_set_gather_counts --
+ * leaves the current and the prefetched sweep cut under the OLD layout: upload the sweep again afterwards.  srl_build_residuals checks
+ * it on the host (one comparison per pass): when the current sweep's range is not the one this rank owns under the present layout it
+ * returns SRL_ERR_NO_SWEEP with a zeroed record and an srl_last_error that names both ranges, before anything is launched or exchanged;
+ * a sweep prefetched under the old layout is refused the same way once srl_sweep_swap has made it current.  A change that leaves this
+ * rank's range as it was (one rank before and after) needs no upload. */
 #define SRL_COMM_ID_BYTES 128
 int srl_comm_unique_id(void *id /* SRL_COMM_ID_BYTES */);
 /* debug / test hook: take the nccl* entry points of this process from the given shared object instead of the process's RCCL.  Only
@@ -844,10 +854,11 @@ int srl_comm_backend_info(char *origin, int origin_len, int *version, int *prelo
  * passes_armed = armed launches fired on this context so far (0 on a path that never arms).  Any pointer may be NULL. */
 int srl_comm_info(srl_ctx *ctx, int *transport, int *nranks, int *rank, int *ranks_seen, int64_t *passes_armed);
 /* suspend != 0: run unsharded (whole sweep, no collective) while keeping the communicator; 0: back to sharded mode.
- * Re-upload the sweep after switching. */
+ * Changes the shard layout: upload the sweep again after switching (SHARD LAYOUT above; a pass over the old range is refused). */
 int srl_comm_suspend(srl_ctx *ctx, int suspend);
 /* test hook: a host all-reduce callback (sum over ranks of `count` doubles, in place) used INSTEAD of
- * RCCL when set -- lets the sharded logic run over gloo/MPI or G logical shards on one device. */
+ * RCCL when set -- lets the sharded logic run over gloo/MPI or G logical shards on one device.  Sets the shard layout
+ * (nranks, rank): upload the sweep afterwards (SHARD LAYOUT above). */
 typedef int (*srl_allreduce_fn)(double *buf, int count, void *user);
 typedef int (*srl_allgather_i64_fn)(const int64_t *mine, int64_t *all /* nranks */, void *user);
 int srl_comm_set_host_callbacks(srl_ctx *ctx, int nranks, int rank, srl_allreduce_fn ar,
@@ -866,7 +877,7 @@ int srl_comm_set_host_callbacks(srl_ctx *ctx, int nranks, int rank, srl_allreduc
  *   srl_peer_attach : ipc_handles = nranks x SRL_PEER_HANDLE_BYTES gathered from all ranks (how they travel is the caller's
  *                     business: torch.distributed.all_gather_object, MPI, a file) and / or local_ptrs[nranks] for same-process
  *                     peers (NULL entries fall back to the handle).  Sets the shard layout like srl_comm_init_rank: upload the
- *                     sweep afterwards.  nranks <= 8.  Mutually exclusive with srl_comm_init_rank / host callbacks.
+ *                     sweep afterwards (SHARD LAYOUT above).  nranks <= 8.  Mutually exclusive with srl_comm_init_rank / host callbacks.
  *   srl_peer_detach : back to an unsharded context (unmaps the peers' inboxes).
  * All ranks must call srl_build_residuals the same number of times with the same options (as with any collective).
  *

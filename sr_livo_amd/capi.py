@@ -18,6 +18,7 @@ SRL_ERR_NO_DEVICE = -1
 SRL_ERR_BAD_ARG = -3
 SRL_ERR_UNSUPPORTED = -4
 SRL_ERR_NO_MAP = -5
+SRL_ERR_NO_SWEEP = -6
 SRL_ERR_COMM = -7
 SRL_ERR_NAN_PLANARITY = -8
 SRL_ERR_NOT_ENOUGH_RESIDUALS = -9

@@ -1718,6 +1718,23 @@ int srl_build_residuals(srl_ctx *ctx, const srl_frame *f, const srl_icp_opts *o,
     if (!ctx || !f || !o || !out) return SRL_ERR_BAD_ARG;
     if (!ctx->d_table) return SRL_ERR_NO_MAP;
     if (!ctx->sweep_loaded) return SRL_ERR_NO_SWEEP;
+    {
+        // The current sweep was cut under the layout of the call that made it current.  A call that has changed nranks / rank since
+        // (include/srlivo_hip.h, SHARD LAYOUT) leaves a range no other rank agrees with: refused here, on the host, before anything is
+        // launched or exchanged.  A layout change that gives this rank the same range (1 rank -> 1 rank) passes.
+        int b = 0, cnt = 0;
+        srl_shard_range(ctx->cur.total, ctx->nranks, ctx->rank, &b, &cnt);
+        if (b != ctx->cur.begin || cnt != ctx->cur.n) {
+            char buf[320];
+            std::snprintf(buf, sizeof buf, "srl_build_residuals: the shard layout changed after the sweep was uploaded: the sweep holds keypoints [%d, %d) of %d, "
+                          "rank %d of %d owns [%d, %d) -- upload the sweep again after a layout change", ctx->cur.begin, ctx->cur.begin + ctx->cur.n,
+                          ctx->cur.total, ctx->rank, ctx->nranks, b, b + cnt);
+            ctx->err = buf;
+            std::memset(out, 0, sizeof *out);
+            ctx->taps_valid = false;
+            return SRL_ERR_NO_SWEEP;
+        }
+    }
     if (ctx->cur.total == 0) {
         // an empty keypoint set is a valid pass: the loop of optimize.cpp:68 does not run, num_residuals = 0 fails the
         // test at :110 and the caller gets summary.success = false (no exception, nothing visited)

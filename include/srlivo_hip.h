@@ -225,7 +225,7 @@ int srl_color_registered_download(srl_ctx *ctx, int64_t first, int count, srl_co
  * vioPhotometric are srl_color_map_vio_rows, the optical flow is srl_flow_track_image, the inlier sets the reference takes from findFundamentalMat and
  * solvePnPRansac have a stand-in of this library's own (srl_consensus_*, not OpenCV's results), and so have the undistortion and the
  * equalisation of the image (srl_image_prepare: this library's specified operations, not OpenCV's bytes); the rest of the vision stage
- * (cv::resize at a ratio other than 1, the publishers) stays with the caller.
+ * (the publishers) stays with the caller; cv::resize at a ratio other than 1 is srl_image_prepare_resized.
  *
  * Per point, FP64 unless noted, no contraction, sums of three as (a0 + a1) + a2:
  *   p = (double) stored FP32 position; pc = R_cw p + t_cw with q_cw = q_world_camera.inverse(), R_cw = q_cw.toRotationMatrix(),
@@ -552,7 +552,7 @@ int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, co
  * CV_16SC2 map layout with 5 fractional bits, the 15-bit fixed-point bilinear weights, the 15-bit gray and 14-bit YCrCb coefficients,
  * CLAHE's clip / redistribute / bilinear-LUT structure and the reference's tile rule.  The one deliberate difference: the map is the
  * explicit formula below on (j - cx) / fx (OpenCV iterates an inverse camera matrix along the row); DESIGN.md section 4.5 lists the rest.
- * cv::resize stays with the caller (image_resize_ratio is 1.0 in the reference, :11).
+ * cv::resize (:113-118; image_resize_ratio is 1.0 in the reference, :11) is stage (r) below, run by srl_image_prepare_resized alone.
  * Notation: DESCALE(x, n) = (x + (1 << (n - 1))) >> n with an arithmetic shift; sat8 clamps to 0 ... 255; rne = round half to even.
  * (a) map, built once per preparer on the HOST in FP64, no contraction (srl_image_prep_build_map: pure, no device).  For destination
  *     pixel (column j, row i): x = (j - cx) / fx, y = (i - cy) / fy, r2 = x x + y y, kr = 1 + ((k3 r2 + k2) r2 + k1) r2,
@@ -579,6 +579,19 @@ int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, co
  *     txf = (float)x (1.0f / (float)tw) - 0.5f, tx1 = floor(txf), xa = txf - (float)tx1, xa1 = 1.0f - xa, tx2 = tx1 + 1, then tx1 clamped
  *     up to 0 and tx2 down to T - 1; the same in y;
  *     out = sat8(rne((lut[ty1][tx1][v] xa1 + lut[ty1][tx2][v] xa) ya1 + (lut[ty2][tx1][v] xa1 + lut[ty2][tx2][v] xa) ya)).
+ * (r) resize of an 8 bit x 3 channel frame of src_rows x src_cols to the preparer's rows x cols, in front of (b).  Again this library's
+ *     operation: it follows OpenCV's conventions for INTER_LINEAR (11-bit coefficients, the two-pass fixed-point rule) and claims no
+ *     equality with its bytes.  Tables, built on the HOST, no contraction (srl_image_resize_build_tables: pure, no device), once for
+ *     the columns (src_cols -> cols) and once for the rows (src_rows -> rows).  For each destination index d:
+ *     scale = (double)src_len / dst_len; f = (float)((d + 0.5) scale - 0.5); s = floor(f); f = f - (float)s, a float subtraction;
+ *     if s < 0 then s = 0 and f = 0; if s >= src_len - 1 then s = src_len - 1 and f = 0; ofs[d] = s;
+ *     coef[2 d] = rne((1.0f - f) 2048.0f), coef[2 d + 1] = rne(f 2048.0f) as int16.
+ *     Pixel rule, per channel, with s1 = min(s + 1, src_len - 1) in either direction, column coefficients a0, a1 and row coefficients
+ *     b0, b1: h = S[row][ofs_x] a0 + S[row][s1_x] a1 in int32 for the two rows ofs_y (h0) and s1_y (h1);
+ *     out = min(255, ((((b0 (h0 >> 4)) >> 16) + ((b1 (h1 >> 4)) >> 16) + 2) >> 2)).  Every operand is non-negative; the largest
+ *     intermediate, 2048 x 32640, fits int32.
+ *     Exact half (OpenCV's INTER_AREA substitution): when src_cols == 2 cols and src_rows == 2 rows the result is the 2 x 2 box mean
+ *     instead, (s00 + s01 + s10 + s11 + 2) >> 2.
  * The chain: undist = remap(raw); gray_eq = CLAHE(gray(undist), 3.0); bgr_eq = YCrCb->BGR(CLAHE(Y, 1.0), Cr, Cb) of undist.  Integer
  * arithmetic and uncontracted IEEE FP32: the same input gives the same bytes, call after call.
  *
@@ -587,6 +600,13 @@ int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, co
  * is allocated on the first image) and info->installed_color = 1.  Synchronous.  srl_image_prep_download: which = 0 gray_eq (rows x cols),
  * 1 bgr_eq (rows x cols x 3).  srl_flow_track_prepared is srl_flow_track_image with the prepared gray_eq as its image and no host round
  * trip (first image of a tracker: next = prev, *n_tracked = 0, as there).
+ * srl_image_prepare_resized is srl_image_prepare for a frame of any size: the frame is uploaded once at its own size, resized on the
+ * device by (r) into the place of the preparer's upload, and the chain runs on that.  With src_rows == rows and src_cols == cols no
+ * resize runs and every stage is bytewise srl_image_prepare's.  The tables live on the device, built at the first use of a source size
+ * and rebuilt when it changes; the source's staging and device block come with the first resized frame and only grow.  Refused with
+ * SRL_ERR_BAD_ARG: a NULL image, src_rows or src_cols < 1 or > SRL_FLOW_MAX_EXTENT, src_rows * src_cols > SRL_COLOR_IMAGE_MAX_PIXELS,
+ * row_stride_bytes < 3 src_cols; everything else as srl_image_prepare, the prepared images staying as they were.
+ * srl_image_resize_build_tables refuses src_len < 1, dst_len < 1 and NULL arrays (SRL_ERR_BAD_ARG, the arrays left alone).
  * Before a device is touched -- SRL_ERR_BAD_ARG: NULL arguments (info may be NULL); rows or cols outside 16 ... SRL_FLOW_MAX_EXTENT;
  * rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS; rows <= T or cols <= T (the reflection would leave the image); tiles given and below 2 or
  * above min(rows, cols) / 2; intrinsics or coefficients that are not finite, fx or fy equal to 0, a clip that is not finite and positive;
@@ -594,7 +614,7 @@ int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, co
  * first image); a second create; n as for srl_flow_track_image.  SRL_ERR_NO_MAP: no preparer, or srl_flow_track_prepared without a
  * tracker.  SRL_ERR_NO_SWEEP: a download or srl_flow_track_prepared before the first image.  SRL_ERR_UNSUPPORTED: more than one rank.
  * A refused srl_image_prepare zeroes *info and leaves the previous results in place.  Every call cancels an armed launch;
- * srl_ctx_destroy frees the preparer.  Device memory: 16 bytes per pixel and 512 T T bytes of look-up tables (2 MB at T = 64). */
+ * srl_ctx_destroy frees the preparer.  Device memory: 16 bytes per pixel and 512 T T bytes of look-up tables (2 MB at T = 64); the resize adds 8 bytes per row and per column of tables and 3 bytes per source pixel. */
 typedef struct srl_image_prep_opts {
     int32_t rows, cols;
     double fx, fy, cx, cy;
@@ -608,6 +628,8 @@ int srl_image_prep_build_map(const srl_image_prep_opts *o, int16_t *map1 /* rows
 int srl_image_prep_create(srl_ctx *ctx, const srl_image_prep_opts *o);
 int srl_image_prep_destroy(srl_ctx *ctx);
 int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_image_prep_info *info /* or NULL */);
+int srl_image_resize_build_tables(int src_len, int dst_len, int32_t *ofs /* dst_len */, int16_t *coef /* dst_len x 2 */);   /* host only */
+int srl_image_prepare_resized(srl_ctx *ctx, const uint8_t *raw_bgr, int src_rows, int src_cols, int64_t row_stride_bytes, srl_image_prep_info *info /* or NULL */);
 int srl_image_prep_download(srl_ctx *ctx, int which /* 0 gray_eq, 1 bgr_eq */, uint8_t *out, int64_t row_stride_bytes);
 int srl_flow_track_prepared(srl_ctx *ctx, const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked);
 

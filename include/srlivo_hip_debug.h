@@ -145,6 +145,9 @@ int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8_t *image_p
  * argument or an unknown stage); no preparer: SRL_ERR_NO_MAP; no image yet: SRL_ERR_NO_SWEEP. */
 enum { SRL_PREP_STAGE_UNDIST = 0, SRL_PREP_STAGE_GRAY = 1, SRL_PREP_STAGE_YCRCB = 2, SRL_PREP_STAGE_LUT_GRAY = 3, SRL_PREP_STAGE_LUT_Y = 4 };
 int srl_image_prep_download_stage(srl_ctx *ctx, int stage, uint8_t *out, int64_t capacity);
+/* parity tests of the resize (srl_image_prepare_resized): the frame the last image's remap read, rows x cols x 3 bytes of the preparer's
+ * size -- the resized frame, or the uploaded one where no resize ran.  capacity, refusals: as above. */
+int srl_image_prep_download_resized(srl_ctx *ctx, uint8_t *out, int64_t capacity);
 /* tests of the consensus estimators (srl_consensus_fundamental, srl_consensus_pnp) on EVERY hypothesis: what this context's last call that
  * ran on the device (n >= 8 / n >= 4, not refused) left in the workspace.  Synchronous; cancels an armed launch.
  * info: model = SRL_CONSENSUS_FUNDAMENTAL / _PNP, hypotheses = H, n, slots = 3 / 4, usable = the number of usable points, norm = Hartley's

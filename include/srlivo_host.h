@@ -172,6 +172,11 @@ int srl_lio_optimize(srl_lio *lio, const srl_icp_opts *opts, double sample_voxel
 int srl_lio_eskf_try_init(srl_lio *lio, const double *t, const double *gyr, const double *acc, int n, int *initialized);
 int srl_lio_eskf_get_init_stats(srl_lio *lio, double out[14]);
 int srl_lio_set_initial_flag(srl_lio *lio, int flag);
+/* G_norm is process-global as well (utility.cpp:14: 9.81): the first processed frame of a replay writes the norm of the filter's gravity
+ * back into it (lioOptimization.cpp:1024) and the next initialisation scales its gravity by it, so a second replay in one process
+ * starts from another value than the first.  A harness that compares replays bit for bit sets it before each.  g_norm must be finite
+ * and positive. */
+int srl_lio_set_g_norm(srl_lio *lio, double g_norm);
 /* lioOptimization::stateInitialization (lioOptimization.cpp:895-990): pose prior (q wxyz, t) of frame index_frame from
  * prev2 / prev1 = poses of all_cloud_frame[size-2] / [size-1]; initialization: 0 INIT_IMU, 1 INIT_CONSTANT_VELOCITY. */
 int srl_lio_state_initialization(srl_lio *lio, int index_frame, int initialization, const double prev2[7],
@@ -337,6 +342,96 @@ int srl_oft_sizes(srl_oft *oft, int *last_pose, int *cur_pose, int *last_tracked
 int srl_oft_times(srl_oft *oft, double *last_image_time, double *current_image_time);
 int srl_oft_pose_map(srl_oft *oft, int which, srl_color_track_point *out, int capacity, int *n);
 int srl_oft_tracked_for_vio(srl_oft *oft, srl_color_vio_point *out, int capacity, int *n);
+
+/* ------------------------------------------------------------------ one camera frame end to end (csrc/host/imageProcessing.{h,cpp})
+ * imageProcessing::process (imageProcessing.cpp:89-164), statement by statement, on the camera state the handle keeps
+ * (srl_lio_vio_set_camera_state / _get_camera_state) and on an opticalFlowTracker, an image preparer and the colour-map bookkeeping
+ * the handle owns.  A frame runs, in this order:
+ *   first data (:91-111)   image_scale_factor = image_width image_resize_ratio / cols of the frame; the four intrinsics of
+ *                          srl_lio_vio_set_options divided by it, for good; the preparer created at (int)(image_height / scale) rows x
+ *                          (int)(image_width / scale) columns with them and the distortion coefficients (srl_image_prep_create); the
+ *                          tracker's setIntrinsic = srl_oft_use_device_consensus with them; maximum_tracked_points and the depth limits
+ *                          handed on
+ *   prepare (:113-125)     srl_image_prepare_resized iff fabs(image_resize_ratio - 1.0) > 1e-6, else srl_image_prepare; the tracker
+ *                          follows on the prepared gray image (srl_oft_use_prepared_image)
+ *   first data (:127-135)  the selection with minimum_dis = track_windows_size / scale, skip 1, and init
+ *   every frame (:137-163) trackImage; removeOutlierUsingRansacPnp; vioEsikf and vioPhotometric, both only when PnP accepted; the
+ *                          render with obs_time = time_sweep_end and the camera as the two updates left it; updatePoseForProjection
+ *                          with a margin of -0.4; refreshPointsForProjection (nothing on a frame_id it has refreshed for already);
+ *                          updateAndAppendTrackPoints with track_windows_size / scale; time_last_process = time_sweep_end, which the
+ *                          handle's next colour insertion reads -- srl_lio_set_color_times is not needed on this path.
+ * image_rows / image_cols of every projection test are the RAW frame's, as in the reference (lioOptimization.cpp:1080-1081); the render
+ * tests against the prepared image it reads.  The colour map must exist (srl_lio_set_color_map_options).
+ * Every step that leaves the mirror goes through a table of step functions whose defaults are the device calls named above;
+ * srl_lio_image_set_steps replaces any of them (NULL members keep the default; a NULL table puts every default back) so that a test
+ * can record order, gates and arguments without a device.  A step returns a srl_status; a failing step ends the frame with that
+ * status and no later step runs; *out holds what the frame reached.  The frame may be offered again: of the first data nothing is done
+ * twice (the intrinsics are scaled once, the preparer is created once, the consensus setup runs once), and the first selection and init
+ * run until they have succeeded.  A replaced fundamental or pnp step holds from the first frame on, also behind the default consensus
+ * setup; a member that goes back to NULL gets the device call back.  select: write at most `capacity` records and set *n; with *n >
+ * capacity return SRL_ERR_BAD_ARG and the call is repeated with room for *n.
+ * SRL_ERR_BAD_ARG: NULL lio or image, rows or cols < 1, a stride below a row, options never set.  A host-only handle with a step left
+ * at its default: SRL_ERR_NO_DEVICE, never a host loop.  A context of more than one rank: SRL_ERR_UNSUPPORTED (the preparer's and
+ * the consensus calls' own refusal).
+ * srl_lio_image_oft: the handle's tracker, for the srl_oft_* read-backs (owned by the handle; NULL lio: NULL).
+ * srl_lio_image_candidates: points_rgb_vec_for_projection as the last refresh left it (capacity 0 asks for the number alone). */
+typedef struct srl_image_process_opts {
+    int32_t image_width, image_height;          /* setImageWidth / setImageHeight */
+    double image_resize_ratio;                  /* imageProcessing.cpp:11: 1.0 */
+    double dist[5];                             /* camera_dist_coeffs: k1 k2 p1 p2 k3 */
+    double track_windows_size;                  /* :15: 40 */
+    int32_t maximum_tracked_points, reserved;   /* :14: 300 */
+    double tracker_minimum_depth, tracker_maximum_depth;      /* :17-18: 0.1, 200 */
+} srl_image_process_opts;
+typedef struct srl_image_process_result {
+    int32_t first_data, prepared_rows, prepared_cols;
+    int32_t tracked_after_flow, tracked_after_pnp, pnp_accepted;      /* map_rgb_points_in_cur_image_pose.size() behind either step */
+    int32_t esikf_accepted, esikf_iterations, esikf_used;
+    int32_t photometric_accepted, photometric_iterations, photometric_used;
+    int32_t refreshed_candidates, reserved;
+    double image_scale_factor;
+    srl_color_render_totals render;
+    srl_color_track_totals track;
+} srl_image_process_result;
+typedef struct srl_image_process_steps {
+    void *user;
+    int (*prep_create)(const srl_image_prep_opts *opts, void *user);
+    int (*prepare)(const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, int resized, void *user);
+    int (*consensus_setup)(const double *fx_fy_cx_cy, void *user);
+    int (*select)(const srl_color_camera *cam, int image_rows, int image_cols, const srl_color_select_opts *opts, int refresh, srl_color_selected *out,
+                  int capacity, int *n, void *user);
+    srl_oft_flow_provider flow;
+    srl_oft_fundamental_provider fundamental;
+    srl_oft_pnp_provider pnp;
+    srl_vio_rows_provider rows;
+    int (*render)(const srl_color_camera *cam, double obs_time, srl_color_render_totals *totals, void *user);
+    srl_oft_update_provider track_update;
+} srl_image_process_steps;
+void srl_image_process_opts_default(srl_image_process_opts *o);      /* the reference's constructor values; width, height, dist 0 */
+int srl_lio_image_set_options(srl_lio *lio, const srl_image_process_opts *opts);
+int srl_lio_image_set_steps(srl_lio *lio, const srl_image_process_steps *steps);
+int srl_lio_image_process(srl_lio *lio, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end, int frame_id,
+                          srl_image_process_result *out /* or NULL */);
+srl_oft *srl_lio_image_oft(srl_lio *lio);
+int srl_lio_image_candidates(srl_lio *lio, srl_color_selected *out, int capacity, int *n);
+int srl_lio_image_time_last_process(srl_lio *lio, double *time_last_process);
+/* srl_lio_run_measurement with the measurement's camera frame: lioOptimization::process (lioOptimization.cpp:1037-1086) with to_rendering
+ * set.  raw_bgr == NULL: no image -- exactly srl_lio_run_measurement, whatever the other image arguments hold.  Otherwise the sweep is
+ * inserted into the colour map with to_rendering, and behind stateEstimation, before the sliding window moves:
+ *   :1053-1071  fx fy cx cy, R_imu_camera and t_imu_camera of the handle's camera state are set from the configured values
+ *               (srl_lio_vio_set_options; the intrinsics as process's first data scaled them) while all_cloud_frame.size() < 3 and
+ *               otherwise left as the frame before left them, camera updates included;
+ *   :1073-1075  rotation and translation are the frame's, q_world_camera = rotation R_imu_camera, t_world_camera = rotation t_imu_camera
+ *               + translation;
+ *   :1077-1083  srl_lio_image_process's frame with time_sweep_end and frame_id of the sweep; *image_out (optional) is its record.
+ * The camera frame also runs behind a stateEstimation that failed (the reference's process does not look at the summary, :1049-1083;
+ * the sweep is then in neither map and the pose is the prior), and *image_out is its record.  Returns the first failure: the arguments',
+ * srl_lio_run_measurement's (SRL_ERR_NOT_ENOUGH_RESIDUALS included), then the camera frame's.  A measurement that only feeds the filter's
+ * initialisation runs no camera frame. */
+int srl_lio_run_measurement_image(srl_lio *lio, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                  const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
+                                  const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_replay_result *out,
+                                  srl_image_process_result *image_out /* or NULL */);
 
 /* lioOptimization::searchNeighbors / computeNeighborhoodDistribution single-call forms */
 int srl_lio_search_neighbors(srl_lio *lio, const double point[3], int nb_voxels_visited, double size_voxel_map,

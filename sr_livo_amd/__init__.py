@@ -14,5 +14,6 @@ from .capi import (  # noqa: F401
     ColorTrackOpts, ColorTrackTotals, COLOR_TRACK_POINT_DTYPE, default_color_track_opts, Oft,
     ConsensusOpts, ConsensusResult, default_consensus_opts, SRL_CONSENSUS_FUNDAMENTAL, SRL_CONSENSUS_PNP,
     SRL_CONSENSUS_MAX_POINTS, SRL_CONSENSUS_MAX_HYPOTHESES,
-    ImagePrep, ImagePrepOpts, ImagePrepInfo, default_image_prep_opts, image_prep_build_map,
+    ImagePrep, ImagePrepOpts, ImagePrepInfo, default_image_prep_opts, image_prep_build_map, image_resize_build_tables,
+    ImageProcessOpts, ImageProcessResult, ImageProcessSteps,
 )

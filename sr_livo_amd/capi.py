@@ -283,6 +283,37 @@ OFT_PNP_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_
 OFT_UPDATE_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorCamera), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(ColorTrackOpts),
                                      C.c_void_p, C.c_int64, C.POINTER(ColorTrackTotals), C.c_void_p)
 VIO_ROWS_PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorVioArgs), C.c_void_p, C.c_int, C.POINTER(ColorVioSums), C.c_void_p)
+
+
+class ImageProcessOpts(C.Structure):
+    """srl_image_process_opts: what imageProcessing::process reads beside the options of srl_lio_vio_set_options"""
+    _fields_ = [("image_width", C.c_int32), ("image_height", C.c_int32), ("image_resize_ratio", C.c_double), ("dist", C.c_double * 5),
+                ("track_windows_size", C.c_double), ("maximum_tracked_points", C.c_int32), ("reserved", C.c_int32),
+                ("tracker_minimum_depth", C.c_double), ("tracker_maximum_depth", C.c_double)]
+
+
+class ImageProcessResult(C.Structure):
+    """srl_image_process_result: what one srl_lio_image_process did"""
+    _fields_ = [(f, C.c_int32) for f in ("first_data", "prepared_rows", "prepared_cols", "tracked_after_flow", "tracked_after_pnp", "pnp_accepted",
+                                         "esikf_accepted", "esikf_iterations", "esikf_used", "photometric_accepted", "photometric_iterations",
+                                         "photometric_used", "refreshed_candidates", "reserved")] + \
+               [("image_scale_factor", C.c_double), ("render", ColorRenderTotals), ("track", ColorTrackTotals)]
+
+
+IMAGE_PREP_CREATE_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ImagePrepOpts), C.c_void_p)
+IMAGE_PREPARE_STEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p)
+IMAGE_CONSENSUS_SETUP_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_void_p)
+IMAGE_SELECT_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorCamera), C.c_int, C.c_int, C.POINTER(ColorSelectOpts), C.c_int, C.c_void_p, C.c_int,
+                                   C.POINTER(C.c_int), C.c_void_p)
+IMAGE_RENDER_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorCamera), C.c_double, C.POINTER(ColorRenderTotals), C.c_void_p)
+
+
+class ImageProcessSteps(C.Structure):
+    """srl_image_process_steps: the steps of imageProcessing::process that leave the mirror; a NULL member keeps the device call"""
+    _fields_ = [("user", C.c_void_p), ("prep_create", IMAGE_PREP_CREATE_STEP_FN), ("prepare", IMAGE_PREPARE_STEP_FN),
+                ("consensus_setup", IMAGE_CONSENSUS_SETUP_STEP_FN), ("select", IMAGE_SELECT_STEP_FN), ("flow", OFT_FLOW_PROVIDER_FN),
+                ("fundamental", OFT_FUNDAMENTAL_PROVIDER_FN), ("pnp", OFT_PNP_PROVIDER_FN), ("rows", VIO_ROWS_PROVIDER_FN),
+                ("render", IMAGE_RENDER_STEP_FN), ("track_update", OFT_UPDATE_PROVIDER_FN)]
 CAMERA_STATE_DOUBLES = 31      # time_td, R_imu_camera (9), t_imu_camera (3), fx fy cx cy, q_world_camera (4), t_world_camera (3), rotation (4), translation (3)
 
 _lib = None
@@ -344,6 +375,9 @@ def load_library():
         "srl_image_prep_create": ([p, C.POINTER(ImagePrepOpts)], C.c_int),
         "srl_image_prep_destroy": ([p], C.c_int),
         "srl_image_prepare": ([p, p, C.c_int, C.c_int, C.c_int64, C.POINTER(ImagePrepInfo)], C.c_int),
+        "srl_image_resize_build_tables": ([C.c_int, C.c_int, p, p], C.c_int),
+        "srl_image_prepare_resized": ([p, p, C.c_int, C.c_int, C.c_int64, C.POINTER(ImagePrepInfo)], C.c_int),
+        "srl_image_prep_download_resized": ([p, p, C.c_int64], C.c_int),
         "srl_image_prep_download": ([p, C.c_int, p, C.c_int64], C.c_int),
         "srl_image_prep_download_stage": ([p, C.c_int, p, C.c_int64], C.c_int),
         "srl_flow_track_prepared": ([p, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
@@ -503,6 +537,9 @@ def load_library():
         "srl_lio_set_odometry_options": ([p, C.POINTER(OdometryOpts)], C.c_int),
         "srl_lio_run_measurement": ([p, C.c_double, p, p, p, C.c_int, p, p, C.c_int, C.c_double, C.c_double,
                                      C.POINTER(ReplayResult)], C.c_int),
+        "srl_lio_run_measurement_image": ([p, C.c_double, p, p, p, C.c_int, p, p, C.c_int, C.c_double, C.c_double, p, C.c_int, C.c_int, C.c_int64,
+                                           C.POINTER(ReplayResult), C.POINTER(ImageProcessResult)], C.c_int),
+        "srl_lio_set_g_norm": ([p, C.c_double], C.c_int),
         "srl_lio_last_frame": ([p, C.c_int, p, p, p, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_optimize_resident": ([p, C.POINTER(IcpOpts), C.c_double, p, C.c_int, dp, dp, C.c_int, p,
                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
@@ -520,6 +557,13 @@ def load_library():
         "srl_lio_vio_set_rows_provider": ([p, VIO_ROWS_PROVIDER_FN, p], C.c_int),
         "srl_lio_vio_esikf": ([p, p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), p, C.c_int], C.c_int),
         "srl_lio_vio_photometric": ([p, p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), p, C.c_int], C.c_int),
+        "srl_image_process_opts_default": ([C.POINTER(ImageProcessOpts)], None),
+        "srl_lio_image_set_options": ([p, C.POINTER(ImageProcessOpts)], C.c_int),
+        "srl_lio_image_set_steps": ([p, C.POINTER(ImageProcessSteps)], C.c_int),
+        "srl_lio_image_process": ([p, p, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, C.POINTER(ImageProcessResult)], C.c_int),
+        "srl_lio_image_oft": ([p], C.c_void_p),
+        "srl_lio_image_candidates": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_lio_image_time_last_process": ([p, C.POINTER(C.c_double)], C.c_int),
         "srl_grid_sampling": ([p, C.c_int, C.c_double, p, C.POINTER(C.c_int)], C.c_int),
         "srl_debug_tr1_order": ([p, C.c_int, p], C.c_int),
         "srl_debug_tr1_order_by_relation": ([p, C.c_int, p], C.c_int),
@@ -621,6 +665,17 @@ def image_prep_build_map(opts):
     if rc != SRL_OK:
         raise SrlError(rc, "srl_image_prep_build_map", "")
     return map1[:n].reshape(opts.rows, opts.cols, 2), map2[:n].reshape(opts.rows, opts.cols)
+
+
+def image_resize_build_tables(src_len, dst_len):
+    """srl_image_resize_build_tables (host only): (ofs (dst_len,) int32, coef (dst_len, 2) int16); raises SrlError where it refuses"""
+    n = max(int(dst_len), 1)
+    ofs = np.zeros(n, dtype=np.int32)
+    coef = np.zeros((n, 2), dtype=np.int16)
+    rc = load_library().srl_image_resize_build_tables(int(src_len), int(dst_len), _ptr(ofs), _ptr(coef))
+    if rc != SRL_OK:
+        raise SrlError(rc, "srl_image_resize_build_tables", "")
+    return ofs, coef
 
 
 def default_consensus_opts(model, **kw):
@@ -1502,6 +1557,23 @@ class ImagePrep:
         self.ctx._chk(self.lib.srl_image_prepare(self.ctx.h, _ptr(b), b.shape[0], b.shape[1], b.strides[0], C.byref(info)), "srl_image_prepare")
         return info
 
+    def prepare_resized(self, raw_bgr):
+        """srl_image_prepare_resized: raw_bgr (src_rows, src_cols, 3) uint8 of any size (rows may be strided), resized on the device to the
+        preparer's size before the chain.  Returns ImagePrepInfo."""
+        b = np.asarray(raw_bgr)
+        if b.dtype != np.uint8 or b.ndim != 3 or b.shape[2] != 3 or b.strides[2] != 1 or b.strides[1] != 3 or b.strides[0] < 3 * b.shape[1]:
+            b = np.ascontiguousarray(b, dtype=np.uint8)
+        info = ImagePrepInfo()
+        self.ctx._chk(self.lib.srl_image_prepare_resized(self.ctx.h, _ptr(b), b.shape[0], b.shape[1], b.strides[0], C.byref(info)),
+                      "srl_image_prepare_resized")
+        return info
+
+    def download_resized(self):
+        """srl_image_prep_download_resized: the frame the last image's remap read, (rows, cols, 3) uint8"""
+        out = np.zeros((self.opts.rows, self.opts.cols, 3), dtype=np.uint8)
+        self.ctx._chk(self.lib.srl_image_prep_download_resized(self.ctx.h, _ptr(out), out.size), "srl_image_prep_download_resized")
+        return out
+
     def download(self, which):
         """srl_image_prep_download: SRL_PREP_GRAY_EQ -> (rows, cols) uint8, SRL_PREP_BGR_EQ -> (rows, cols, 3) uint8"""
         shape = (self.opts.rows, self.opts.cols, 3) if which == SRL_PREP_BGR_EQ else (self.opts.rows, self.opts.cols)
@@ -1748,6 +1820,10 @@ class Lio:
         return dict(mean_gyr=o[0:3].copy(), mean_acc=o[3:6].copy(), gyr_cov=o[6:9].copy(), acc_cov=o[9:12].copy(),
                     num_init_meas=int(o[12]), initial_flag=bool(o[13]))
 
+    def set_g_norm(self, g_norm=9.81):
+        """srl_lio_set_g_norm: the process-global G_norm (9.81 at start; a replay's first processed frame rewrites it)"""
+        self._chk(self.lib.srl_lio_set_g_norm(self.h, float(g_norm)), "srl_lio_set_g_norm")
+
     def set_initial_flag(self, flag):
         self._chk(self.lib.srl_lio_set_initial_flag(self.h, int(bool(flag))), "set_initial_flag")
 
@@ -1882,6 +1958,54 @@ class Lio:
 
     def vio_photometric(self, tracked, number_of_new_visited_voxel, capacity=16):
         return self._vio_update(self.lib.srl_lio_vio_photometric, "srl_lio_vio_photometric", tracked, number_of_new_visited_voxel, capacity)
+
+    def image_set_options(self, **kw):
+        """srl_lio_image_set_options: image_width, image_height, image_resize_ratio, dist (five), track_windows_size,
+        maximum_tracked_points, tracker_minimum_depth, tracker_maximum_depth over the reference's defaults"""
+        o = ImageProcessOpts()
+        self.lib.srl_image_process_opts_default(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, (C.c_double * 5)(*v) if k == "dist" else v)
+        self._chk(self.lib.srl_lio_image_set_options(self.h, C.byref(o)), "srl_lio_image_set_options")
+        return o
+
+    def image_set_steps(self, steps=None):
+        """srl_lio_image_set_steps: an ImageProcessSteps whose members are ctypes callbacks (kept alive here), or None for the device calls"""
+        self._image_steps = steps
+        self._chk(self.lib.srl_lio_image_set_steps(self.h, C.byref(steps) if steps is not None else None), "srl_lio_image_set_steps")
+
+    def image_process(self, raw_bgr, time_sweep_end, frame_id, ok=()):
+        """srl_lio_image_process: imageProcessing::process on the handle's camera state, raw_bgr (rows, cols, 3) uint8 (rows may be
+        strided).  Returns ImageProcessResult; with a status listed in `ok`, (status, ImageProcessResult)."""
+        b = np.asarray(raw_bgr)
+        if b.dtype != np.uint8 or b.ndim != 3 or b.shape[2] != 3 or b.strides[2] != 1 or b.strides[1] != 3 or b.strides[0] < 3 * b.shape[1]:
+            b = np.ascontiguousarray(b, dtype=np.uint8)
+        res = ImageProcessResult()
+        rc = self._chk(self.lib.srl_lio_image_process(self.h, _ptr(b), b.shape[0], b.shape[1], b.strides[0], float(time_sweep_end), int(frame_id),
+                                                      C.byref(res)), "srl_lio_image_process", ok)
+        return (rc, res) if ok else res
+
+    def image_oft(self):
+        """srl_lio_image_oft: the handle's tracker as an Oft that does not own it (read-backs: sizes, times, pose_map, tracked_for_vio)"""
+        o = Oft.__new__(Oft)
+        o.lib, o.ctx, o._keep = self.lib, self.ctx, {}
+        o.h = C.c_void_p(self.lib.srl_lio_image_oft(self.h))
+        o.close = lambda: None
+        return o
+
+    def image_candidates(self):
+        """srl_lio_image_candidates: points_rgb_vec_for_projection as the last refresh left it (COLOR_SELECTED_DTYPE)"""
+        n = C.c_int()
+        self._chk(self.lib.srl_lio_image_candidates(self.h, None, 0, C.byref(n)), "srl_lio_image_candidates")
+        out = np.zeros(n.value, dtype=COLOR_SELECTED_DTYPE)
+        if n.value:
+            self._chk(self.lib.srl_lio_image_candidates(self.h, _ptr(out), len(out), C.byref(n)), "srl_lio_image_candidates")
+        return out
+
+    def image_time_last_process(self):
+        t = C.c_double()
+        self._chk(self.lib.srl_lio_image_time_last_process(self.h, C.byref(t)), "srl_lio_image_time_last_process")
+        return t.value
 
     def render_points_in_recent_voxel(self, camera, obs_time):
         """rgbMapTracker::renderPointsInRecentVoxel on voxels_recent_visited (srl_lio_render_points_in_recent_voxel); camera = ColorCamera.
@@ -2098,6 +2222,26 @@ class Lio:
         return dict(rc=rc, processed=bool(out.processed), initialized=bool(out.initialized), index_frame=out.index_frame,
                     success=bool(out.success), num_residuals=out.num_residuals_used, iters=out.iterations, frame_points=out.frame_points,
                     keypoints=out.keypoints, points_added=out.points_added, state=np.array(out.state))
+
+    def run_measurement_image(self, time_frame, imu_t, imu_acc, imu_gyr, pts_raw, pts_timestamp, time_sweep_begin, time_sweep_offset, raw_bgr,
+                              allow=(SRL_ERR_NOT_ENOUGH_RESIDUALS,)):
+        """srl_lio_run_measurement_image: run_measurement with the measurement's camera frame, raw_bgr (rows, cols, 3) uint8 or None (no
+        image: exactly run_measurement).  Returns run_measurement's dict with the ImageProcessResult under "image"."""
+        it = _f64(imu_t); ia = _f64(imu_acc, (-1, 3)); ig = _f64(imu_gyr, (-1, 3))
+        pr = _f64(pts_raw, (-1, 3)); pt = _f64(pts_timestamp)
+        b, rows, cols, stride = None, 0, 0, 0
+        if raw_bgr is not None:
+            b = np.asarray(raw_bgr)
+            if b.dtype != np.uint8 or b.ndim != 3 or b.shape[2] != 3 or b.strides[2] != 1 or b.strides[1] != 3 or b.strides[0] < 3 * b.shape[1]:
+                b = np.ascontiguousarray(b, dtype=np.uint8)
+            rows, cols, stride = b.shape[0], b.shape[1], b.strides[0]
+        out, img = ReplayResult(), ImageProcessResult()
+        rc = self._chk(self.lib.srl_lio_run_measurement_image(self.h, float(time_frame), _ptr(it), _ptr(ia), _ptr(ig), len(it), _ptr(pr), _ptr(pt),
+                                                              len(pr), float(time_sweep_begin), float(time_sweep_offset), _ptr(b), rows, cols, stride,
+                                                              C.byref(out), C.byref(img)), "run_measurement_image", ok=allow)
+        return dict(rc=rc, processed=bool(out.processed), initialized=bool(out.initialized), index_frame=out.index_frame,
+                    success=bool(out.success), num_residuals=out.num_residuals_used, iters=out.iterations, frame_points=out.frame_points,
+                    keypoints=out.keypoints, points_added=out.points_added, state=np.array(out.state), image=img)
 
     def last_frame(self):
         n = C.c_int()

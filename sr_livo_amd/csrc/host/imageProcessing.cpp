@@ -168,6 +168,125 @@ bool imageProcessing::vioPhotometric(cameraState &st, const srl_color_vio_point 
     return true;
 }
 
+namespace {
+srl_color_camera camera_of(const cameraState &st, double fov_margin) {
+    srl_color_camera c;
+    c.q_world_camera[0] = st.q_world_camera.w; c.q_world_camera[1] = st.q_world_camera.x;
+    c.q_world_camera[2] = st.q_world_camera.y; c.q_world_camera[3] = st.q_world_camera.z;
+    for (int k = 0; k < 3; k++) c.t_world_camera[k] = st.t_world_camera[k];
+    c.fx = st.fx; c.fy = st.fy; c.cx = st.cx; c.cy = st.cy;
+    c.fov_margin = fov_margin;
+    return c;
+}
+const double frame_fov_margin = 0.005;                   // state.cpp:25: the margin of every p_frame->p_state
+}  // namespace
+
+int imageProcessing::process(cameraState &st, const imageFrame &frame, int number_of_new_visited_voxel, srl_image_process_result *result) {      // :89-164
+    srl_image_process_result r = {};
+    auto leave = [&](int rc) { status = rc; if (result) *result = r; return rc; };
+    if (!op_tracker || !steps.prepCreate || !steps.prepare || !steps.consensusSetup || !steps.select || !steps.render) return leave(SRL_ERR_NO_DEVICE);
+    if (!frame.rgb_image || frame.image_rows < 1 || frame.image_cols < 1) return leave(SRL_ERR_BAD_ARG);
+    r.first_data = first_data ? 1 : 0;
+
+    // :91-111.  The reference has no failing step; here one may fail, and the frame is then offered again.  So nothing of the first
+    // data is done twice: the scale, the size and the scaled intrinsics are committed once, with the preparer (first_data_stage 1), the
+    // consensus setup once behind them (2), and first_data itself falls behind init as in the reference
+    if (first_data && first_data_stage < 1) {
+        if (image_width < 1 || image_height < 1 || !(image_resize_ratio > 0.0)) return leave(SRL_ERR_BAD_ARG);
+        const double scale = image_width * image_resize_ratio / frame.image_cols;
+        const double fx = camera_intrinsic(0, 0) / scale, cx = camera_intrinsic(0, 2) / scale;
+        const double fy = camera_intrinsic(1, 1) / scale, cy = camera_intrinsic(1, 2) / scale;
+        srl_image_prep_opts po;
+        srl_image_prep_opts_default(&po);
+        po.cols = (int)(image_width / scale);            // cv::Size(int, int) of two doubles
+        po.rows = (int)(image_height / scale);
+        po.fx = fx; po.fy = fy; po.cx = cx; po.cy = cy;
+        for (int k = 0; k < 5; k++) po.dist[k] = camera_dist_coeffs[k];
+        { const int rc = steps.prepCreate(po); if (rc != SRL_OK) return leave(rc); }                  // :103
+        image_scale_factor = scale;                      // :93-98
+        camera_intrinsic(0, 0) = fx; camera_intrinsic(0, 2) = cx; camera_intrinsic(1, 1) = fy; camera_intrinsic(1, 2) = cy;
+        prepared_rows = po.rows; prepared_cols = po.cols;
+        first_data_stage = 1;
+    }
+    if (first_data && first_data_stage < 2) {
+        const double k4[4] = {camera_intrinsic(0, 0), camera_intrinsic(1, 1), camera_intrinsic(0, 2), camera_intrinsic(1, 2)};
+        { const int rc = steps.consensusSetup(k4); if (rc != SRL_OK) return leave(rc); }              // :106
+        op_tracker->maximum_tracked_points = maximum_tracked_points;                                  // :107
+        minimum_depth_for_projection = tracker_minimum_depth;                                         // :109-110
+        maximum_depth_for_projection = tracker_maximum_depth;
+        first_data_stage = 2;
+    }
+    r.prepared_rows = prepared_rows; r.prepared_cols = prepared_cols; r.image_scale_factor = image_scale_factor;
+
+    {                                                    // :113-125: the resize iff the ratio says so, then remap, gray + CLAHE, YCrCb
+        const bool resized = std::fabs(image_resize_ratio - 1.0) > 1e-6;
+        const int rc = steps.prepare(frame.rgb_image, frame.image_rows, frame.image_cols, frame.row_stride_bytes, resized);
+        if (rc != SRL_OK) return leave(rc);
+    }
+
+    const srl_color_camera cam_in = camera_of(st, frame_fov_margin);
+    if (first_data) {                                    // :127-135
+        const srl_color_select_opts so = {track_windows_size / image_scale_factor, 1, 0, minimum_depth_for_projection, maximum_depth_for_projection};
+        std::vector<srl_color_selected> rgb_points_vec_temp;
+        { const int rc = steps.select(cam_in, frame.image_rows, frame.image_cols, so, false, rgb_points_vec_temp); if (rc != SRL_OK) return leave(rc); }
+        if (!op_tracker->init(rgb_points_vec_temp.data(), (int)rgb_points_vec_temp.size(), nullptr, prepared_rows, prepared_cols, prepared_cols,
+                              frame.time_sweep_end))
+            return leave(op_tracker->status);
+        first_data = false;
+    }
+
+    // :137 (distance = -20 switches rejectErrorTrackingPoints off: not built)
+    if (!op_tracker->trackImage(nullptr, prepared_rows, prepared_cols, prepared_cols, frame.time_sweep_end, frame.image_rows, frame.image_cols))
+        return leave(op_tracker->status);
+    r.tracked_after_flow = (int)op_tracker->map_rgb_points_in_cur_image_pose.size();
+
+    bool enough_points = true;                           // :139-145
+    {
+        bool accepted = false;
+        if (!op_tracker->removeOutlierUsingRansacPnp(1, &accepted)) return leave(op_tracker->status);
+        if (!accepted) enough_points = false;
+    }
+    r.tracked_after_pnp = (int)op_tracker->map_rgb_points_in_cur_image_pose.size();
+    r.pnp_accepted = enough_points ? 1 : 0;
+
+    if (enough_points) {                                 // :149-150
+        const std::vector<srl_color_vio_point> tracked = op_tracker->trackedForVio();
+        const bool res_esikf = vioEsikf(st, tracked.data(), (int)tracked.size(), number_of_new_visited_voxel);
+        if (status != SRL_OK) return leave(status);
+        r.esikf_accepted = res_esikf ? 1 : 0; r.esikf_iterations = (int)iterations.size(); r.esikf_used = last_used;
+    }
+    if (enough_points) {                                 // :152-153
+        const std::vector<srl_color_vio_point> tracked = op_tracker->trackedForVio();
+        const bool res_photometric = vioPhotometric(st, tracked.data(), (int)tracked.size(), number_of_new_visited_voxel);
+        if (status != SRL_OK) return leave(status);
+        r.photometric_accepted = res_photometric ? 1 : 0; r.photometric_iterations = (int)iterations.size(); r.photometric_used = last_used;
+    }
+
+    const srl_color_camera cam_out = camera_of(st, frame_fov_margin);      // the camera as the two updates left it
+    { const int rc = steps.render(cam_out, frame.time_sweep_end, r.render); if (rc != SRL_OK) return leave(rc); }      // :155
+
+    projection_camera = camera_of(st, -0.4);             // :157 updatePoseForProjection(p_frame, -0.4)
+    projection_rows = frame.image_rows; projection_cols = frame.image_cols; projection_frame_id = frame.frame_id;
+
+    if (!(projection_cols == 0 || projection_rows == 0) && projection_frame_id != updated_frame_index) {      // :159, rgbMapTracker.cpp:26-43
+        const srl_color_select_opts so = {10.0, 1, 0, minimum_depth_for_projection, maximum_depth_for_projection};
+        std::vector<srl_color_selected> temp;
+        { const int rc = steps.select(projection_camera, projection_rows, projection_cols, so, true, temp); if (rc != SRL_OK) return leave(rc); }
+        points_for_projection.swap(temp);
+        updated_frame_index = projection_frame_id;
+    }
+    r.refreshed_candidates = (int)points_for_projection.size();
+
+    // :161 (the reference's last argument, 1000000, is a parameter its function never reads)
+    const bool topped = op_tracker->updateAndAppendTrackPoints(&cam_out, frame.image_rows, frame.image_cols, points_for_projection.data(),
+                                                               (int)points_for_projection.size(), track_windows_size / image_scale_factor);
+    r.track = op_tracker->update_totals;
+    if (!topped) return leave(op_tracker->status);
+
+    time_last_process = frame.time_sweep_end;            // :163
+    return leave(SRL_OK);
+}
+
 void imageProcessing::updateCameraParameters(cameraState &st, const srl::Mat<6, 1> &d_x) {      // :554-566
     srl::Quat q_imu_camera = srl::Quat::fromRotationMatrix(st.R_imu_camera);
     q_imu_camera = (q_imu_camera * numType::so3ToQuat(srl::vec3(d_x(0), d_x(1), d_x(2)))).normalized();

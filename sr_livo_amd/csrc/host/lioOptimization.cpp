@@ -892,6 +892,7 @@ void lioOptimization::process(std::vector<point3D> &cut_sweep, double timestamp_
     optimizeSummary summary = stateEstimation(p_frame);
     if (summary_out) *summary_out = summary;
     dt_sum = 0;
+    if (camera_half) camera_half(p_frame);                                // :1053-1086: also behind a failed stateEstimation, as in the reference
 
     int num_remove = 0;
     auto drop_front = [&]() {

@@ -11,6 +11,7 @@
 #include "state.h"
 #include "utility.h"
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -178,6 +179,9 @@ public:
     bool runMeasurement(Measurement &measurement, optimizeSummary *summary = nullptr);
     void process(std::vector<point3D> &cut_sweep, double timestamp_begin, double timestamp_offset, optimizeSummary *summary = nullptr);
     optimizeSummary stateEstimation(cloudFrame *p_frame);
+    // the camera half of process() (lioOptimization.cpp:1053-1086), between stateEstimation (whatever its summary says: the reference does not look at it) and the sliding window: the
+    // frame is the newest of all_cloud_frame.  Empty unless a caller with an image sets it for one measurement (srl_lio_run_measurement_image)
+    std::function<void(cloudFrame *)> camera_half;
     void releaseFrames();
     icpOptions optimize_options;                                         // odometry_options.optimize_options
     double init_sample_voxel_size = 1.0, sample_voxel_size = 1.5;        // parameters.h:64,72

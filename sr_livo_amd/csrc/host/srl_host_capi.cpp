@@ -6,6 +6,7 @@
 #include "tr1_order.h"
 #include "tr1_relation.h"
 
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <stdexcept>
@@ -21,6 +22,10 @@ struct srl_lio {
     cameraState camera;
     srl_vio_rows_provider vio_provider = nullptr;
     void *vio_user = nullptr;
+    // imageProcessing::process: the tracker it works on (made at the first frame) and the step table as given
+    srl_oft *oft = nullptr;
+    srl_image_process_steps image_steps = {};
+    bool image_options_set = false;
 };
 
 namespace {
@@ -123,6 +128,7 @@ int srl_lio_create(int device, srl_lio **out) {
 
 int srl_lio_destroy(srl_lio *h) {
     if (!h) return SRL_OK;
+    delete h->oft;                            // its device tracker lives on the context lio owns
     delete h->lio;
     delete h;
     return SRL_OK;
@@ -520,6 +526,11 @@ int srl_lio_set_initial_flag(srl_lio *h, int flag) {
     initial_flag = flag != 0;
     return SRL_OK;
 }
+int srl_lio_set_g_norm(srl_lio *h, double g_norm) {
+    if (!h || !(g_norm > 0.0) || !std::isfinite(g_norm)) return SRL_ERR_BAD_ARG;
+    G_norm = g_norm;
+    return SRL_OK;
+}
 int srl_lio_state_initialization(srl_lio *h, int index_frame, int initialization, const double prev2[7], const double prev1[7],
                                  double out[7]) {
     if (!h || !out || (index_frame > 2 && (!prev2 || !prev1))) return SRL_ERR_BAD_ARG;
@@ -854,5 +865,199 @@ int srl_lio_vio_esikf(srl_lio *h, const srl_color_vio_point *tracked, int n, int
 int srl_lio_vio_photometric(srl_lio *h, const srl_color_vio_point *tracked, int n, int number_of_new_visited_voxel, int *accepted, int *iterations, int *used,
                             double *states, int capacity) {
     return vio_update(h, true, tracked, n, number_of_new_visited_voxel, accepted, iterations, used, states, capacity);
+}
+}  // extern "C"
+
+// ------------------------------------------------------------------ one camera frame end to end (imageProcessing::process)
+namespace {
+// the handle's step table as imageProcessing::process and the tracker take it: a member the caller gave, or the device call
+int image_install_steps(srl_lio *h) {
+    srl_ctx *ctx = h->lio->context();
+    const srl_image_process_steps S = h->image_steps;
+    void *user = S.user;
+    const bool all = S.prep_create && S.prepare && S.consensus_setup && S.select && S.flow && S.fundamental && S.pnp && (S.rows || h->vio_provider) &&
+                     S.render && S.track_update;
+    if (!ctx && !all) { h->err = "host-only handle: no device for the steps of imageProcessing::process left at their defaults"; return SRL_ERR_NO_DEVICE; }
+    if (!h->oft) h->oft = new srl_oft(ctx);
+    opticalFlowTracker &t = h->oft->t;
+    lioOptimization *L = h->lio;
+    h->vio.op_tracker = &t;
+    processSteps &P = h->vio.steps;
+    if (S.prep_create) P.prepCreate = [S, user](const srl_image_prep_opts &o) { return S.prep_create(&o, user); };
+    else P.prepCreate = [ctx](const srl_image_prep_opts &o) { return srl_image_prep_create(ctx, &o); };
+    if (S.prepare) P.prepare = [S, user](const uint8_t *raw, int rows, int cols, int64_t stride, bool resized) { return S.prepare(raw, rows, cols, stride, resized ? 1 : 0, user); };
+    else P.prepare = [ctx](const uint8_t *raw, int rows, int cols, int64_t stride, bool resized) {
+        return resized ? srl_image_prepare_resized(ctx, raw, rows, cols, stride, nullptr) : srl_image_prepare(ctx, raw, rows, cols, stride, nullptr);
+    };
+    // The tracker's two consensus providers: the device's estimators on the intrinsics k (useDeviceConsensus installs both), then the
+    // caller's on top where the table has them.  ONE function, run behind the consensus setup of the first data and again by every later
+    // install, so that a replaced step holds from the first frame on and a member that went back to NULL gets the device call back.
+    // (pnp_is_device: a failing step ends the frame with its status, it is not the cv::Exception the reference catches)
+    const auto consensus_providers = [S, user, &t](const double *k) {
+        if (!(S.fundamental && S.pnp)) { const int rc = t.useDeviceConsensus(k, nullptr, nullptr); if (rc != SRL_OK) return rc; }
+        if (S.fundamental) t.fundamental = [S, user](const float *l, const float *c, int n, uint8_t *st) { return S.fundamental(l, c, n, st, user); };
+        if (S.pnp) { t.pnp = [S, user](const float *xyz, const float *uv, int n, int32_t *in, int *nin) { return S.pnp(xyz, uv, n, in, nin, user); }; t.pnp_is_device = true; }
+        return (int)SRL_OK;
+    };
+    P.consensusSetup = [S, user, consensus_providers](const double *k) {
+        if (S.consensus_setup) { const int rc = S.consensus_setup(k, user); if (rc != SRL_OK) return rc; }
+        return consensus_providers(k);
+    };
+    if (h->vio.first_data_stage >= 2) {
+        const double k[4] = {h->vio.camera_intrinsic(0, 0), h->vio.camera_intrinsic(1, 1), h->vio.camera_intrinsic(0, 2), h->vio.camera_intrinsic(1, 2)};
+        const int rc = consensus_providers(k);
+        if (rc != SRL_OK) return rc;
+    }
+    if (S.select)
+        P.select = [S, user](const srl_color_camera &cam, int rows, int cols, const srl_color_select_opts &o, bool refresh, std::vector<srl_color_selected> &out) {
+            out.resize(4096);
+            int n = 0;
+            int rc = S.select(&cam, rows, cols, &o, refresh ? 1 : 0, out.data(), (int)out.size(), &n, user);
+            if (rc == SRL_ERR_BAD_ARG && n > (int)out.size()) {
+                out.resize((size_t)n);
+                rc = S.select(&cam, rows, cols, &o, refresh ? 1 : 0, out.data(), (int)out.size(), &n, user);
+            }
+            if (rc == SRL_OK && (n < 0 || n > (int)out.size())) rc = SRL_ERR_BAD_ARG;
+            out.resize(rc == SRL_OK ? (size_t)n : 0);
+            return rc;
+        };
+    else
+        P.select = [h, L](const srl_color_camera &cam, int rows, int cols, const srl_color_select_opts &o, bool refresh, std::vector<srl_color_selected> &out) {
+            L->minimum_depth_for_projection = o.minimum_depth; L->maximum_depth_for_projection = o.maximum_depth;
+            try {
+                out = L->selectPointsForProjection(cam, rows, cols, o.minimum_dis, o.skip_step, o.use_all_points != 0);
+                if (refresh) L->points_for_projection = out;
+            } catch (const std::exception &e) { return status_from_exception(h, e); }
+            return (int)SRL_OK;
+        };
+    if (S.render) P.render = [S, user](const srl_color_camera &cam, double obs_time, srl_color_render_totals &tot) { return S.render(&cam, obs_time, &tot, user); };
+    else
+        P.render = [h, L](const srl_color_camera &cam, double obs_time, srl_color_render_totals &tot) {
+            try { L->renderPointsInRecentVoxel(cam, obs_time); } catch (const std::exception &e) { return status_from_exception(h, e); }
+            tot = L->render_totals;
+            return (int)SRL_OK;
+        };
+    // the tracker's providers
+    if (S.flow) {
+        t.flow = [S, user](const uint8_t *g, int r, int c, int64_t s, const float *p, int n, float *x, uint8_t *st) { return S.flow(g, r, c, s, p, n, x, st, user); };
+        t.use_prepared_image = true;                                       // a NULL gray is the prepared image, not the empty one
+    } else {
+        t.flow = nullptr;
+        const int rc = t.usePreparedImage(true);
+        if (rc != SRL_OK) return rc;
+    }
+    if (S.track_update)
+        t.update = [S, user](const srl_color_camera *cam, int r, int c, const srl_color_track_point *tr, int n, const int32_t *cand, int nc,
+                             const srl_color_track_opts *o, srl_color_track_point *out, int64_t cap, srl_color_track_totals *tot) {
+            return S.track_update(cam, r, c, tr, n, cand, nc, o, out, cap, tot, user);
+        };
+    else t.update = nullptr;
+    if (S.rows) h->vio.rows = [S, user](const srl_color_vio_args *a, const srl_color_vio_point *p, int m, srl_color_vio_sums *s) { return S.rows(a, p, m, s, user); };
+    else if (h->vio_provider) {
+        srl_lio *self = h;
+        h->vio.rows = [self](const srl_color_vio_args *a, const srl_color_vio_point *p, int m, srl_color_vio_sums *s) { return self->vio_provider(a, p, m, s, self->vio_user); };
+    } else h->vio.rows = [ctx](const srl_color_vio_args *a, const srl_color_vio_point *p, int m, srl_color_vio_sums *s) { return srl_color_map_vio_rows(ctx, a, p, m, s, nullptr, nullptr); };
+    return SRL_OK;
+}
+}  // namespace
+
+extern "C" {
+void srl_image_process_opts_default(srl_image_process_opts *o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof *o);
+    o->image_resize_ratio = 1.0; o->track_windows_size = 40; o->maximum_tracked_points = 300;      // imageProcessing.cpp:11-18
+    o->tracker_minimum_depth = 0.1; o->tracker_maximum_depth = 200;
+}
+int srl_lio_image_set_options(srl_lio *h, const srl_image_process_opts *o) {
+    if (!h || !o || o->image_width < 1 || o->image_height < 1 || !(o->image_resize_ratio > 0.0) || !(o->track_windows_size > 0.0)) return SRL_ERR_BAD_ARG;
+    imageProcessing &v = h->vio;
+    v.image_width = o->image_width; v.image_height = o->image_height; v.image_resize_ratio = o->image_resize_ratio;
+    for (int k = 0; k < 5; k++) v.camera_dist_coeffs[k] = o->dist[k];
+    v.track_windows_size = o->track_windows_size; v.maximum_tracked_points = o->maximum_tracked_points;
+    v.tracker_minimum_depth = o->tracker_minimum_depth; v.tracker_maximum_depth = o->tracker_maximum_depth;
+    h->image_options_set = true;
+    return SRL_OK;
+}
+int srl_lio_image_set_steps(srl_lio *h, const srl_image_process_steps *steps) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    if (steps) h->image_steps = *steps; else h->image_steps = srl_image_process_steps();
+    return SRL_OK;
+}
+int srl_lio_image_process(srl_lio *h, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end, int frame_id,
+                          srl_image_process_result *out) {
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || !raw_bgr || rows < 1 || cols < 1 || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    if (!h->image_options_set) { h->err = "srl_lio_image_process: no options (srl_lio_image_set_options)"; return SRL_ERR_BAD_ARG; }
+    { const int rc = image_install_steps(h); if (rc != SRL_OK) return rc; }
+    imageFrame f;
+    f.rgb_image = raw_bgr; f.image_rows = rows; f.image_cols = cols; f.row_stride_bytes = row_stride_bytes;
+    f.time_sweep_end = time_sweep_end; f.frame_id = frame_id;
+    int rc;
+    try { rc = h->vio.process(h->camera, f, h->lio->number_of_new_visited_voxel, out); }
+    catch (const std::exception &e) { return status_from_exception(h, e); }
+    if (rc == SRL_OK) h->lio->time_last_process = h->vio.time_last_process;      // what the next colour insertion reads; a frame that did not finish moves nothing
+    if (rc != SRL_OK && h->lio->context()) { const char *m = srl_last_error(h->lio->context()); if (m && *m) h->err = m; }
+    return rc;
+}
+srl_oft *srl_lio_image_oft(srl_lio *h) {
+    if (!h) return nullptr;
+    if (!h->oft) h->oft = new srl_oft(h->lio->context());
+    return h->oft;
+}
+int srl_lio_image_candidates(srl_lio *h, srl_color_selected *out, int capacity, int *n) {
+    if (n) *n = 0;
+    if (!h || !n || capacity < 0 || (capacity > 0 && !out)) return SRL_ERR_BAD_ARG;
+    const std::vector<srl_color_selected> &c = h->vio.points_for_projection;
+    *n = (int)c.size();
+    if ((int)c.size() > capacity) return capacity == 0 ? SRL_OK : SRL_ERR_BAD_ARG;
+    if (!c.empty()) std::memcpy(out, c.data(), c.size() * sizeof(srl_color_selected));
+    return SRL_OK;
+}
+int srl_lio_run_measurement_image(srl_lio *h, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                  const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
+                                  const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_replay_result *out,
+                                  srl_image_process_result *image_out) {
+    if (image_out) std::memset(image_out, 0, sizeof *image_out);
+    if (!raw_bgr) return srl_lio_run_measurement(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, out);
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || rows < 1 || cols < 1 || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    if (!h->image_options_set) { h->err = "srl_lio_run_measurement_image: no options (srl_lio_image_set_options)"; return SRL_ERR_BAD_ARG; }
+    { const int rc = image_install_steps(h); if (rc != SRL_OK) return rc; }
+    lioOptimization &L = *h->lio;
+    int image_rc = SRL_OK;
+    std::string image_err;
+    L.camera_half = [&](cloudFrame *p_frame) {
+        cameraState &c = h->camera;
+        if (L.all_cloud_frame.size() < 3) {               // :1053-1061
+            c.fx = h->vio.camera_intrinsic(0, 0); c.fy = h->vio.camera_intrinsic(1, 1);
+            c.cx = h->vio.camera_intrinsic(0, 2); c.cy = h->vio.camera_intrinsic(1, 2);
+            c.R_imu_camera = h->vio.R_imu_camera; c.t_imu_camera = h->vio.t_imu_camera;
+        }                                                 // :1062-1071: else the frame's before, which the handle's camera state still holds
+        c.rotation = p_frame->p_state->rotation; c.translation = p_frame->p_state->translation;
+        c.q_world_camera = srl::Quat::fromRotationMatrix(c.rotation.toRotationMatrix() * c.R_imu_camera);      // :1073-1074
+        c.t_world_camera = c.rotation.toRotationMatrix() * c.t_imu_camera + c.translation;
+        imageFrame f;                                     // :1077-1083
+        f.rgb_image = raw_bgr; f.image_rows = rows; f.image_cols = cols; f.row_stride_bytes = row_stride_bytes;
+        f.time_sweep_end = p_frame->time_sweep_end; f.frame_id = p_frame->frame_id;
+        try { image_rc = h->vio.process(c, f, L.number_of_new_visited_voxel, image_out); }
+        catch (const std::exception &e) { image_rc = SRL_ERR_HIP; image_err = e.what(); }
+        if (image_rc == SRL_OK) L.time_last_process = h->vio.time_last_process;
+    };
+    const bool rendering_before = L.to_rendering;
+    L.to_rendering = true;
+    const int rc = srl_lio_run_measurement(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, out);
+    L.to_rendering = rendering_before;
+    L.camera_half = nullptr;
+    if (rc != SRL_OK) return rc;
+    if (image_rc != SRL_OK) {
+        const char *m = L.context() ? srl_last_error(L.context()) : "";
+        h->err = !image_err.empty() ? image_err : (m && *m ? m : "the camera frame of srl_lio_run_measurement_image failed");
+    }
+    return image_rc;
+}
+int srl_lio_image_time_last_process(srl_lio *h, double *time_last_process) {
+    if (!h || !time_last_process) return SRL_ERR_BAD_ARG;
+    *time_last_process = h->lio->time_last_process;
+    return SRL_OK;
 }
 }  // extern "C"

@@ -16,6 +16,11 @@ struct SrlImagePrep {
     unsigned char *d_undist = nullptr, *d_gray = nullptr, *d_y = nullptr, *d_crcb = nullptr;      // 3, 1, 1, 2 bytes per pixel
     unsigned char *d_lut = nullptr;                             // [plane][ty][tx][256]: plane 0 gray, 1 Y
     unsigned char *d_gray_eq = nullptr, *d_bgr_eq = nullptr;    // the two results
+    // srl_image_prepare_resized: a frame of another size is uploaded into src and resized into raw.d
+    SrlImagePair src;                                           // src_rows x src_cols x 3, rows packed; comes with the first such frame
+    int *d_ofs_x = nullptr, *d_ofs_y = nullptr;                 // srl_image_resize_build_tables per column and per row of the preparer's size
+    unsigned *d_coef_x = nullptr, *d_coef_y = nullptr;          // (coef[2 d], coef[2 d + 1]) as one dword
+    int tab_rows = 0, tab_cols = 0;                             // the source size the tables on the device are for (0: none yet)
 };
 
 // the refusals of the preparer's entry points and of srl_flow_track_prepared: no preparer, no image yet; more than one rank

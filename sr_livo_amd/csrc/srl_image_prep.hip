@@ -4,6 +4,11 @@
 // equality with its bytes.  All arithmetic is integer except CLAHE's look-up scale and its bilinear blend, which are plain IEEE FP32
 // (-ffp-contract=off, no atomics on floats): the same input gives the same bytes, and they equal a NumPy restatement bitwise.
 //
+//   k_resize_bgr  only behind srl_image_prepare_resized, and only for a frame of another size than the preparer's: four destination
+//                 pixels per lane as below, each from its two source columns and two source rows through the tables of
+//                 srl_image_resize_build_tables (device memory, rebuilt when the source size changes) -- or, at exactly half the size,
+//                 the 2 x 2 box mean.  Integer only.  It writes where an upload of the preparer's size lands, so the three kernels below
+//                 read the resized frame where they read the uploaded one.
 //   k_prep_pixel  four consecutive pixels (of the image taken as one flat array) per lane, so that every store is an aligned dword
 //                 whatever the width: reads map1 / map2 (16 + 8 bytes per lane) and up to four BGR neighbours per pixel, writes undist
 //                 (12 bytes), gray, Y (4 each) and CrCb (8).  The planes are allocated for a multiple of four pixels: the last lane's
@@ -18,7 +23,8 @@
 //
 // Bounds: a source neighbour is read only inside 0 <= y < rows, 0 <= x < cols (anything else contributes 0).  A tile reads extended
 // coordinates below cols + T and rows + T, reflected to >= cols - 1 - T and rows - 1 - T: create refuses rows <= T and cols <= T.  LUT
-// indices are clamped to 0 ... T - 1 by the specification itself.
+// indices are clamped to 0 ... T - 1 by the specification itself.  The resize reads source columns ofs and min(ofs + 1, src_cols - 1) with
+// ofs clamped to 0 ... src_cols - 1 (the builder's own range), rows alike; at half the size columns 2 x, 2 x + 1 <= 2 cols - 1.
 #include "srl_image_prep.h"
 #include "srl_color_map.h"
 #include "../../include/srlivo_hip_debug.h"
@@ -81,6 +87,54 @@ __device__ __forceinline__ void prep_first(const PrepDims &D, int g, int *x, int
 __device__ __forceinline__ void prep_step(const PrepDims &D, int *x, int *y) {
     if (++*x == D.cols) { *x = 0; ++*y; }
     if (*y >= D.rows) { *y = D.rows - 1; *x = D.cols - 1; }
+}
+
+struct PrepResizeArgs { PrepDims D; int src_rows, src_cols; };               // D: the destination, the preparer's size
+
+// HALF: src = 2 x dst in both directions, the 2 x 2 box mean; the tables are not read
+template <bool HALF>
+__global__ void __launch_bounds__(256) k_resize_bgr(const unsigned char *__restrict__ src, const int *__restrict__ ofs_x, const unsigned *__restrict__ coef_x,
+                                                     const int *__restrict__ ofs_y, const unsigned *__restrict__ coef_y, unsigned *__restrict__ dst,
+                                                     PrepResizeArgs A, int ngroups) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= ngroups) return;
+    int x, y;
+    prep_first(A.D, g, &x, &y);
+    const size_t down = (size_t)A.src_cols * 3;
+    unsigned ub[12];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int x0, x1, y0, y1, a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+        if (HALF) {
+            x0 = 2 * x; x1 = x0 + 1; y0 = 2 * y; y1 = y0 + 1;
+        } else {
+            const unsigned cx = coef_x[x], cy = coef_y[y];                      // (coef[2 d], coef[2 d + 1]) as one dword
+            a0 = (int)(cx & 0xFFFFu); a1 = (int)(cx >> 16); b0 = (int)(cy & 0xFFFFu); b1 = (int)(cy >> 16);
+            x0 = ofs_x[x]; y0 = ofs_y[y];
+            x0 = x0 < 0 ? 0 : (x0 > A.src_cols - 1 ? A.src_cols - 1 : x0);      // never taken (the builder's range); keeps the read inside
+            y0 = y0 < 0 ? 0 : (y0 > A.src_rows - 1 ? A.src_rows - 1 : y0);
+            x1 = x0 + 1 < A.src_cols ? x0 + 1 : A.src_cols - 1;
+            y1 = y0 + 1 < A.src_rows ? y0 + 1 : A.src_rows - 1;
+        }
+        const unsigned char *r0 = src + (size_t)y0 * down, *r1 = src + (size_t)y1 * down;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const int s00 = r0[3 * x0 + ch], s01 = r0[3 * x1 + ch], s10 = r1[3 * x0 + ch], s11 = r1[3 * x1 + ch];
+            int v;
+            if (HALF) {
+                v = (s00 + s01 + s10 + s11 + 2) >> 2;
+            } else {
+                const int h0 = s00 * a0 + s01 * a1, h1 = s10 * a0 + s11 * a1;
+                v = ((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2;
+                v = (v > 1023 ? 1023 : v) >> 2;                                 // min(255, v >> 2), the clamp first as in prep_sat8_descale14
+            }
+            ub[3 * k + ch] = (unsigned)v;
+        }
+        prep_step(A.D, &x, &y);
+    }
+    dst[3 * (size_t)g] = ub[0] | ub[1] << 8 | ub[2] << 16 | ub[3] << 24;
+    dst[3 * (size_t)g + 1] = ub[4] | ub[5] << 8 | ub[6] << 16 | ub[7] << 24;
+    dst[3 * (size_t)g + 2] = ub[8] | ub[9] << 8 | ub[10] << 16 | ub[11] << 24;
 }
 
 __global__ void __launch_bounds__(256) k_prep_pixel(const unsigned char *__restrict__ raw, const uint4 *__restrict__ map1, const uint2 *__restrict__ map2,
@@ -228,7 +282,7 @@ __global__ void __launch_bounds__(256) k_prep_apply(const unsigned *__restrict__
     bgr_eq[3 * (size_t)g + 2] = ub[8] | ub[9] << 8 | ub[10] << 16 | ub[11] << 24;
 }
 
-// the maps, the five intermediate planes, the LUT and the two results out of d_block (null: only measured); returns the block's size
+// the maps, the five intermediate planes, the LUT, the two results and the resize's tables out of d_block (null: only measured); returns the block's size
 size_t prep_layout(SrlImagePrep *p) {
     const size_t npix4 = ((size_t)p->rows * (size_t)p->cols + 3) / 4 * 4;
     SrlCarve c{p->d_block};
@@ -236,11 +290,14 @@ size_t prep_layout(SrlImagePrep *p) {
     p->d_undist = c.take<unsigned char>(npix4 * 3); p->d_gray = c.take<unsigned char>(npix4); p->d_y = c.take<unsigned char>(npix4);
     p->d_crcb = c.take<unsigned char>(npix4 * 2); p->d_lut = c.take<unsigned char>((size_t)2 * p->T * p->T * 256);
     p->d_gray_eq = c.take<unsigned char>(npix4); p->d_bgr_eq = c.take<unsigned char>(npix4 * 3);
+    p->d_ofs_x = c.take<int>((size_t)p->cols); p->d_coef_x = c.take<unsigned>((size_t)p->cols);
+    p->d_ofs_y = c.take<int>((size_t)p->rows); p->d_coef_y = c.take<unsigned>((size_t)p->rows);
     return c.at;
 }
 
 void prep_free(SrlImagePrep *p) {
     p->raw.release();
+    p->src.release();
     if (p->d_block) hipFree(p->d_block);
 }
 
@@ -332,20 +389,13 @@ extern "C" int srl_image_prep_destroy(srl_ctx *ctx) {
     return SRL_OK;
 }
 
-extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_image_prep_info *info) {
-    if (info) std::memset(info, 0, sizeof *info);
-    if (!ctx || !raw_bgr) return SRL_ERR_BAD_ARG;
-    { const int rc = srl_prep_need(ctx, false); if (rc) return rc; }
-    SrlImagePrep *p = ctx->prep;
-    if (rows != p->rows || cols != p->cols) { ctx->err = "image preparer: the image size differs from the preparer's"; return SRL_ERR_BAD_ARG; }
-    if (row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
-    { const int rc = srl_prep_one_rank(ctx); if (rc) return rc; }
-    SRL_DISARM(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+namespace {
+
+// the three kernels over the frame in p->raw.d (uploaded, or resized into it), the hand-over to the colour map and the wait
+int prep_chain(srl_ctx *ctx, SrlImagePrep *p, srl_image_prep_info *info) {
     hipStream_t st = ctx->stream;
+    const int rows = p->rows, cols = p->cols;
     const size_t npix = (size_t)rows * (size_t)cols;
-    // every call ends synchronised, so the staging block is free
-    { const int rc = p->raw.upload(ctx, raw_bgr, rows, (size_t)cols * 3, row_stride_bytes); if (rc) return rc; }
     const int ngroups = (int)((npix + 3) / 4);
     const unsigned nb = (unsigned)((ngroups + 255) / 256);
     const PrepDims D = {rows, cols, (int)npix};
@@ -373,6 +423,94 @@ extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows,
     p->have_image = true;
     prep_info(p, installed, info);
     return SRL_OK;
+}
+
+// the tables of a source size on the device: built at its first use, rebuilt when it changes
+int prep_resize_tables(srl_ctx *ctx, SrlImagePrep *p, int src_rows, int src_cols) {
+    if (p->tab_rows == src_rows && p->tab_cols == src_cols) return SRL_OK;
+    const int len[2] = {p->cols, p->rows}, from[2] = {src_cols, src_rows};
+    int *d_ofs[2] = {p->d_ofs_x, p->d_ofs_y};
+    unsigned *d_coef[2] = {p->d_coef_x, p->d_coef_y};
+    p->tab_rows = p->tab_cols = 0;
+    for (int k = 0; k < 2; k++) {
+        std::vector<int32_t> ofs((size_t)len[k]);
+        std::vector<int16_t> coef((size_t)len[k] * 2);
+        { const int rc = srl_image_resize_build_tables(from[k], len[k], ofs.data(), coef.data()); if (rc) return rc; }
+        // (pageable sources: the copies are made before the calls return; the last call ended synchronised)
+        HIPCHK(ctx, hipMemcpy(d_ofs[k], ofs.data(), ofs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(d_coef[k], coef.data(), coef.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    }
+    p->tab_rows = src_rows; p->tab_cols = src_cols;
+    return SRL_OK;
+}
+
+}  // namespace
+
+extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_image_prep_info *info) {
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!ctx || !raw_bgr) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_prep_need(ctx, false); if (rc) return rc; }
+    SrlImagePrep *p = ctx->prep;
+    if (rows != p->rows || cols != p->cols) { ctx->err = "image preparer: the image size differs from the preparer's"; return SRL_ERR_BAD_ARG; }
+    if (row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_prep_one_rank(ctx); if (rc) return rc; }
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // every call ends synchronised, so the staging block is free
+    { const int rc = p->raw.upload(ctx, raw_bgr, rows, (size_t)cols * 3, row_stride_bytes); if (rc) return rc; }
+    return prep_chain(ctx, p, info);
+}
+
+extern "C" int srl_image_resize_build_tables(int src_len, int dst_len, int32_t *ofs, int16_t *coef) {
+    if (src_len < 1 || dst_len < 1 || !ofs || !coef) return SRL_ERR_BAD_ARG;
+    const double scale = (double)src_len / dst_len;
+    for (int d = 0; d < dst_len; d++) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s = (int)std::floor(f);
+        f = f - (float)s;
+        if (s < 0) { s = 0; f = 0.0f; }
+        if (s >= src_len - 1) { s = src_len - 1; f = 0.0f; }
+        ofs[d] = s;
+        coef[2 * d] = (int16_t)std::nearbyint((1.0f - f) * 2048.0f);          // round to nearest even (the default mode)
+        coef[2 * d + 1] = (int16_t)std::nearbyint(f * 2048.0f);
+    }
+    return SRL_OK;
+}
+
+extern "C" int srl_image_prepare_resized(srl_ctx *ctx, const uint8_t *raw_bgr, int src_rows, int src_cols, int64_t row_stride_bytes, srl_image_prep_info *info) {
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!ctx || !raw_bgr) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_prep_need(ctx, false); if (rc) return rc; }
+    SrlImagePrep *p = ctx->prep;
+    if (src_rows < 1 || src_cols < 1 || src_rows > SRL_FLOW_MAX_EXTENT || src_cols > SRL_FLOW_MAX_EXTENT || (int64_t)src_rows * src_cols > SRL_COLOR_IMAGE_MAX_PIXELS) {
+        ctx->err = "image preparer: a source frame of 1 ... 16384 rows and columns and at most SRL_COLOR_IMAGE_MAX_PIXELS pixels";
+        return SRL_ERR_BAD_ARG;
+    }
+    if (row_stride_bytes < (int64_t)src_cols * 3) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_prep_one_rank(ctx); if (rc) return rc; }
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (src_rows == p->rows && src_cols == p->cols) {          // the preparer's own size: srl_image_prepare, no resize kernel
+        { const int rc = p->raw.upload(ctx, raw_bgr, src_rows, (size_t)src_cols * 3, row_stride_bytes); if (rc) return rc; }
+        return prep_chain(ctx, p, info);
+    }
+    const bool half = src_cols == 2 * p->cols && src_rows == 2 * p->rows;
+    if (!half) { const int rc = prep_resize_tables(ctx, p, src_rows, src_cols); if (rc) return rc; }
+    const size_t src_bytes = (size_t)src_rows * (size_t)src_cols * 3;
+    { const int rc = p->src.reserve(ctx, src_bytes, src_bytes); if (rc) return rc; }
+    { const int rc = p->src.upload(ctx, raw_bgr, src_rows, (size_t)src_cols * 3, row_stride_bytes); if (rc) return rc; }
+    const size_t npix = (size_t)p->rows * (size_t)p->cols;
+    const int ngroups = (int)((npix + 3) / 4);
+    const unsigned nb = (unsigned)((ngroups + 255) / 256);
+    PrepResizeArgs RA;
+    RA.D = {p->rows, p->cols, (int)npix}; RA.src_rows = src_rows; RA.src_cols = src_cols;
+    if (half)
+        hipLaunchKernelGGL(k_resize_bgr<true>, dim3(nb), dim3(256), 0, ctx->stream, p->src.d, p->d_ofs_x, p->d_coef_x, p->d_ofs_y, p->d_coef_y,
+                           reinterpret_cast<unsigned *>(p->raw.d), RA, ngroups);
+    else
+        hipLaunchKernelGGL(k_resize_bgr<false>, dim3(nb), dim3(256), 0, ctx->stream, p->src.d, p->d_ofs_x, p->d_coef_x, p->d_ofs_y, p->d_coef_y,
+                           reinterpret_cast<unsigned *>(p->raw.d), RA, ngroups);
+    return prep_chain(ctx, p, info);
 }
 
 extern "C" int srl_image_prep_download(srl_ctx *ctx, int which, uint8_t *out, int64_t row_stride_bytes) {
@@ -406,5 +544,18 @@ extern "C" int srl_image_prep_download_stage(srl_ctx *ctx, int stage, uint8_t *o
     const unsigned char *src = stage == SRL_PREP_STAGE_UNDIST ? p->d_undist : stage == SRL_PREP_STAGE_GRAY ? p->d_gray
                                : p->d_lut + (stage == SRL_PREP_STAGE_LUT_Y ? lut_bytes : 0);
     HIPCHK(ctx, hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
+    return SRL_OK;
+}
+
+extern "C" int srl_image_prep_download_resized(srl_ctx *ctx, uint8_t *out, int64_t capacity) {
+    if (!ctx || !out) return SRL_ERR_BAD_ARG;
+    { const int rc = srl_prep_need(ctx, true); if (rc) return rc; }
+    SrlImagePrep *p = ctx->prep;
+    const size_t need = (size_t)p->rows * (size_t)p->cols * 3;
+    if (capacity < (int64_t)need) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(out, p->raw.d, need, hipMemcpyDeviceToHost));
     return SRL_OK;
 }

@@ -781,6 +781,57 @@ int srl_frame_commit_report(srl_ctx *ctx, const double q[4], const double t[3], 
  * soon as world_out (if asked for) has arrived; the passes of the next sweep are ordered behind the insertion on the context's stream,
  * and the map's totals are brought up to date by the next call that reads them (srl_map_size, srl_map_download, the next insertion). */
 
+/* ------------------------------------------------------------------ Livox messages -> device point queue -> sweeps cut at image times
+ * (csrc/srl_points.hip).  Replaces cloudProcessing::livoxHandler (cloudProcessing.cpp:125-214), the point side of getMeasurements
+ * (lioOptimization.cpp:672-680, :719-723, :759-763) and makePointTimestamp (:786-819).  The image and IMU queues and the policy of
+ * getMeasurements stay with the caller, who is given the three numbers the policy reads of point_buffer (srl_points_info).
+ *
+ * srl_livox_decode: points = msg->points.data() (srl_livox_point is the in-memory layout of livox_ros_driver::CustomPoint), message index i
+ *   from 1 (point 0 is never output).  Valid iff line < n_scans; |x|, |y|, |z| (float magnitude, compared as double) each not > 1e8;
+ *   x > 0.7; not (x > 2.0 and (tag & 0x03 or tag & 0x0C)); and one of fabsf(x_i - x_{i-1}), fabsf(y_i - y_{i-1}), fabsf(z_i - z_{i-1}) > 1e-7
+ *   (float subtraction against MESSAGE index i - 1, compared as double).  relative_time = double(offset_time) * time_unit_scale; timestamp =
+ *   relative_time / 1000.0 + header_stamp.  The valid points are ordered by relative_time ascending, TIES BY MESSAGE INDEX (a stable sort:
+ *   the reference's std::sort leaves ties in an order of its library's own; the two agree wherever no two valid points share an
+ *   offset_time).  Sorted position j is picked iff (j + 1) % point_filter_num == 0; a picked point is appended to the queue iff
+ *   (x x + y y) + z z > blind blind in FP64.  last_end_time = header_stamp + (relative_time of the last sorted valid point) / 1000.0; NaN
+ *   when the message has no valid point (the reference reads .back() of an empty vector there).  first / last_timestamp: of the appended
+ *   points, NaN when none.  The same message gives the same bytes, call after call.
+ *   Synchronous; a page-locked `points` goes by DMA.  Before a device is touched: NULL ctx / opts, point_num < 0, NULL points with
+ *   point_num > 0, point_filter_num < 1, n_scans < 0, time_unit_scale not > 0 (NaN included), NaN blind or header_stamp: SRL_ERR_BAD_ARG;
+ *   point_num > 2^20: SRL_ERR_UNSUPPORTED; more than one rank: SRL_ERR_UNSUPPORTED.  report may be NULL.  Cancels an armed launch.
+ * srl_time_unit_scale: cloudProcessing::setTimeUnit's float literal widened to double (unit 0 s: 1.e3f, 1 ms: 1.f, 2 us: 1.e-3f, 3 ns:
+ *   1.e-6f, anything else: 1.f) -- 1.e-6f is not 1e-6.
+ * The queue is a FIFO in HBM the context owns (grown by doubling; the order never changes).  srl_points_info: its size and the timestamps
+ *   of its front and back (NaN when empty), from what the decode and cut reports already returned -- no device synchronisation.
+ * srl_points_cut: while (front().timestamp < t) pop -- the longest PREFIX whose every timestamp is < t; it stops at the first element that
+ *   fails even if later ones would pass.  An empty queue, or every element passing: everything is cut.  The cut points stay in HBM as THE
+ *   RESIDENT CUT until the next cut.  report (may be NULL): the count and the new front timestamp (NaN: the queue is empty now).
+ * srl_frame_undistort_cut: makePointTimestamp on the resident cut -- relative = timestamp - time_begin; alpha = relative / (time_end -
+ *   time_begin); relative *= 1000.0; with point_time_enable every point is kept and alpha > 1.0 becomes 1.0 - 1e-5, otherwise points with
+ *   timestamp > time_end or < time_begin are removed (stable, no clamp) -- then srl_frame_undistort's kernel with time_frame_begin =
+ *   time_begin and imu_point_in = zeros.  *n = the points that remain.  The corrected sweep is where srl_frame_subsample, srl_frame_take and
+ *   srl_frame_take_subsampled look for it.  SRL_MC_IMU: the interval of every point is found on the device (the smallest k with t <
+ *   stamp[k + 1] + 1e-6, accepted iff t > stamp[k] - 1e-6; the first point without one and every point behind it get none) where the
+ *   rewritten times and the state stamps are non-decreasing; otherwise the times are downloaded and the walk is replayed on the host as
+ *   in srl_frame_undistort (srl_debug_points_fallbacks counts these) -- the result is the same.
+ * srl_frame_point_times: timestamp, relative_time (ms) and alpha_time of the points index[0..m) of that sweep (each output optional).
+ * SRL_ERR_NO_SWEEP: srl_points_info / _clear / _cut before the first srl_livox_decode; srl_frame_undistort_cut without a cut;
+ *   srl_frame_point_times without a sweep undistorted from a cut. */
+typedef struct srl_livox_point { uint32_t offset_time; float x, y, z; uint8_t reflectivity, tag, line, pad; } srl_livox_point;   /* 20 B */
+typedef struct srl_livox_opts { int32_t n_scans, reserved0; double time_unit_scale; double blind; int32_t point_filter_num, reserved1; } srl_livox_opts;
+typedef struct srl_livox_report { int32_t valid, picked, appended, reserved; double last_end_time, first_timestamp, last_timestamp; } srl_livox_report;
+typedef struct srl_points_cut_report { int32_t count, reserved; double front_timestamp; } srl_points_cut_report;
+double srl_time_unit_scale(int unit);
+int srl_livox_decode(srl_ctx *ctx, const srl_livox_point *points, int point_num, double header_stamp, const srl_livox_opts *opts,
+                     srl_livox_report *report);
+int srl_points_info(srl_ctx *ctx, int *size, double *front_timestamp, double *back_timestamp);
+int srl_points_clear(srl_ctx *ctx);
+int srl_points_cut(srl_ctx *ctx, double t, srl_points_cut_report *report);
+int srl_frame_undistort_cut(srl_ctx *ctx, double time_begin, double time_end, int point_time_enable, const srl_imu_state *imu_states,
+                            int n_states, int motion_compensation, const double R_il[9], const double t_il[3], int *n);
+int srl_frame_point_times(srl_ctx *ctx, const int32_t *index, int m, double *timestamp /* m or NULL */, double *relative_time /* m or NULL */,
+                          double *alpha_time /* m or NULL */);
+
 /* ------------------------------------------------------------------ hot path
  * replaces: lioOptimization::buildPlaneResiduals (optimize.cpp:18-131) incl. searchNeighbors
  * (:365-426), computeNeighborhoodDistribution (:316-353), and the H_x^T H_x / H_x^T h contraction

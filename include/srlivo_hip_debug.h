@@ -162,6 +162,22 @@ typedef struct srl_debug_consensus_info { int32_t model, hypotheses, n, slots, u
 int srl_debug_consensus_download(srl_ctx *ctx, srl_debug_consensus_info *info, int32_t *usable, int64_t point_capacity, int32_t *samples,
                                  double *models, int32_t *counts, int64_t hypothesis_capacity);
 
+/* Read-backs of the device point queue (csrc/srl_points.hip), for tests and for a caller's own fallback.  Each array is optional; *n (may
+ * be NULL) receives the record count, and nothing is copied when capacity < count (SRL_ERR_BAD_ARG, *n set: ask again).
+ * srl_points_queue_download: the queue front to back -- raw_point (n x 3), relative_time (ms within its message), timestamp.
+ * srl_points_cut_download: the resident cut of the last srl_points_cut, same records (relative_time is still the message's: the rewrite
+ *   belongs to srl_frame_undistort_cut).  SRL_ERR_NO_SWEEP without a queue / a cut.
+ * srl_debug_points_fallbacks: how often srl_frame_undistort_cut replayed the IMU interval walk on the host because the rewritten times of
+ *   the cut or the state stamps were not non-decreasing. */
+int srl_points_queue_download(srl_ctx *ctx, double *raw_xyz, double *relative_time, double *timestamp, int capacity, int *n);
+int srl_points_cut_download(srl_ctx *ctx, double *raw_xyz, double *relative_time, double *timestamp, int capacity, int *n);
+int srl_debug_points_fallbacks(srl_ctx *ctx, int64_t *count);
+/* The undistorted sweep as srl_frame_undistort or srl_frame_undistort_cut left it in HBM, all n points (each array optional, capacity as
+ * above): the uncorrected points (what srl_frame_subsample keys on), imu_point, the corrected raw_point, and the IMU interval of every
+ * point (-1: the walk never reached it; meaningful after a call in SRL_MC_IMU mode only). */
+int srl_debug_undistorted_download(srl_ctx *ctx, double *uncorrected_xyz, double *imu_point, double *corrected_xyz, int32_t *interval, int capacity,
+                                   int *n);
+
 #ifdef __cplusplus
 }
 #endif

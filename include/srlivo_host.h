@@ -216,6 +216,27 @@ int srl_lio_run_measurement(srl_lio *lio, double time_frame, const double *imu_t
 /* point3D::raw_point / ::point / ::imu_point of the newest frame in all_cloud_frame (any pointer may be NULL) */
 int srl_lio_last_frame(srl_lio *lio, int capacity, double *raw_point, double *point, double *imu_point, int *n);
 
+/* The point side of the node on the device point queue (srlivo_hip.h: srl_livox_decode, srl_points_cut, srl_frame_undistort_cut).
+ * srl_lio_set_lidar_options: cloudProcessing's N_SCANS, time_unit_scale (srl_time_unit_scale), blind and point_filter_num; refused like
+ *   srl_livox_decode refuses them.
+ * srl_lio_feed_livox: lioOptimization::livoxHandler (lioOptimization.cpp:593-601): the message is decoded into the handle's queue;
+ *   last_time_lidar = header_stamp, and cloud_pro->last_end_time follows the report (a message without a valid point leaves it as it
+ *   was).  The reference asserts header_stamp > last_time_lidar; here such a message is refused with SRL_ERR_BAD_ARG and nothing is queued,
+ *   as is a feed before the options are set.
+ * srl_lio_points_info: srl_points_info plus the two times above (every output optional; the two times are written even when the queue does
+ *   not exist yet and the call returns SRL_ERR_NO_SWEEP).
+ * srl_lio_run_measurement_queued: srl_lio_run_measurement with the sweep cut from the queue at time_cut (while (front().timestamp <
+ *   time_cut) pop, lioOptimization.cpp:719-723 / :759-763) in place of pts_raw / pts_timestamp: the cut points are rewritten, undistorted and
+ *   sub-sampled where they lie, and only the kept points' fields come back.  The same results bit for bit as srl_lio_run_measurement on
+ *   the same points.  Needs srl_lio_set_device_subsample(1) and voxel_size > 0: otherwise SRL_ERR_UNSUPPORTED and the queue is left uncut.
+ *   An empty cut is the reference's "no lidar points, no Measurements element": SRL_OK, out->processed = 0, nothing changes (the IMU
+ *   samples are not consumed either).  There is no _image twin yet: srl_lio_run_measurement_image's body is not a forward. */
+int srl_lio_set_lidar_options(srl_lio *lio, const srl_livox_opts *opts);
+int srl_lio_feed_livox(srl_lio *lio, const srl_livox_point *points, int point_num, double header_stamp, srl_livox_report *report);
+int srl_lio_points_info(srl_lio *lio, int *size, double *front_timestamp, double *back_timestamp, double *last_time_lidar, double *last_end_time);
+int srl_lio_run_measurement_queued(srl_lio *lio, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                   double time_cut, double time_sweep_begin, double time_sweep_offset, srl_replay_result *out);
+
 /* Frame-resident form of optimize() + the map update that follows it in stateEstimation
  * (lioOptimization.cpp:1027,1051): the raw frame (n x 3) is uploaded once; keypoints are selected on the device
  * from point = R(q)(R_il raw + t_il) + t with the PRIOR pose in state_io (what point3D::point holds when

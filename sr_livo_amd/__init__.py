@@ -16,4 +16,6 @@ from .capi import (  # noqa: F401
     SRL_CONSENSUS_MAX_POINTS, SRL_CONSENSUS_MAX_HYPOTHESES,
     ImagePrep, ImagePrepOpts, ImagePrepInfo, default_image_prep_opts, image_prep_build_map, image_resize_build_tables,
     ImageProcessOpts, ImageProcessResult, ImageProcessSteps,
+    LivoxOpts, LivoxReport, PointsCutReport, LIVOX_POINT_DTYPE, livox_opts, time_unit_scale,
+    TIME_UNIT_SEC, TIME_UNIT_MS, TIME_UNIT_US, TIME_UNIT_NS,
 )

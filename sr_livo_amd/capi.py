@@ -272,6 +272,27 @@ class ReplayResult(C.Structure):
 
 MC_IMU, MC_CONSTANT_VELOCITY, MC_NONE = 0, 1, 2
 
+
+class LivoxOpts(C.Structure):
+    """srl_livox_opts: cloudProcessing's N_SCANS, time_unit_scale, blind, point_filter_num"""
+    _fields_ = [("n_scans", C.c_int32), ("reserved0", C.c_int32), ("time_unit_scale", C.c_double), ("blind", C.c_double),
+                ("point_filter_num", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class LivoxReport(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("picked", C.c_int32), ("appended", C.c_int32), ("reserved", C.c_int32), ("last_end_time", C.c_double),
+                ("first_timestamp", C.c_double), ("last_timestamp", C.c_double)]
+
+
+class PointsCutReport(C.Structure):
+    _fields_ = [("count", C.c_int32), ("reserved", C.c_int32), ("front_timestamp", C.c_double)]
+
+
+# srl_livox_point = livox_ros_driver::CustomPoint in memory (20 B)
+LIVOX_POINT_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("reflectivity", "u1"), ("tag", "u1"),
+                              ("line", "u1"), ("pad", "u1")])
+TIME_UNIT_SEC, TIME_UNIT_MS, TIME_UNIT_US, TIME_UNIT_NS = 0, 1, 2, 3
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p)
 PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(Frame), C.POINTER(IcpOpts), C.POINTER(NormalEq), C.c_void_p)
@@ -564,6 +585,21 @@ def load_library():
         "srl_lio_image_oft": ([p], C.c_void_p),
         "srl_lio_image_candidates": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_image_time_last_process": ([p, C.POINTER(C.c_double)], C.c_int),
+        "srl_time_unit_scale": ([C.c_int], C.c_double),
+        "srl_livox_decode": ([p, p, C.c_int, C.c_double, C.POINTER(LivoxOpts), C.POINTER(LivoxReport)], C.c_int),
+        "srl_points_info": ([p, C.POINTER(C.c_int), dp, dp], C.c_int),
+        "srl_points_clear": ([p], C.c_int),
+        "srl_points_cut": ([p, C.c_double, C.POINTER(PointsCutReport)], C.c_int),
+        "srl_points_queue_download": ([p, p, p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_points_cut_download": ([p, p, p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_debug_points_fallbacks": ([p, C.POINTER(C.c_int64)], C.c_int),
+        "srl_debug_undistorted_download": ([p, p, p, p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "srl_frame_undistort_cut": ([p, C.c_double, C.c_double, C.c_int, p, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int)], C.c_int),
+        "srl_frame_point_times": ([p, p, C.c_int, p, p, p], C.c_int),
+        "srl_lio_set_lidar_options": ([p, C.POINTER(LivoxOpts)], C.c_int),
+        "srl_lio_feed_livox": ([p, p, C.c_int, C.c_double, C.POINTER(LivoxReport)], C.c_int),
+        "srl_lio_points_info": ([p, C.POINTER(C.c_int), dp, dp, dp, dp], C.c_int),
+        "srl_lio_run_measurement_queued": ([p, C.c_double, p, p, p, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(ReplayResult)], C.c_int),
         "srl_grid_sampling": ([p, C.c_int, C.c_double, p, C.POINTER(C.c_int)], C.c_int),
         "srl_debug_tr1_order": ([p, C.c_int, p], C.c_int),
         "srl_debug_tr1_order_by_relation": ([p, C.c_int, p], C.c_int),
@@ -613,6 +649,33 @@ def default_opts(**kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def time_unit_scale(unit):
+    """srl_time_unit_scale: cloudProcessing::setTimeUnit's float literal widened to double (1.e-6f is not 1e-6)"""
+    return float(load_library().srl_time_unit_scale(int(unit)))
+
+
+def livox_opts(n_scans=6, time_unit=TIME_UNIT_NS, blind=0.01, point_filter_num=1, time_unit_scale_value=None):
+    """srl_livox_opts; the scale comes from srl_time_unit_scale(time_unit) unless given"""
+    o = LivoxOpts()
+    o.n_scans = int(n_scans)
+    o.time_unit_scale = float(time_unit_scale(time_unit) if time_unit_scale_value is None else time_unit_scale_value)
+    o.blind = float(blind)
+    o.point_filter_num = int(point_filter_num)
+    return o
+
+
+def _livox_points(points):
+    a = np.ascontiguousarray(points)
+    if a.dtype != LIVOX_POINT_DTYPE:
+        raise TypeError("Livox points must have LIVOX_POINT_DTYPE (the 20-byte CustomPoint record)")
+    return a
+
+
+def _livox_report_dict(r):
+    return dict(valid=r.valid, picked=r.picked, appended=r.appended, last_end_time=r.last_end_time, first_timestamp=r.first_timestamp,
+                last_timestamp=r.last_timestamp)
 
 
 def default_color_opts(**kw):
@@ -1329,6 +1392,77 @@ class Context:
         n = C.c_int()
         self._chk(self.lib.srl_frame_size(self.h, C.byref(n)), "srl_frame_size")
         return n.value
+
+    # --- Livox messages -> device point queue -> sweeps cut at image times
+    def livox_decode(self, points, header_stamp, opts, ok=()):
+        """srl_livox_decode: points = LIVOX_POINT_DTYPE records of one message.  Returns the report as a dict (with rc)."""
+        a = _livox_points(points)
+        r = LivoxReport()
+        rc = self._chk(self.lib.srl_livox_decode(self.h, _ptr(a), len(a), float(header_stamp), C.byref(opts), C.byref(r)), "srl_livox_decode", ok=ok)
+        return dict(_livox_report_dict(r), rc=rc)
+
+    def points_info(self):
+        """srl_points_info -> (size, front_timestamp, back_timestamp); no device synchronisation"""
+        n, f, b = C.c_int(), C.c_double(), C.c_double()
+        self._chk(self.lib.srl_points_info(self.h, C.byref(n), C.byref(f), C.byref(b)), "srl_points_info")
+        return n.value, f.value, b.value
+
+    def points_clear(self):
+        self._chk(self.lib.srl_points_clear(self.h), "srl_points_clear")
+
+    def points_cut(self, t):
+        """srl_points_cut: while (front().timestamp < t) pop -> (count, new front timestamp); the cut stays resident"""
+        r = PointsCutReport()
+        self._chk(self.lib.srl_points_cut(self.h, float(t), C.byref(r)), "srl_points_cut")
+        return r.count, r.front_timestamp
+
+    def _points_download(self, fn, what):
+        n = C.c_int()
+        self._chk(fn(self.h, None, None, None, 0, C.byref(n)), what, ok=(SRL_ERR_BAD_ARG,) )
+        m = n.value
+        raw = np.empty((m, 3)); rel = np.empty(m); ts = np.empty(m)
+        self._chk(fn(self.h, _ptr(raw), _ptr(rel), _ptr(ts), m, C.byref(n)), what)
+        return dict(raw=raw, relative_time=rel, timestamp=ts)
+
+    def points_queue_download(self):
+        """the queue front to back: dict(raw (n, 3), relative_time, timestamp)"""
+        return self._points_download(self.lib.srl_points_queue_download, "srl_points_queue_download")
+
+    def points_cut_download(self):
+        return self._points_download(self.lib.srl_points_cut_download, "srl_points_cut_download")
+
+    def points_fallbacks(self):
+        n = C.c_int64()
+        self._chk(self.lib.srl_debug_points_fallbacks(self.h, C.byref(n)), "srl_debug_points_fallbacks")
+        return n.value
+
+    def frame_undistort_cut(self, time_begin, time_end, point_time_enable, imu_states, mode, R_il=None, t_il=None):
+        """srl_frame_undistort_cut on the resident cut; returns n, the points the time rewrite kept"""
+        st = _f64(imu_states, (-1, 17))
+        R_il = _f64(np.eye(3) if R_il is None else R_il).ravel()
+        t_il = _f64(np.zeros(3) if t_il is None else t_il)
+        n = C.c_int()
+        self._chk(self.lib.srl_frame_undistort_cut(self.h, float(time_begin), float(time_end), int(bool(point_time_enable)), _ptr(st), len(st), int(mode),
+                                                   _dptr(R_il), _dptr(t_il), C.byref(n)), "srl_frame_undistort_cut")
+        return n.value
+
+    def undistorted_download(self):
+        """srl_debug_undistorted_download: dict(uncorrected, imu, raw (n, 3) each, interval (n,)) of the undistorted sweep in HBM"""
+        n = C.c_int()
+        self._chk(self.lib.srl_debug_undistorted_download(self.h, None, None, None, None, 0, C.byref(n)), "srl_debug_undistorted_download",
+                  ok=(SRL_ERR_BAD_ARG,))
+        m = n.value
+        unc = np.empty((m, 3)); imu = np.empty((m, 3)); raw = np.empty((m, 3)); seg = np.empty(m, dtype=np.int32)
+        self._chk(self.lib.srl_debug_undistorted_download(self.h, _ptr(unc), _ptr(imu), _ptr(raw), _ptr(seg), m, C.byref(n)),
+                  "srl_debug_undistorted_download")
+        return dict(uncorrected=unc, imu=imu, raw=raw, interval=seg)
+
+    def frame_point_times(self, index):
+        """srl_frame_point_times -> (timestamp, relative_time ms, alpha_time) of the points index[] of the sweep undistorted from the cut"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        ts = np.empty(len(idx)); rel = np.empty(len(idx)); al = np.empty(len(idx))
+        self._chk(self.lib.srl_frame_point_times(self.h, _ptr(idx), len(idx), _ptr(ts), _ptr(rel), _ptr(al)), "srl_frame_point_times")
+        return ts, rel, al
 
     def radix_sort_pairs(self, keys, bits):
         """test hook: the frame path's stable (key, position) sort over the low `bits` bits -> (keys_sorted, positions_sorted)"""
@@ -2242,6 +2376,36 @@ class Lio:
         return dict(rc=rc, processed=bool(out.processed), initialized=bool(out.initialized), index_frame=out.index_frame,
                     success=bool(out.success), num_residuals=out.num_residuals_used, iters=out.iterations, frame_points=out.frame_points,
                     keypoints=out.keypoints, points_added=out.points_added, state=np.array(out.state), image=img)
+
+    def set_lidar_options(self, opts):
+        """srl_lio_set_lidar_options: opts = livox_opts(...)"""
+        self._chk(self.lib.srl_lio_set_lidar_options(self.h, C.byref(opts)), "set_lidar_options")
+
+    def feed_livox(self, points, header_stamp):
+        """srl_lio_feed_livox (lioOptimization::livoxHandler): one message into the handle's device point queue; returns the report dict"""
+        a = _livox_points(points)
+        r = LivoxReport()
+        self._chk(self.lib.srl_lio_feed_livox(self.h, _ptr(a), len(a), float(header_stamp), C.byref(r)), "feed_livox")
+        return _livox_report_dict(r)
+
+    def points_info(self):
+        """srl_lio_points_info -> dict(size, front_timestamp, back_timestamp, last_time_lidar, last_end_time)"""
+        n = C.c_int()
+        f, b, tl, te = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.lib.srl_lio_points_info(self.h, C.byref(n), C.byref(f), C.byref(b), C.byref(tl), C.byref(te)), "points_info")
+        return dict(size=n.value, front_timestamp=f.value, back_timestamp=b.value, last_time_lidar=tl.value, last_end_time=te.value)
+
+    def run_measurement_queued(self, time_frame, imu_t, imu_acc, imu_gyr, time_cut, time_sweep_begin, time_sweep_offset,
+                               allow=(SRL_ERR_NOT_ENOUGH_RESIDUALS,)):
+        """srl_lio_run_measurement_queued: run_measurement with the sweep cut from the device point queue at time_cut"""
+        it = _f64(imu_t); ia = _f64(imu_acc, (-1, 3)); ig = _f64(imu_gyr, (-1, 3))
+        out = ReplayResult()
+        rc = self._chk(self.lib.srl_lio_run_measurement_queued(self.h, float(time_frame), _ptr(it), _ptr(ia), _ptr(ig), len(it), float(time_cut),
+                                                               float(time_sweep_begin), float(time_sweep_offset), C.byref(out)),
+                       "run_measurement_queued", ok=allow)
+        return dict(rc=rc, processed=bool(out.processed), initialized=bool(out.initialized), index_frame=out.index_frame,
+                    success=bool(out.success), num_residuals=out.num_residuals_used, iters=out.iterations, frame_points=out.frame_points,
+                    keypoints=out.keypoints, points_added=out.points_added, state=np.array(out.state))
 
     def last_frame(self):
         n = C.c_int()

@@ -716,16 +716,20 @@ void lioOptimization::makePointTimestamp(std::vector<point3D> &sweep, double tim
 cloudFrame *lioOptimization::buildFrame(std::vector<point3D> &cut_sweep, state *cur_state, double timestamp_begin, double timestamp_offset) {
     srl_ctx *ctx = voxel_map.ctx;
     if (!ctx) throw std::runtime_error("buildFrame: no HIP context (the product has no CPU path)");
-    std::vector<point3D> sweep(cut_sweep);
+    // the sweep cut from the device point queue (srl_lio_run_measurement_queued) never visits the host: cut_sweep is empty and unused
+    const bool queued = sweep_from_queue;
+    std::vector<point3D> sweep;
+    if (!queued) sweep = cut_sweep;
 
     const double time_sweep_begin = timestamp_begin;
     const double time_frame_begin = timestamp_begin;
-    makePointTimestamp(sweep, time_frame_begin, timestamp_begin + timestamp_offset);
+    if (!queued) makePointTimestamp(sweep, time_frame_begin, timestamp_begin + timestamp_offset);
 
     // device: distortFrameBy* + transformAllImuPoint over the whole sweep
-    const int n = (int)sweep.size();
+    int n = (int)sweep.size();
     const double sample_size = index_frame < init_num_frames ? init_voxel_size : voxel_size;
     const bool on_device = device_subsample && voxel_size > 0;      // (no sub-sample: the frame is the first shuffle's order of all n points)
+    if (queued && !on_device) throw std::runtime_error("buildFrame: a sweep from the point queue needs the device sub-sample");
     std::vector<double> raw((size_t)n * 3), rel((size_t)n), imu_in((size_t)n * 3), imu_out, raw_out;
     if (!on_device) { imu_out.resize((size_t)n * 3); raw_out.resize((size_t)n * 3); }
     for (int i = 0; i < n; i++) {
@@ -742,9 +746,13 @@ cloudFrame *lioOptimization::buildFrame(std::vector<point3D> &cut_sweep, state *
         st[k].quat[0] = imu_states[k].quat.w; st[k].quat[1] = imu_states[k].quat.x; st[k].quat[2] = imu_states[k].quat.y; st[k].quat[3] = imu_states[k].quat.z;
     }
     const int mode = motion_compensation == CONSTANT_VELOCITY ? SRL_MC_CONSTANT_VELOCITY : motion_compensation == IMU ? SRL_MC_IMU : SRL_MC_NONE;
-    check(ctx, srl_frame_undistort(ctx, raw.data(), rel.data(), imu_in.data(), n, st.data(), (int)st.size(), time_frame_begin, mode,
-                                   R_imu_lidar.a, t_imu_lidar.a, on_device ? nullptr : imu_out.data(), on_device ? nullptr : raw_out.data()),
-          "srl_frame_undistort");
+    if (queued)      // makePointTimestamp and the undistortion on the resident cut; n = what the rewrite kept
+        check(ctx, srl_frame_undistort_cut(ctx, time_frame_begin, timestamp_begin + timestamp_offset, point_time_enable ? 1 : 0, st.data(), (int)st.size(), mode,
+                                           R_imu_lidar.a, t_imu_lidar.a, &n), "srl_frame_undistort_cut");
+    else
+        check(ctx, srl_frame_undistort(ctx, raw.data(), rel.data(), imu_in.data(), n, st.data(), (int)st.size(), time_frame_begin, mode,
+                                       R_imu_lidar.a, t_imu_lidar.a, on_device ? nullptr : imu_out.data(), on_device ? nullptr : raw_out.data()),
+              "srl_frame_undistort");
 
     // the order: both shuffles on index arrays with the engine they share.  subSampleFrame keys on point3D::point, which still holds the
     // sensor-frame point here (cloudProcessing.cpp:143) -- what srl_frame_undistort received as raw_xyz
@@ -764,10 +772,17 @@ cloudFrame *lioOptimization::buildFrame(std::vector<point3D> &cut_sweep, state *
         std::shuffle(perm.begin(), perm.end(), seed);
         std::vector<double> f_raw((size_t)m * 3), f_imu((size_t)m * 3);
         check(ctx, srl_frame_take_subsampled(ctx, perm.data(), m, index.data(), f_raw.data(), f_imu.data()), "srl_frame_take_subsampled");
+        // the point3D time fields of the kept points are all the mirror needs of a sweep it never saw
+        std::vector<double> f_ts, f_rel, f_alpha;
+        if (queued) {
+            f_ts.resize((size_t)m); f_rel.resize((size_t)m); f_alpha.resize((size_t)m);
+            check(ctx, srl_frame_point_times(ctx, index.data(), m, f_ts.data(), f_rel.data(), f_alpha.data()), "srl_frame_point_times");
+        }
         releaseSweep();
         frame.resize((size_t)m);
         for (int k = 0; k < m; k++) {
-            frame[k] = sweep[index[k]];
+            if (queued) { frame[k].timestamp = f_ts[k]; frame[k].relative_time = f_rel[k]; frame[k].alpha_time = f_alpha[k]; }
+            else frame[k] = sweep[index[k]];
             for (int d = 0; d < 3; d++) { frame[k].imu_point[d] = f_imu[(size_t)k * 3 + d]; frame[k].raw_point[d] = f_raw[(size_t)k * 3 + d]; }
         }
     } else {

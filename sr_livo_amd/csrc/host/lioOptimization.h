@@ -154,6 +154,16 @@ public:
     void makePointTimestamp(std::vector<point3D> &sweep, double time_begin, double time_end);
     cloudFrame *buildFrame(std::vector<point3D> &cut_sweep, state *cur_state, double timestamp_begin, double timestamp_offset);
     bool device_subsample = true;
+    // The sweep of the next buildFrame is the resident cut of the device point queue (srl_points_cut), not cut_sweep: the time rewrite and
+    // the undistortion run on it where it lies (srl_frame_undistort_cut), the device sub-sample follows unchanged, and the point3D time
+    // fields of the kept points come back through srl_frame_point_times.  Set for one measurement by srl_lio_run_measurement_queued.
+    bool sweep_from_queue = false;
+    // cloudProcessing's options as srl_livox_decode reads them (setN_SCANS, setTimeUnit, setBlind, setPointFilterNum), and what
+    // lioOptimization::livoxHandler (lioOptimization.cpp:593-601) and cloudProcessing::livoxHandler keep between messages
+    srl_livox_opts lidar_options = {};                                   // (the reference has no defaults for three of the four)
+    bool lidar_options_set = false;
+    double last_time_lidar = -1.0;                                       // lioOptimization.cpp:383
+    double last_end_time = -1.0;                                         // cloudProcessing.cpp:9
     // optimize() on the frame buildFrame left resident in HBM
     optimizeSummary optimizeBuiltFrame(cloudFrame *p_frame, const icpOptions &cur_icp_options, double sample_voxel_size,
                                        std::vector<int> *keypoint_index = nullptr);

@@ -620,6 +620,66 @@ int srl_lio_run_measurement(srl_lio *h, double time_frame, const double *imu_t, 
     return SRL_OK;
 }
 
+// ---- the point side of the node: Livox messages into the device point queue, sweeps cut from it
+int srl_lio_set_lidar_options(srl_lio *h, const srl_livox_opts *o) {
+    if (!h || !o) return SRL_ERR_BAD_ARG;
+    if (o->point_filter_num < 1 || o->n_scans < 0 || !(o->time_unit_scale > 0.0) || std::isinf(o->time_unit_scale) || std::isnan(o->blind)) return SRL_ERR_BAD_ARG;
+    h->lio->lidar_options = *o;
+    h->lio->lidar_options_set = true;
+    return SRL_OK;
+}
+
+int srl_lio_feed_livox(srl_lio *h, const srl_livox_point *points, int point_num, double header_stamp, srl_livox_report *report) {
+    if (report) { std::memset(report, 0, sizeof *report); report->last_end_time = report->first_timestamp = report->last_timestamp = std::nan(""); }
+    if (!h || point_num < 0 || (point_num > 0 && !points)) return SRL_ERR_BAD_ARG;
+    lioOptimization &L = *h->lio;
+    if (!L.lidar_options_set) { h->err = "srl_lio_feed_livox: no options (srl_lio_set_lidar_options)"; return SRL_ERR_BAD_ARG; }
+    // lioOptimization.cpp:595: assert(msg->header.stamp.toSec() > last_time_lidar) -- here a refusal, and nothing is queued
+    if (!(header_stamp > L.last_time_lidar)) { h->err = "srl_lio_feed_livox: a message that is not newer than the last one"; return SRL_ERR_BAD_ARG; }
+    srl_ctx *ctx = L.context();
+    if (!ctx) { h->err = "host-only handle: no device, no point queue"; return SRL_ERR_NO_DEVICE; }
+    srl_livox_report r;
+    const int rc = srl_livox_decode(ctx, points, point_num, header_stamp, &L.lidar_options, &r);
+    if (rc != SRL_OK) { h->err = srl_last_error(ctx); return rc; }
+    L.last_time_lidar = header_stamp;                              // :600
+    if (r.valid > 0) L.last_end_time = r.last_end_time;            // cloudProcessing.cpp:213 (no valid point: .back() of an empty vector upstream; kept here)
+    if (report) *report = r;
+    return SRL_OK;
+}
+
+int srl_lio_points_info(srl_lio *h, int *size, double *front_timestamp, double *back_timestamp, double *last_time_lidar, double *last_end_time) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    lioOptimization &L = *h->lio;
+    if (last_time_lidar) *last_time_lidar = L.last_time_lidar;
+    if (last_end_time) *last_end_time = L.last_end_time;
+    srl_ctx *ctx = L.context();
+    if (!ctx) { h->err = "host-only handle: no device, no point queue"; return SRL_ERR_NO_DEVICE; }
+    const int rc = srl_points_info(ctx, size, front_timestamp, back_timestamp);
+    if (rc != SRL_OK) h->err = srl_last_error(ctx);
+    return rc;
+}
+
+int srl_lio_run_measurement_queued(srl_lio *h, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                   double time_cut, double time_sweep_begin, double time_sweep_offset, srl_replay_result *out) {
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || n_imu < 0 || (n_imu > 0 && (!imu_t || !imu_acc || !imu_gyr)) || std::isnan(time_cut)) return SRL_ERR_BAD_ARG;
+    lioOptimization &L = *h->lio;
+    srl_ctx *ctx = L.context();
+    if (!ctx) { h->err = "host-only handle: no device, no point queue"; return SRL_ERR_NO_DEVICE; }
+    if (!(L.device_subsample && L.voxel_size > 0)) {
+        h->err = "srl_lio_run_measurement_queued needs the device sub-sample (srl_lio_set_device_subsample(1), voxel_size > 0)";
+        return SRL_ERR_UNSUPPORTED;                                // the queue is left uncut
+    }
+    srl_points_cut_report cut;
+    int rc = srl_points_cut(ctx, time_cut, &cut);
+    if (rc != SRL_OK) { h->err = srl_last_error(ctx); return rc; }
+    if (cut.count == 0) return SRL_OK;                             // lioOptimization.cpp:730 / :770: no lidar points, no Measurements element
+    L.sweep_from_queue = true;
+    rc = srl_lio_run_measurement(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, nullptr, nullptr, 0, time_sweep_begin, time_sweep_offset, out);
+    L.sweep_from_queue = false;
+    return rc;
+}
+
 int srl_lio_last_frame(srl_lio *h, int capacity, double *raw_point, double *point, double *imu_point, int *n) {
     if (!h || !n) return SRL_ERR_BAD_ARG;
     if (h->lio->all_cloud_frame.empty()) { *n = 0; return SRL_OK; }

@@ -164,6 +164,9 @@ struct srl_ctx {
     int *d_corr_seg = nullptr;
     int corr_cap = 0;
     int corr_n = -1;
+    bool corr_from_cut = false;        // the undistorted sweep came from the device point queue (srl_frame_undistort_cut): its rewritten
+                                       // times are resident too (srl_frame_point_times)
+    struct SrlPoints *points = nullptr;   // the device point queue and its resident cut (srl_points.hip); nullptr until the first srl_livox_decode
     // buildFrame's sub-sample of the undistorted sweep (srl_frame_subsample): the kept sweep indices in container order, and the tag words
     // that check a permutation on the device (zeroed when allocated; a call tags with a value no earlier call of this block used)
     int *d_sub_kept = nullptr;
@@ -331,6 +334,8 @@ extern "C" int srl_ctx_disarm(srl_ctx *ctx);
 #define SRL_DISARM(ctx) do { if ((ctx)->armed.on) { int rcd__ = srl_ctx_disarm(ctx); if (rcd__) return rcd__; } } while (0)
 // frees the consensus workspace (srl_consensus.hip); srl_ctx_destroy calls it
 extern "C" void srl_consensus_release(srl_ctx *ctx);
+// frees the device point queue (srl_points.hip); srl_ctx_destroy calls it
+extern "C" void srl_points_release(srl_ctx *ctx);
 
 // frame pipeline stage stamps (only while srl_debug_frame_timing is on): close stage `slot` here
 #include <chrono>

@@ -19,6 +19,7 @@
 //                               (lioOptimization.cpp:520-554) chained on the device.
 #include "srl_ctx.h"
 #include "srl_frame_scratch.h"
+#include "srl_undistort.h"
 #include "srl_hash.h"
 #include "host/srl_la.h"
 #include "host/tr1_order.h"
@@ -629,64 +630,26 @@ int sub_seen_begin(srl_ctx *ctx, unsigned *tag) {
 
 }  // namespace
 
-extern "C" {
+int srl_corr_reserve(srl_ctx *ctx, int n) {
+    if (n <= ctx->corr_cap) return SRL_OK;
+    void *bufs[] = {ctx->d_corr_raw, ctx->d_corr_imu, ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_seg};
+    for (void *b : bufs) if (b) HIPCHK(ctx, hipFree(b));
+    ctx->d_corr_raw = ctx->d_corr_imu = ctx->d_corr_in = ctx->d_corr_rel = nullptr; ctx->d_corr_seg = nullptr;
+    ctx->corr_cap = 0;
+    const int cap = std::max(n, 4096);
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_raw, (size_t)cap * 24));
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_imu, (size_t)cap * 24));
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_in, (size_t)cap * 24));
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_rel, (size_t)cap * 8));
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_seg, (size_t)cap * 4));
+    ctx->corr_cap = cap;
+    return SRL_OK;
+}
 
-int srl_frame_undistort(srl_ctx *ctx, const double *raw_xyz, const double *relative_time_ms, const double *imu_point_in, int n,
-                        const srl_imu_state *imu_states, int n_states, double time_frame_begin, int motion_compensation,
-                        const double R_il[9], const double t_il[3], double *imu_point_out, double *raw_out) {
-    if (!ctx || n < 0 || (n > 0 && (!raw_xyz || !relative_time_ms)) || !imu_states || n_states < 1 || !R_il || !t_il)
-        return SRL_ERR_BAD_ARG;
-    SRL_DISARM(ctx);
-    if (motion_compensation != SRL_MC_IMU && motion_compensation != SRL_MC_CONSTANT_VELOCITY && motion_compensation != SRL_MC_NONE)
-        return SRL_ERR_BAD_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    ctx->corr_n = -1;
-    ctx->sub_n = -1;
-    if (n > ctx->corr_cap) {
-        void *bufs[] = {ctx->d_corr_raw, ctx->d_corr_imu, ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_seg};
-        for (void *b : bufs) if (b) HIPCHK(ctx, hipFree(b));
-        ctx->d_corr_raw = ctx->d_corr_imu = ctx->d_corr_in = ctx->d_corr_rel = nullptr; ctx->d_corr_seg = nullptr;
-        ctx->corr_cap = 0;
-        const int cap = std::max(n, 4096);
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_raw, (size_t)cap * 24));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_imu, (size_t)cap * 24));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_in, (size_t)cap * 24));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_rel, (size_t)cap * 8));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_corr_seg, (size_t)cap * 4));
-        ctx->corr_cap = cap;
-    }
-    if (n == 0) { ctx->corr_n = 0; return SRL_OK; }
-    hipStream_t st = ctx->stream;
-    DevBuf b_states;
-    HIPCHK(ctx, b_states.alloc(ctx, (size_t)n_states * sizeof(srl_imu_state)));
-    static_assert(sizeof(srl_imu_state) == 17 * sizeof(double), "srl_imu_state is 17 packed doubles");
-    HIPCHK(ctx, hipMemcpyAsync(b_states.p, imu_states, (size_t)n_states * sizeof(srl_imu_state), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_in, raw_xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_rel, relative_time_ms, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    if (imu_point_in) HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_imu, imu_point_in, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    else HIPCHK(ctx, hipMemsetAsync(ctx->d_corr_imu, 0, (size_t)n * 24, st));
-
-    std::vector<int> seg;
-    if (motion_compensation == SRL_MC_IMU) {
-        // the interval walk of distortFrameByImu (utility.cpp:247-305) is sequential in the point order: a point that
-        // fits the current interval advances the point cursor, one that does not advances the interval -- and a point
-        // no later interval fits stops everything behind it.  Integer control flow on N timestamps: replayed on the
-        // host; the per-point math runs on the device.
-        seg.assign((size_t)n, -1);
-        int iter = 0;
-        for (int k = 0; k + 1 < n_states; k++) {
-            const double tb = imu_states[k].timestamp, te = imu_states[k + 1].timestamp;
-            while (iter != n) {
-                const double time_point = time_frame_begin + relative_time_ms[iter] / 1000.0;
-                if (time_point > tb - 1e-6 && time_point < te + 1e-6) seg[iter++] = k;
-                else break;
-            }
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_seg, seg.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    }
-
+int srl_undistort_launch(srl_ctx *ctx, int n, const double *d_states, const srl_imu_state *imu_states, int n_states, double time_frame_begin,
+                         int motion_compensation, const double R_il[9], const double t_il[3]) {
     UndistortArgs A;
-    A.raw = ctx->d_corr_in; A.rel = ctx->d_corr_rel; A.states = b_states.as<double>(); A.seg = ctx->d_corr_seg;
+    A.raw = ctx->d_corr_in; A.rel = ctx->d_corr_rel; A.states = d_states; A.seg = ctx->d_corr_seg;
     A.imu = ctx->d_corr_imu; A.raw_out = ctx->d_corr_raw; A.n = n; A.mode = motion_compensation;
     A.tfb = time_frame_begin; A.tfe = imu_states[n_states - 1].timestamp;
     const srl_imu_state &s0 = imu_states[0], &s1 = imu_states[n_states - 1];
@@ -702,8 +665,48 @@ int srl_frame_undistort(srl_ctx *ctx, const double *raw_xyz, const double *relat
     std::memcpy(A.Rinv, Rinv.a, sizeof A.Rinv);
     std::memcpy(A.RilT, RilT.a, sizeof A.RilT);
     for (int d = 0; d < 3; d++) { A.tinv[d] = tinv[d]; A.RilT_til[d] = rt[d]; }
-    hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
+    return SRL_OK;
+}
+
+extern "C" {
+
+int srl_frame_undistort(srl_ctx *ctx, const double *raw_xyz, const double *relative_time_ms, const double *imu_point_in, int n,
+                        const srl_imu_state *imu_states, int n_states, double time_frame_begin, int motion_compensation,
+                        const double R_il[9], const double t_il[3], double *imu_point_out, double *raw_out) {
+    if (!ctx || n < 0 || (n > 0 && (!raw_xyz || !relative_time_ms)) || !imu_states || n_states < 1 || !R_il || !t_il)
+        return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    if (motion_compensation != SRL_MC_IMU && motion_compensation != SRL_MC_CONSTANT_VELOCITY && motion_compensation != SRL_MC_NONE)
+        return SRL_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->corr_n = -1;
+    ctx->sub_n = -1;
+    ctx->corr_from_cut = false;
+    int rc = srl_corr_reserve(ctx, n);
+    if (rc) return rc;
+    if (n == 0) { ctx->corr_n = 0; return SRL_OK; }
+    hipStream_t st = ctx->stream;
+    DevBuf b_states;
+    HIPCHK(ctx, b_states.alloc(ctx, (size_t)n_states * sizeof(srl_imu_state)));
+    static_assert(sizeof(srl_imu_state) == 17 * sizeof(double), "srl_imu_state is 17 packed doubles");
+    HIPCHK(ctx, hipMemcpyAsync(b_states.p, imu_states, (size_t)n_states * sizeof(srl_imu_state), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_in, raw_xyz, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_rel, relative_time_ms, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (imu_point_in) HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_imu, imu_point_in, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    else HIPCHK(ctx, hipMemsetAsync(ctx->d_corr_imu, 0, (size_t)n * 24, st));
+
+    std::vector<int> seg;
+    if (motion_compensation == SRL_MC_IMU) {
+        // Integer control flow on N timestamps (srl_undistort.h): replayed on the host; the per-point math runs on the device.
+        seg.resize((size_t)n);
+        srl_imu_interval_walk(relative_time_ms, n, imu_states, n_states, time_frame_begin, seg.data());
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_corr_seg, seg.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+
+    rc = srl_undistort_launch(ctx, n, b_states.as<double>(), imu_states, n_states, time_frame_begin, motion_compensation, R_il, t_il);
+    if (rc) return rc;
     if (imu_point_out) HIPCHK(ctx, hipMemcpyAsync(imu_point_out, ctx->d_corr_imu, (size_t)n * 24, hipMemcpyDeviceToHost, st));
     if (raw_out) HIPCHK(ctx, hipMemcpyAsync(raw_out, ctx->d_corr_raw, (size_t)n * 24, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));

@@ -328,8 +328,8 @@ inline void srl_radix_pass(const unsigned *keys, const unsigned *vals, unsigned 
         hipLaunchKernelGGL(k_radix_pass, grid, block, 0, st, keys, vals, keys_out, vals_out, n, shift, bits, (const int *)start, 2);
     }
 }
-// stable sort of (key, value) pairs by the low `bits` (<= 27) bits of the key: ceil(bits / 9) passes, each one launch (n <= 131 072), two
-// (n <= 1 M) or five (bulk).  vals == nullptr: the values are the positions 0..n-1.  tmp_keys / tmp_vals: n words each (untouched by a
+// stable sort of (key, value) pairs by the low `bits` (<= 32; the frame path needs <= 27, srl_points.hip sorts whole 32-bit offsets in four
+// passes of eight) bits of the key: ceil(bits / 9) passes, each one launch (n <= 131 072), two (n <= 1 M) or five (bulk).  vals == nullptr: the values are the positions 0..n-1.  tmp_keys / tmp_vals: n words each (untouched by a
 // one-pass sort); scratch: srl_radix_scratch_ints(n) ints.
 inline void srl_radix_sort_pairs(const unsigned *keys, const unsigned *vals, unsigned *keys_sorted, unsigned *vals_sorted, unsigned *tmp_keys,
                                  unsigned *tmp_vals, int n, unsigned bits, hipStream_t st, int *scratch = nullptr) {

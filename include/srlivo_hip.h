@@ -832,6 +832,61 @@ int srl_frame_undistort_cut(srl_ctx *ctx, double time_begin, double time_end, in
 int srl_frame_point_times(srl_ctx *ctx, const int32_t *index, int m, double *timestamp /* m or NULL */, double *relative_time /* m or NULL */,
                           double *alpha_time /* m or NULL */);
 
+/* ------------------------------------------------------------------ PointCloud2 messages (Velodyne, Ouster, RoboSense) -> the same device
+ * point queue (csrc/srl_pc2.hip, csrc/srl_pc2_layout.cpp).  Replaces cloudProcessing::process (cloudProcessing.cpp:100-123) with its three
+ * handlers: velodyneHandler (:325-433), ousterHandler (:216-323), robosenseHandler (:435-542).  Everything behind the queue (srl_points_cut,
+ * srl_frame_undistort_cut) is the Livox path's.
+ *
+ * srl_pc2_layout is what pcl::fromROSMsg reads of a sensor_msgs::PointCloud2: point i of n = width * height lies at (i / width) * row_step +
+ *   (i % width) * point_step, its fields at the byte offsets given (no alignment needed: the kernels assemble unaligned fields from bytes).
+ *   The datatypes are the reference's registered point structs (cloudProcessing.h:50-114), fixed by lidar_type: x, y, z float32 always;
+ *   2 VELO: time float32, ring uint16.  3 OUST: t uint32, ring uint8.  4 ROBO: timestamp float64, ring uint16.  `data` goes up once, as it is.
+ * srl_pc2_decode: last_end_time is the member the reference carries from message to message (-1 at construction): the caller passes what
+ *   the previous report gave.  given_offset_time = (time field of the LAST point in message order) > 0, decided before any sort (a NaN
+ *   there: 0).
+ *   given_offset_time = 1: the points are ordered by the time field ascending, TIES BY MESSAGE INDEX (a stable sort; the reference's
+ *     std::sort leaves ties in an order of its library's own -- every Ouster column shares one t).  relative_time of sorted position j:
+ *     double(time) * time_unit_scale (VELO, OUST); (timestamp_j - timestamp_sorted[0]) * time_unit_scale (ROBO).  Position j is picked iff
+ *     j % point_filter_num == 0; a picked point is appended iff (x x + y y) + z z > blind blind in FP64 and timestamp = relative_time / 1000.0 +
+ *     header_stamp > last_end_time.  dt_last_point = the sorted last point's double(time) * time_unit_scale -- for ROBO its ABSOLUTE
+ *     timestamp * time_unit_scale, not the difference (the reference's statement at :456, reproduced).
+ *   given_offset_time = 0: yaw = atan2(double(y), double(x)) * 57.2957 per point, computed ON THE HOST with libm (srl_pc2_yaw_angles: the
+ *     reference's bits are its libm's) and uploaded beside the message.  The first point of every ring in message order has relative_time =
+ *     0.0 and timestamp = 0.0 (the reference never assigns it: such a point passes the last_end_time test only while that is negative); every
+ *     other point has relative_time = (yaw_first - yaw) / omega if yaw <= yaw_first, else (yaw_first - yaw + 360.0) / omega, omega = 0.361 *
+ *     scan_rate, timestamp = relative_time / 1000.0 + header_stamp.  Stable sort by relative_time; position j is picked iff j %
+ *     point_filter_num == 0 and appended iff timestamp > last_end_time (NO blind test in this branch).  dt_last_point = the sorted last
+ *     relative_time.
+ *   report->last_end_time = header_stamp + dt_last_point / 1000.0.  points = n; picked = positions with j % point_filter_num == 0; first /
+ *   last_timestamp: of the appended points, NaN when none.  The same call gives the same bytes, every time.
+ *   n == 0: SRL_OK, nothing queued, report->last_end_time NaN (the reference returns before it assigns: the caller keeps its value).
+ *   SRL_ERR_BAD_ARG with nothing queued: NULL ctx / layout / opts / data; is_bigendian != 0; a field that does not fit inside point_step;
+ *   data_bytes short of the last point's end; lidar_type other than 2, 3, 4; point_filter_num < 1; time_unit_scale not positive and finite;
+ *   NaN blind, header_stamp or last_end_time; yaw branch: scan_rate <= 0, n_scans < 1, a ring >= n_scans (the reference indexes out of
+ *   bounds); a NaN sort key (given branch: any NaN time; yaw branch: a NaN relative_time) -- std::sort under < is undefined there.  The
+ *   last two are found on the device; the queue's size lives on the host and is simply not advanced.  n > 2^20 or more than one rank:
+ *   SRL_ERR_UNSUPPORTED.  Synchronous.  report may be NULL.  Cancels an armed launch.  The first call creates the queue, as the first
+ *   srl_livox_decode does (srl_points_info and the others answer SRL_ERR_NO_SWEEP before either).
+ * srl_pc2_yaw_angles: yaw[i] = atan2(double(y_i), double(x_i)) * 57.2957 for the n points of the layout; a pure host function (no HIP call,
+ *   the coordinates are read with memcpy).  SRL_ERR_BAD_ARG as above for the layout, data_bytes and NULL pointers. */
+typedef struct srl_pc2_layout {
+    uint32_t width, height, point_step, row_step;
+    int32_t  off_x, off_y, off_z, off_time, off_ring;   /* byte offsets inside one point */
+    int32_t  is_bigendian;                               /* must be 0 */
+} srl_pc2_layout;                                        /* 40 B */
+typedef struct srl_pc2_opts {
+    int32_t lidar_type;              /* cloudProcessing.h:25: 2 VELO, 3 OUST, 4 ROBO; 1 (LIVOX) and others refused */
+    int32_t n_scans, scan_rate, point_filter_num;
+    double  time_unit_scale, blind;
+} srl_pc2_opts;                                          /* 32 B */
+typedef struct srl_pc2_report {
+    int32_t points, given_offset_time, picked, appended;
+    double  last_end_time, first_timestamp, last_timestamp;
+} srl_pc2_report;                                        /* 40 B */
+int srl_pc2_decode(srl_ctx *ctx, const void *data, size_t data_bytes, const srl_pc2_layout *layout, double header_stamp,
+                   double last_end_time, const srl_pc2_opts *opts, srl_pc2_report *report);
+int srl_pc2_yaw_angles(const void *data, size_t data_bytes, const srl_pc2_layout *layout, double *yaw);
+
 /* ------------------------------------------------------------------ hot path
  * replaces: lioOptimization::buildPlaneResiduals (optimize.cpp:18-131) incl. searchNeighbors
  * (:365-426), computeNeighborhoodDistribution (:316-353), and the H_x^T H_x / H_x^T h contraction

@@ -236,6 +236,17 @@ int srl_lio_feed_livox(srl_lio *lio, const srl_livox_point *points, int point_nu
 int srl_lio_points_info(srl_lio *lio, int *size, double *front_timestamp, double *back_timestamp, double *last_time_lidar, double *last_end_time);
 int srl_lio_run_measurement_queued(srl_lio *lio, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
                                    double time_cut, double time_sweep_begin, double time_sweep_offset, srl_replay_result *out);
+/* The same for the spinning LiDARs (srlivo_hip.h: srl_pc2_decode).
+ * srl_lio_set_pc2_options: cloudProcessing's lidar_type, N_SCANS, SCAN_RATE, point_filter_num, time_unit_scale and blind; refused like
+ *   srl_pc2_decode refuses them (n_scans and scan_rate are looked at by the yaw branch alone, and refused there).
+ * srl_lio_feed_pointcloud2: lioOptimization::standardCloudHandler (lioOptimization.cpp:583-591): the message is decoded with the handle's
+ *   last_end_time into the handle's queue; last_time_lidar = header_stamp, and last_end_time follows the report (an empty message leaves
+ *   it as it was).  header_stamp <= last_time_lidar (the reference's assert) and a feed before the options are set: SRL_ERR_BAD_ARG,
+ *   nothing queued.  The two times and the queue are the ones srl_lio_feed_livox uses: both feeds keep one FIFO.
+ *   report->given_offset_time is cloudProcessing::isPointTimeEnable(): what the caller puts into srl_odometry_opts.point_time_enable. */
+int srl_lio_set_pc2_options(srl_lio *lio, const srl_pc2_opts *opts);
+int srl_lio_feed_pointcloud2(srl_lio *lio, const void *data, size_t data_bytes, const srl_pc2_layout *layout, double header_stamp,
+                             srl_pc2_report *report);
 
 /* Frame-resident form of optimize() + the map update that follows it in stateEstimation
  * (lioOptimization.cpp:1027,1051): the raw frame (n x 3) is uploaded once; keypoints are selected on the device

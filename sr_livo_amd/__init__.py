@@ -18,4 +18,6 @@ from .capi import (  # noqa: F401
     ImageProcessOpts, ImageProcessResult, ImageProcessSteps,
     LivoxOpts, LivoxReport, PointsCutReport, LIVOX_POINT_DTYPE, livox_opts, time_unit_scale,
     TIME_UNIT_SEC, TIME_UNIT_MS, TIME_UNIT_US, TIME_UNIT_NS,
+    Pc2Layout, Pc2Opts, Pc2Report, PC2_POINT_DTYPES, PC2_DRIVER_LAYOUTS, LIDAR_LIVOX, LIDAR_VELO, LIDAR_OUST, LIDAR_ROBO,
+    pc2_opts, pc2_message, pc2_yaw_angles,
 )

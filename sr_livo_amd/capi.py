@@ -288,6 +288,38 @@ class PointsCutReport(C.Structure):
     _fields_ = [("count", C.c_int32), ("reserved", C.c_int32), ("front_timestamp", C.c_double)]
 
 
+class Pc2Layout(C.Structure):
+    """srl_pc2_layout: what pcl::fromROSMsg reads of a sensor_msgs::PointCloud2"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32), ("off_x", C.c_int32),
+                ("off_y", C.c_int32), ("off_z", C.c_int32), ("off_time", C.c_int32), ("off_ring", C.c_int32), ("is_bigendian", C.c_int32)]
+
+
+class Pc2Opts(C.Structure):
+    """srl_pc2_opts: cloudProcessing's lidar_type, N_SCANS, SCAN_RATE, point_filter_num, time_unit_scale, blind"""
+    _fields_ = [("lidar_type", C.c_int32), ("n_scans", C.c_int32), ("scan_rate", C.c_int32), ("point_filter_num", C.c_int32),
+                ("time_unit_scale", C.c_double), ("blind", C.c_double)]
+
+
+class Pc2Report(C.Structure):
+    _fields_ = [("points", C.c_int32), ("given_offset_time", C.c_int32), ("picked", C.c_int32), ("appended", C.c_int32),
+                ("last_end_time", C.c_double), ("first_timestamp", C.c_double), ("last_timestamp", C.c_double)]
+
+
+# cloudProcessing.h:25, and the fields srl_pc2_decode reads per type (the reference's registered point structs, :50-114)
+LIDAR_LIVOX, LIDAR_VELO, LIDAR_OUST, LIDAR_ROBO = 1, 2, 3, 4
+PC2_POINT_DTYPES = {
+    LIDAR_VELO: np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("time", "<f4"), ("ring", "<u2")]),
+    LIDAR_OUST: np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("time", "<u4"), ("ring", "u1")]),
+    LIDAR_ROBO: np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("time", "<f8"), ("ring", "<u2")]),
+}
+# where the drivers put them: velodyne_pointcloud's PointXYZIRT (22 B, time unaligned), ouster_ros (48 B), rslidar_sdk's XYZIRT (26 B, the
+# double at 18)
+PC2_DRIVER_LAYOUTS = {
+    LIDAR_VELO: (22, dict(x=0, y=4, z=8, ring=16, time=18)),
+    LIDAR_OUST: (48, dict(x=0, y=4, z=8, time=20, ring=26)),
+    LIDAR_ROBO: (26, dict(x=0, y=4, z=8, ring=16, time=18)),
+}
+
 # srl_livox_point = livox_ros_driver::CustomPoint in memory (20 B)
 LIVOX_POINT_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("reflectivity", "u1"), ("tag", "u1"),
                               ("line", "u1"), ("pad", "u1")])
@@ -599,6 +631,10 @@ def load_library():
         "srl_lio_set_lidar_options": ([p, C.POINTER(LivoxOpts)], C.c_int),
         "srl_lio_feed_livox": ([p, p, C.c_int, C.c_double, C.POINTER(LivoxReport)], C.c_int),
         "srl_lio_points_info": ([p, C.POINTER(C.c_int), dp, dp, dp, dp], C.c_int),
+        "srl_pc2_decode": ([p, p, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_double, C.POINTER(Pc2Opts), C.POINTER(Pc2Report)], C.c_int),
+        "srl_pc2_yaw_angles": ([p, C.c_size_t, C.POINTER(Pc2Layout), dp], C.c_int),
+        "srl_lio_set_pc2_options": ([p, C.POINTER(Pc2Opts)], C.c_int),
+        "srl_lio_feed_pointcloud2": ([p, p, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.POINTER(Pc2Report)], C.c_int),
         "srl_lio_run_measurement_queued": ([p, C.c_double, p, p, p, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(ReplayResult)], C.c_int),
         "srl_grid_sampling": ([p, C.c_int, C.c_double, p, C.POINTER(C.c_int)], C.c_int),
         "srl_debug_tr1_order": ([p, C.c_int, p], C.c_int),
@@ -676,6 +712,56 @@ def _livox_points(points):
 def _livox_report_dict(r):
     return dict(valid=r.valid, picked=r.picked, appended=r.appended, last_end_time=r.last_end_time, first_timestamp=r.first_timestamp,
                 last_timestamp=r.last_timestamp)
+
+
+def pc2_opts(lidar_type, n_scans=16, scan_rate=10, point_filter_num=1, time_unit=TIME_UNIT_US, blind=0.01, time_unit_scale_value=None):
+    """srl_pc2_opts; the scale comes from srl_time_unit_scale(time_unit) unless given"""
+    o = Pc2Opts()
+    o.lidar_type, o.n_scans, o.scan_rate, o.point_filter_num = int(lidar_type), int(n_scans), int(scan_rate), int(point_filter_num)
+    o.time_unit_scale = float(time_unit_scale(time_unit) if time_unit_scale_value is None else time_unit_scale_value)
+    o.blind = float(blind)
+    return o
+
+
+def pc2_message(points, lidar_type, point_step=None, offsets=None, height=1, row_pad=0, fill=0xA5):
+    """A PointCloud2 `data` buffer for tests: points = PC2_POINT_DTYPES[lidar_type] records (x, y, z, time, ring), written field by field at
+    `offsets` (dict x y z time ring -> byte offset inside a point; default: the driver's) into points of point_step bytes, height rows of
+    len(points) / height points, each row followed by row_pad bytes.  Every byte that is no field is `fill`.  No field needs alignment.
+    -> (uint8 array, Pc2Layout)"""
+    a = np.ascontiguousarray(points, dtype=PC2_POINT_DTYPES[int(lidar_type)])
+    step0, off0 = PC2_DRIVER_LAYOUTS[int(lidar_type)]
+    point_step = int(step0 if point_step is None else point_step)
+    off = dict(off0 if offsets is None else offsets)
+    n, height = len(a), int(height)
+    if height < 1 or n % height:
+        raise ValueError("len(points) must be a multiple of height")
+    width = n // height
+    row_step = width * point_step + int(row_pad)
+    buf = np.full((height, row_step), fill, dtype=np.uint8)
+    body = buf[:, :width * point_step].reshape(height, width, point_step)
+    for name in ("x", "y", "z", "time", "ring"):
+        col = np.ascontiguousarray(a[name]).view(np.uint8).reshape(height, width, a.dtype[name].itemsize)
+        if off[name] < 0 or off[name] + col.shape[2] > point_step:
+            raise ValueError(f"field {name} does not fit inside point_step")
+        body[:, :, off[name]:off[name] + col.shape[2]] = col
+    lay = Pc2Layout(width=width, height=height, point_step=point_step, row_step=row_step, off_x=off["x"], off_y=off["y"], off_z=off["z"],
+                    off_time=off["time"], off_ring=off["ring"], is_bigendian=0)
+    return buf.reshape(-1), lay
+
+
+def pc2_yaw_angles(data, layout):
+    """srl_pc2_yaw_angles: atan2(double(y), double(x)) * 57.2957 per point, on the host (libm)"""
+    d = np.ascontiguousarray(data, dtype=np.uint8)
+    yaw = np.empty(int(layout.width) * int(layout.height))
+    rc = load_library().srl_pc2_yaw_angles(_ptr(d), d.nbytes, C.byref(layout), _dptr(yaw))
+    if rc != SRL_OK:
+        raise SrlError(rc, "srl_pc2_yaw_angles")
+    return yaw
+
+
+def _pc2_report_dict(r):
+    return dict(points=r.points, given_offset_time=r.given_offset_time, picked=r.picked, appended=r.appended, last_end_time=r.last_end_time,
+                first_timestamp=r.first_timestamp, last_timestamp=r.last_timestamp)
 
 
 def default_color_opts(**kw):
@@ -1400,6 +1486,14 @@ class Context:
         r = LivoxReport()
         rc = self._chk(self.lib.srl_livox_decode(self.h, _ptr(a), len(a), float(header_stamp), C.byref(opts), C.byref(r)), "srl_livox_decode", ok=ok)
         return dict(_livox_report_dict(r), rc=rc)
+
+    def pc2_decode(self, data, layout, header_stamp, last_end_time, opts, ok=()):
+        """srl_pc2_decode: data = the message's bytes (pc2_message), layout = Pc2Layout.  Returns the report as a dict (with rc)."""
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        r = Pc2Report()
+        rc = self._chk(self.lib.srl_pc2_decode(self.h, _ptr(d), d.nbytes, C.byref(layout), float(header_stamp), float(last_end_time), C.byref(opts),
+                                               C.byref(r)), "srl_pc2_decode", ok=ok)
+        return dict(_pc2_report_dict(r), rc=rc)
 
     def points_info(self):
         """srl_points_info -> (size, front_timestamp, back_timestamp); no device synchronisation"""
@@ -2387,6 +2481,17 @@ class Lio:
         r = LivoxReport()
         self._chk(self.lib.srl_lio_feed_livox(self.h, _ptr(a), len(a), float(header_stamp), C.byref(r)), "feed_livox")
         return _livox_report_dict(r)
+
+    def set_pc2_options(self, opts):
+        """srl_lio_set_pc2_options: opts = pc2_opts(...)"""
+        self._chk(self.lib.srl_lio_set_pc2_options(self.h, C.byref(opts)), "set_pc2_options")
+
+    def feed_pointcloud2(self, data, layout, header_stamp):
+        """srl_lio_feed_pointcloud2 (lioOptimization::standardCloudHandler): one message into the handle's device point queue"""
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        r = Pc2Report()
+        self._chk(self.lib.srl_lio_feed_pointcloud2(self.h, _ptr(d), d.nbytes, C.byref(layout), float(header_stamp), C.byref(r)), "feed_pointcloud2")
+        return _pc2_report_dict(r)
 
     def points_info(self):
         """srl_lio_points_info -> dict(size, front_timestamp, back_timestamp, last_time_lidar, last_end_time)"""

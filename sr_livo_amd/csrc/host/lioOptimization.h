@@ -162,6 +162,10 @@ public:
     // lioOptimization::livoxHandler (lioOptimization.cpp:593-601) and cloudProcessing::livoxHandler keep between messages
     srl_livox_opts lidar_options = {};                                   // (the reference has no defaults for three of the four)
     bool lidar_options_set = false;
+    // ... and as srl_pc2_decode reads them for lioOptimization::standardCloudHandler (:583-591): setLidarType and setScanRate come with them.
+    // Both handlers share the two times below and the queue, as they share cloud_pro and point_buffer upstream.
+    srl_pc2_opts pc2_options = {};
+    bool pc2_options_set = false;
     double last_time_lidar = -1.0;                                       // lioOptimization.cpp:383
     double last_end_time = -1.0;                                         // cloudProcessing.cpp:9
     // optimize() on the frame buildFrame left resident in HBM

@@ -647,6 +647,34 @@ int srl_lio_feed_livox(srl_lio *h, const srl_livox_point *points, int point_num,
     return SRL_OK;
 }
 
+// ---- ... and PointCloud2 messages of the spinning LiDARs into the same queue
+int srl_lio_set_pc2_options(srl_lio *h, const srl_pc2_opts *o) {
+    if (!h || !o) return SRL_ERR_BAD_ARG;
+    if (o->lidar_type < 2 || o->lidar_type > 4 || o->point_filter_num < 1 || !(o->time_unit_scale > 0.0) || std::isinf(o->time_unit_scale) || std::isnan(o->blind))
+        return SRL_ERR_BAD_ARG;
+    h->lio->pc2_options = *o;          // (scan_rate and n_scans matter in the yaw branch alone: srl_pc2_decode refuses them there)
+    h->lio->pc2_options_set = true;
+    return SRL_OK;
+}
+
+int srl_lio_feed_pointcloud2(srl_lio *h, const void *data, size_t data_bytes, const srl_pc2_layout *layout, double header_stamp, srl_pc2_report *report) {
+    if (report) { std::memset(report, 0, sizeof *report); report->last_end_time = report->first_timestamp = report->last_timestamp = std::nan(""); }
+    if (!h || !data || !layout) return SRL_ERR_BAD_ARG;
+    lioOptimization &L = *h->lio;
+    if (!L.pc2_options_set) { h->err = "srl_lio_feed_pointcloud2: no options (srl_lio_set_pc2_options)"; return SRL_ERR_BAD_ARG; }
+    // lioOptimization.cpp:585: assert(msg->header.stamp.toSec() > last_time_lidar) -- here a refusal, and nothing is queued
+    if (!(header_stamp > L.last_time_lidar)) { h->err = "srl_lio_feed_pointcloud2: a message that is not newer than the last one"; return SRL_ERR_BAD_ARG; }
+    srl_ctx *ctx = L.context();
+    if (!ctx) { h->err = "host-only handle: no device, no point queue"; return SRL_ERR_NO_DEVICE; }
+    srl_pc2_report r;
+    const int rc = srl_pc2_decode(ctx, data, data_bytes, layout, header_stamp, L.last_end_time, &L.pc2_options, &r);
+    if (rc != SRL_OK) { h->err = srl_last_error(ctx); return rc; }
+    L.last_time_lidar = header_stamp;                              // :590
+    if (r.points > 0) L.last_end_time = r.last_end_time;           // cloudProcessing.cpp:322 / :432 / :541 (an empty message returns before it)
+    if (report) *report = r;
+    return SRL_OK;
+}
+
 int srl_lio_points_info(srl_lio *h, int *size, double *front_timestamp, double *back_timestamp, double *last_time_lidar, double *last_end_time) {
     if (!h) return SRL_ERR_BAD_ARG;
     lioOptimization &L = *h->lio;

@@ -69,6 +69,20 @@ int srl_debug_set_fused_reduce(srl_ctx *ctx, int enable);
  * mode 1 (default): both.  2: the voxel cull only, every threshold searched.  0: the bounds are not used at all.  (A/B in the tests:
  * every bit must agree between the three.)  Other values: SRL_ERR_BAD_ARG. */
 int srl_debug_set_bound_culling(srl_ctx *ctx, int mode);
+/* Neighbour records (default on): the map keeps, per voxel, what the 27 lookups around it return (slab and count of every neighbour
+ * voxel, or "none"), brought up to date by whatever edits the map.  A pass of the r = 1 fast path looks only a keypoint's HOME voxel
+ * up in the table and takes the 27 answers from that voxel's record; keypoints whose home voxel is not in the map, r = 2 and the general
+ * path look every voxel up as before.  enable 0: no pass reads the records (every pair of the fast path takes the table lookups); the
+ * map still maintains them, and the table request of such a pair is issued when the pair is consumed, not a pair ahead -- a switch for
+ * equality tests, not a timing baseline.  Every bit of a pass must agree between 0 and 1.  Other values: SRL_ERR_BAD_ARG. */
+int srl_debug_set_neighbour_records(srl_ctx *ctx, int enable);
+/* srl_debug_neighbour_records_download: the records of the map's voxels, 32 words each, in slab order (the order of srl_map_download):
+ * word (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1) = slab << 5 | count of the voxel at key + (dx, dy, dz) (16-bit wrap), 0xFFFFFFFF = none,
+ * words 27 .. 31 zero.  max_voxels < the map's voxels: SRL_ERR_BAD_ARG. */
+int srl_debug_neighbour_records_download(srl_ctx *ctx, uint32_t *words, int max_voxels);
+/* The neighbourhood bounds the last pass left: *num_keypoints entries {x, y, z, tau} (0 after anything that voids them), the first
+ * max_keypoints >= that many floats x 4 of `bounds` filled.  Cancels a waiting launch. */
+int srl_debug_bounds_download(srl_ctx *ctx, float *bounds, int max_keypoints, int *num_keypoints);
 /* Where the pose box of the armed launches lives.  kind 1: fine-grained DEVICE memory the host writes through the PCIe BAR (every
  * workgroup polls it locally; SRL_ERR_UNSUPPORTED when device memory is not CPU-visible on this system).  kind 0: page-locked host
  * memory -- workgroup 0 of the waiting kernel polls it across PCIe and republishes the pose into device memory for the other

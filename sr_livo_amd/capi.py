@@ -513,6 +513,9 @@ def load_library():
         "srl_debug_set_ablate": ([p, C.c_int], C.c_int),
         "srl_debug_set_fused_reduce": ([p, C.c_int], C.c_int),
         "srl_debug_set_bound_culling": ([p, C.c_int], C.c_int),
+        "srl_debug_set_neighbour_records": ([p, C.c_int], C.c_int),
+        "srl_debug_neighbour_records_download": ([p, p, C.c_int], C.c_int),
+        "srl_debug_bounds_download": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_debug_set_pose_box": ([p, C.c_int], C.c_int),
         "srl_debug_set_arm_linger": ([p, C.c_double, C.c_double], C.c_int),
         "srl_debug_pass_stamps": ([p, C.c_int, p, p], C.c_int),
@@ -1353,6 +1356,26 @@ class Context:
         """test hook: 0 = every pass visits every found voxel (no use of the previous pass's neighbourhood bounds); 1 (default) = the
         bounds cull voxels and give the prefilter its threshold; 2 = they cull voxels only, the threshold is searched"""
         self._chk(self.lib.srl_debug_set_bound_culling(self.h, int(mode)), "srl_debug_set_bound_culling")
+
+    def set_neighbour_records(self, on):
+        """test hook: 1 (default) = the r = 1 fast path takes a keypoint's 27 voxel lookups from its home voxel's neighbour record;
+        0 = it looks every voxel up in the table"""
+        self._chk(self.lib.srl_debug_set_neighbour_records(self.h, 1 if on else 0), "srl_debug_set_neighbour_records")
+
+    def neighbour_records_download(self):
+        """the neighbour records of the map's voxels, (voxels, 32) uint32 in the slab order of map_download"""
+        _, nv = self.map_size()
+        words = np.zeros((nv, 32), dtype=np.uint32)
+        self._chk(self.lib.srl_debug_neighbour_records_download(self.h, _ptr(words), nv), "srl_debug_neighbour_records_download")
+        return words
+
+    def bounds_download(self):
+        """the neighbourhood bounds the last pass left: (keypoints, 4) float32 {x, y, z, tau}; empty after anything that voids them"""
+        _, n, _ = self.sweep_shard()
+        out = np.zeros((max(n, 1), 4), dtype=np.float32)
+        got = C.c_int()
+        self._chk(self.lib.srl_debug_bounds_download(self.h, _ptr(out), len(out), C.byref(got)), "srl_debug_bounds_download")
+        return out[: got.value].copy()
 
     def set_search_select_mode(self, mode):
         self._chk(self.lib.srl_debug_set_search_select_mode(self.h, int(mode)), "srl_debug_set_search_select_mode")

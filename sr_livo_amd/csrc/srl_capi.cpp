@@ -97,6 +97,8 @@ bool srl_ctx_is_pinned(const void *p) { return srl_is_pinned(p); }             /
 
 // shared with srl_map_kernels.hip
 int srl_ctx_grow_map(srl_ctx *ctx, unsigned need_slabs, unsigned need_slots);
+int srl_nbrec_alloc(srl_ctx *ctx, unsigned slab_cap, int keep_voxels);
+int srl_nbrec_rebuild(srl_ctx *ctx);
 
 extern "C" {
 
@@ -192,7 +194,7 @@ int srl_ctx_destroy(srl_ctx *ctx) {
     if (ctx->parked_comm && srl_rccl()) srl_rccl()->CommDestroy(ctx->parked_comm);
     if (ctx->d_sub_kept) hipFree(ctx->d_sub_kept);
     if (ctx->d_sub_seen) hipFree(ctx->d_sub_seen);
-    void *bufs[] = {ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_imu, ctx->d_corr_raw, ctx->d_corr_seg, ctx->d_frame_raw, ctx->d_frame_world, ctx->d_table, ctx->d_slabs, ctx->cur.soa, ctx->d_rec, ctx->d_status, ctx->d_partials, ctx->d_binfo,
+    void *bufs[] = {ctx->d_corr_in, ctx->d_corr_rel, ctx->d_corr_imu, ctx->d_corr_raw, ctx->d_corr_seg, ctx->d_frame_raw, ctx->d_frame_world, ctx->d_table, ctx->d_slabs, ctx->d_nbrec, ctx->cur.soa, ctx->d_rec, ctx->d_status, ctx->d_partials, ctx->d_binfo,
                     ctx->d_out, ctx->d_count, ctx->d_bound, ctx->d_granules, ctx->d_rec_granules, ctx->next.soa, ctx->next.stage, ctx->cur.stage, ctx->d_tap_ids, ctx->d_tap_ncand, ctx->d_tap_normal, ctx->d_tap_a2d,
                     ctx->d_tap_offset, ctx->d_gather, ctx->d_peer, ctx->d_mail};
     for (int r = 0; r < SRL_MAX_PEERS; r++) if (ctx->peer_mapped[r]) hipIpcCloseMemHandle(ctx->peer_mapped[r]);
@@ -263,6 +265,8 @@ int srl_map_upload(srl_ctx *ctx, const int16_t *keys_xyz, const int32_t *counts,
         table[h].slab = (unsigned)v;
         table[h].count = (unsigned)c;
     }
+    // storage of the neighbour records first: if it cannot be had, the map that is there stays as it is
+    { const int rcn = srl_nbrec_alloc(ctx, slab_cap, 0); if (rcn) return rcn; }
     if (ctx->d_slabs) { HIPCHK(ctx, hipFree(ctx->d_slabs)); ctx->d_slabs = nullptr; }
     if (ctx->d_table) { HIPCHK(ctx, hipFree(ctx->d_table)); ctx->d_table = nullptr; }
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_slabs, ((size_t)slab_cap + 1) * SRL_SLAB_BYTES));       // + the all-inf slab
@@ -276,7 +280,8 @@ int srl_map_upload(srl_ctx *ctx, const int16_t *keys_xyz, const int32_t *counts,
     ctx->table_cap = table_cap;
     ctx->num_voxels = V;
     ctx->num_points = npts;
-    return SRL_OK;
+    // the neighbour records of the uploaded voxels, from the table just built (stream-ordered, like the prune's)
+    return srl_nbrec_rebuild(ctx);
 }
 
 int srl_map_size(srl_ctx *ctx, int64_t *num_points, int32_t *num_voxels) {
@@ -969,6 +974,7 @@ static void prepare_assoc_args(srl_ctx *ctx, const srl_frame *f, const srl_icp_o
     a.table = ctx->d_table;
     a.table_mask = ctx->table_cap - 1;
     a.slabs = ctx->d_slabs;
+    a.nbrec = ctx->nbrec_mode != 0 ? ctx->d_nbrec : nullptr;
     a.inf_off = ctx->slab_cap * (unsigned)SRL_SLAB_BYTES;
     // records {J, d, w} + status feed the ordered cut-off (optimize.cpp:107) and the parity taps only: 4 MB of stores per
     // 64k sweep that the throughput configuration (max_num_residuals > number of keypoints) never reads -- nor does a fused cut,
@@ -1631,6 +1637,35 @@ int srl_debug_set_bound_culling(srl_ctx *ctx, int mode) {
     SRL_DISARM(ctx);
     ctx->bound_mode = mode;
     ctx->bound_n = 0;
+    return SRL_OK;
+}
+int srl_debug_set_neighbour_records(srl_ctx *ctx, int enable) {
+    if (!ctx || enable < 0 || enable > 1) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    ctx->nbrec_mode = enable;
+    return SRL_OK;
+}
+int srl_debug_neighbour_records_download(srl_ctx *ctx, uint32_t *words, int max_voxels) {
+    if (!ctx || !words) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    if (!ctx->d_nbrec) return SRL_ERR_NO_MAP;
+    { const int rcs = srl_map_settle(ctx); if (rcs) return rcs; }
+    const int V = ctx->num_voxels;
+    if (max_voxels < V) return SRL_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (V > 0) HIPCHK(ctx, hipMemcpyAsync(words, ctx->d_nbrec, (size_t)V * SRL_NBREC_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return SRL_OK;
+}
+int srl_debug_bounds_download(srl_ctx *ctx, float *bounds, int max_keypoints, int *num_keypoints) {
+    if (!ctx || !num_keypoints || max_keypoints < 0 || (max_keypoints > 0 && !bounds)) return SRL_ERR_BAD_ARG;
+    SRL_DISARM(ctx);
+    const int n = ctx->d_bound ? ctx->bound_n : 0;
+    *num_keypoints = n;
+    if (max_keypoints < n) return SRL_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n > 0) HIPCHK(ctx, hipMemcpyAsync(bounds, ctx->d_bound, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return SRL_OK;
 }
 int srl_debug_set_fused_reduce(srl_ctx *ctx, int enable) {

@@ -109,6 +109,8 @@ struct srl_ctx {
     unsigned table_cap = 0;            // slots (power of two)
     unsigned char *d_slabs = nullptr;
     unsigned slab_cap = 0;             // slabs allocated
+    unsigned *d_nbrec = nullptr;       // neighbour records (srl_device.h): SRL_NBREC_WORDS words per slab, slab_cap of them, allocated and grown with the slabs
+    int nbrec_mode = 1;                // srl_debug_set_neighbour_records: 1 = the r = 1 fast path reads them, 0 = it looks every voxel up in the table
     int num_voxels = 0;
     long long num_points = 0;
 

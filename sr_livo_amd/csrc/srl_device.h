@@ -102,6 +102,18 @@ struct SrlSlab {
 };
 static_assert(sizeof(SrlSlab) == SRL_SLAB_BYTES, "slab must be 256 bytes");
 
+// ---- neighbour records: what the 27 lookups around a voxel return, kept per voxel.  One 128-byte, 128-byte-aligned
+// record per slab, index = slab index.  Word d (0 .. 26; d = (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1): the visit order of lane_role, x outer,
+// z inner) describes the voxel at key ((short)(kx + dx), (short)(ky + dy), (short)(kz + dz)) -- the same wrap at +-32 767 as the probes'
+// keys: slab << 5 | count, or SRL_NBREC_NONE when the map has no such voxel.  Word 13 is the voxel itself; words 27 .. 31 stay zero.
+// Which voxels exist, their slabs and their counts depend on the map alone: whatever edits the map brings the records up to date on the
+// same stream (srl_map_kernels.hip: k_nbrec_update), so every reader ordered behind the edit finds them exact.
+#define SRL_NBREC_WORDS 32
+#define SRL_NBREC_COUNT_BITS 5
+#define SRL_NBREC_NONE 0xFFFFFFFFu   // no slab index reaches 2^27 - 1 (SRL_MAX_SLABS), no count 31
+static_assert(SRL_CAP < (1 << SRL_NBREC_COUNT_BITS) - 1, "a voxel's count must fit the record's count field (and stay clear of the sentinel's)");
+__host__ __device__ constexpr unsigned srl_nbrec_enc(unsigned slab, unsigned count) { return slab << SRL_NBREC_COUNT_BITS | count; }
+
 struct SrlBlockInfo {          // per-workgroup integer results
     int accepted;              // residuals accepted in this block
     unsigned sum_pk;           // candidates visited
@@ -184,6 +196,9 @@ struct SrlAssocArgs {
     const SrlMapSlot *table;
     unsigned table_mask;
     const unsigned char *slabs;
+    // neighbour records of the map (above), or null (srl_debug_set_neighbour_records(ctx, 0)): the r = 1 fast path then looks all 27 voxels
+    // of every keypoint up in the table.  Part of the armed signature like every other member.
+    const unsigned *nbrec;
     int write_rec;                     // per-keypoint records + status are needed (ordered cut-off can trigger, or taps); else skipped
     unsigned inf_off;                  // byte offset of the slab whose 20 points are (+inf, +inf, +inf): lanes without a candidate load from it
     // pose (computed on the host exactly like the reference: optimize.cpp:35 and :95)
@@ -204,6 +219,10 @@ struct SrlAssocArgs {
     int thr_cap;        // threshold_voxel_capacity
     int select_mode;
     int ablate;             // debug only (env SRL_ABLATE): bit0 skip phase 2, bit1 stop after compaction, bit2 stop after probe, bit3 skip probe
+                            // (bit 5, value 32: no voxel request is issued -- neither the record word a pair ahead nor, for a pair without
+                            // home slabs, the table request at consume time; bit 3, value 8: nothing is resolved or filed.  With the records on,
+                            // 8 against 8 | 32 separates the record load; with them off the table request is not a pair ahead as it was
+                            // when HISTORY.md's ablation tables were taken)
     // fused final reduction (single rank, no ordered cut possible, no taps): the last workgroup to finish sums the block
     // partials and publishes the result itself -- no second kernel, no kernel boundary on the per-iteration critical path
     unsigned long long *granules;   // nblocks x SRL_ROW_GRANULES tagged 8-byte granules {epoch, 32-bit payload}: the published rows (null = not fused)

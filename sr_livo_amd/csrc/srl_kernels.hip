@@ -359,20 +359,15 @@ __device__ __forceinline__ ProbeReq probe_issue(const int *kv, int kl, const Lan
     }
     return r;
 }
-// Compacts the occupied voxels of both keypoints into their lists (list h at vox + 32 h, visit order kept,
-// zero-filled up to 27 entries so the candidate rounds need no bounds branch).  Returns nv_A | nv_B << 8.
-// cull (wave-uniform): qf_pair / kv_pair = the pair's FP32 queries (8 floats per keypoint, [5] = squared cull radius) and voxel keys (4
-// ints per keypoint); a found voxel whose box lies further from the query than the radius keeps its count in P_k (the reference's loop
-// visits it) but is left out of the candidate list -- none of its points can be among the K nearest (SrlAssocArgs::bound_in)
-__device__ __forceinline__ int probe_finish(const ProbeReq &r, int thr_cap, const SrlMapSlot *table, unsigned mask,
-                                            VoxEnt *vox, int lane, int *ncand_pair, bool cull = false, const float *qf_pair = nullptr,
-                                            const int *kv_pair = nullptr, const LaneRole *role = nullptr, float size_voxel = 1.0f) {
+// What a table request found: the voxel exists (`found`), its slab and its count
+__device__ __forceinline__ void probe_resolve(const ProbeReq &r, const SrlMapSlot *table, unsigned mask, int lane, bool &found, unsigned &slab,
+                                              unsigned &cnt) {
     const bool prober = (lane & 31) < 27;
     // the 2-slot window by selects (non-probing lanes carry EMPTY keys and match nothing) ...
     const bool m0 = prober && r.s0.key == r.key;
     const bool m1 = prober && !m0 && r.s0.key != SRL_EMPTY_KEY && r.s1.key == r.key;
-    bool found = m0 || m1;
-    unsigned slab = m0 ? r.s0.slab : r.s1.slab, cnt = m0 ? r.s0.count : r.s1.count;
+    found = m0 || m1;
+    slab = m0 ? r.s0.slab : r.s1.slab; cnt = m0 ? r.s0.count : r.s1.count;
     // ... and ONE uniform branch for the rare case (< 1 % of the probes at load <= 0.25) that both slots hold other keys
     const bool more = prober && !found && r.s0.key != SRL_EMPTY_KEY && r.s1.key != SRL_EMPTY_KEY;
     if (__ballot(more) != 0ull) {
@@ -386,6 +381,24 @@ __device__ __forceinline__ int probe_finish(const ProbeReq &r, int thr_cap, cons
             }
         }
     }
+}
+// The other request form: word (lane & 31) of the home voxel's neighbour record (srl_device.h) holds the same answer, decoded here.
+// Lanes 27 .. 31 of a half-wave read the record's spare words and probe nothing.
+__device__ __forceinline__ void record_resolve(unsigned word, int lane, bool &found, unsigned &slab, unsigned &cnt) {
+    found = (lane & 31) < 27 && word != SRL_NBREC_NONE;
+    slab = word >> SRL_NBREC_COUNT_BITS;
+    cnt = word & ((1u << SRL_NBREC_COUNT_BITS) - 1u);
+}
+// Everything behind "found, slab, cnt", whichever request form answered: the occupancy threshold, P_k, the cull, and the compaction of
+// the occupied voxels of both keypoints into their lists (list h at vox + 32 h, visit order kept,
+// zero-filled up to 27 entries so the candidate rounds need no bounds branch).  Returns nv_A | nv_B << 8.
+// cull (wave-uniform): qf_pair / kv_pair = the pair's FP32 queries (8 floats per keypoint, [5] = squared cull radius) and voxel keys (4
+// ints per keypoint); a found voxel whose box lies further from the query than the radius keeps its count in P_k (the reference's loop
+// visits it) but is left out of the candidate list -- none of its points can be among the K nearest (SrlAssocArgs::bound_in)
+__device__ __forceinline__ int probe_finish(bool found, unsigned slab, unsigned cnt, int thr_cap,
+                                            VoxEnt *vox, int lane, int *ncand_pair, bool cull = false, const float *qf_pair = nullptr,
+                                            const int *kv_pair = nullptr, const LaneRole *role = nullptr, float size_voxel = 1.0f) {
+    const bool prober = (lane & 31) < 27;
     found = found && (int)cnt >= thr_cap && cnt > 0;            // NumPoints() < threshold -> skipped (optimize.cpp:389)
     // P_k of the two keypoints (the candidates the reference's loop visits, optimize.cpp:391-404) = the resident points of the
     // voxels found: added up here, once per voxel, instead of by ballots over every candidate round.  Summed across the lanes of
@@ -1461,11 +1474,31 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
         s_kv[kq * 4 + 0] = kv[0];
         s_kv[kq * 4 + 1] = kv[1];
         s_kv[kq * 4 + 2] = kv[2];
+        if constexpr (NB == 1 && FAST != 0) {
+            // the keypoint's HOME voxel looked up once, here (one lane per keypoint, off the pair loop's path): its slab, where the 27
+            // answers of phase 1 stand in one record (SrlAssocArgs::nbrec), or -1 -- the map has no such voxel, or the pass reads no
+            // records: that pair asks the table.  A keypoint behind the sweep's end files slab 0: its half of a pair is never used, and
+            // it must not send an existing partner to the table.
+            int home = A.nbrec != nullptr ? 0 : -1;
+            if (A.nbrec != nullptr && g < n_pass()) {
+                home = -1;
+                const unsigned long long key = srl_pack_key((short)kv[0], (short)kv[1], (short)kv[2]);
+                unsigned h = srl_hash_key(key) & A.table_mask;
+                for (unsigned probe = 0; probe <= A.table_mask; ++probe) {
+                    const SrlMapSlot s = A.table[h];
+                    if (s.key == key) { home = (int)s.slab; break; }
+                    if (s.key == SRL_EMPTY_KEY) break;
+                    h = (h + 1) & A.table_mask;
+                }
+            }
+            s_kv[kq * 4 + 3] = home;
+        }
         s_nfound[kq] = 0;
         s_ncand[kq] = 0;
     } else if (wave == WPB - 1 && lane < KPW + 2) {
         const int kq = KPB + (lane - KPW);                                 // the two zero entries behind the last pair
         s_kv[kq * 4 + 0] = 0; s_kv[kq * 4 + 1] = 0; s_kv[kq * 4 + 2] = 0;
+        s_kv[kq * 4 + 3] = A.nbrec != nullptr ? 0 : -1;                   // (what a keypoint behind the sweep's end files: phase 0 above)
     }
     __syncthreads();
     tile_stamp(11);
@@ -1506,16 +1539,38 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
             const LaneRole role = lane_role(lane);
             const int npairs = n_here > 0 ? (n_here + 1) >> 1 : 0;            // (an empty tile: a workgroup behind the end of a shorter sweep)
             auto take = [&]() { int p = 0; if (lane == 0) p = atomicAdd(s_next, 1); return __builtin_amdgcn_readfirstlane(p); };
+            // The request of a pair is ONE word per probing lane: word (lane & 31) of the home voxel's neighbour record, a half-wave reading
+            // one 128-byte line; issued one pair ahead, one register live across the selection.  Phase 0 filed the home slabs (s_kv[.][3]).
+            // A pair with a keypoint whose home voxel the map does not have (or a pass that reads no records) asks the table instead --
+            // probe_issue and probe_resolve back to back when the pair is consumed, inside that wave-uniform branch: the eleven registers
+            // of the table request live there alone.  Same voxels, slabs and counts either way; such a pair stays on the fast path.
+            auto home_of = [&](int pair) { return s_kv[(2 * pair + (lane >> 5)) * 4 + 3]; };
+            auto record_issue = [&](int pair) {
+                const int home = home_of(pair);
+                unsigned w = SRL_NBREC_NONE;
+                if (home >= 0) w = A.nbrec[(unsigned)home * (unsigned)SRL_NBREC_WORDS + (unsigned)(lane & 31)];
+                return w;
+            };
             int cur = take();
-            ProbeReq preq;
-            if (!(abl & 32)) preq = probe_issue(s_kv, 2 * (cur < npairs ? cur : npairs), role, A.table, A.table_mask, lane);
+            unsigned rreq = SRL_NBREC_NONE;
+            if (!(abl & 32)) rreq = record_issue(cur < npairs ? cur : npairs);
             while (cur < npairs) {
                 const int nxt = take();
-                // this pair's probes are consumed BEFORE the next pair's are issued: one probe state live at a time (no copy
-                // of the 11-register request per pair); the next pair's table loads still have the whole selection to land
-                const int nv_pair = __builtin_amdgcn_readfirstlane((abl & 8) ? 0 : probe_finish(preq, A.thr_cap, A.table, A.table_mask, vox, lane, s_ncand + 2 * cur, use_bounds, s_qf + 16 * cur,
-                                                                                                               s_kv + 8 * cur, &role, (float)A.size_voxel));
-                if (!(abl & 32)) preq = probe_issue(s_kv, 2 * (nxt < npairs ? nxt : npairs), role, A.table, A.table_mask, lane);
+                // this pair's request is consumed BEFORE the next pair's is issued; the next pair's load still has the whole selection to land
+                int nv_pair = 0;
+                if (!(abl & 8)) {
+                    bool found;
+                    unsigned slab, cnt;
+                    if (__ballot(home_of(cur) < 0) == 0ull || (abl & 32)) {      // (debug bit 32: no request of either form is issued)
+                        record_resolve(rreq, lane, found, slab, cnt);
+                    } else {
+                        const ProbeReq preq = probe_issue(s_kv, 2 * cur, role, A.table, A.table_mask, lane);
+                        probe_resolve(preq, A.table, A.table_mask, lane, found, slab, cnt);
+                    }
+                    nv_pair = probe_finish(found, slab, cnt, A.thr_cap, vox, lane, s_ncand + 2 * cur, use_bounds, s_qf + 16 * cur, s_kv + 8 * cur, &role, (float)A.size_voxel);
+                }
+                nv_pair = __builtin_amdgcn_readfirstlane(nv_pair);
+                if (!(abl & 32)) rreq = record_issue(nxt < npairs ? nxt : npairs);
                 auto file = [&](int kl, int done, int total) {        // lane 0: result of one keypoint
                     (void)total;
                     if (done == SEL_DONE) {

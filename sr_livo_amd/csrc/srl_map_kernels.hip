@@ -310,6 +310,52 @@ __global__ void k_rebuild_table(const unsigned char *slabs, int V, SrlMapSlot *t
     }
 }
 
+// Neighbour records (srl_device.h) brought up to date behind a map edit: thread (s, d) takes voxel v of the edit -- segment s of an
+// insertion (seg_slot[s] = its table slot; < 0: the batch created nothing there), or slab s when the whole map is renumbered (seg_slot
+// null) -- and looks the voxel at key(v) + offset(d) up in the table, with the probe loop every lookup here has.  Found, as slab n:
+// rec[v][d] = enc(n, count of n) and rec[n][26 - d] = enc(v, count of v) -- so a voxel the edit did not touch learns of a new or a fuller
+// neighbour; not found: rec[v][d] = none.  That covers new voxels, changed counts and two new voxels side by side.  The counts are the
+// table's, final when this kernel runs (k_replay, k_rebuild_table and the upload in front of it on the stream).
+// Writers: word rec[v][d] is written by thread (v, d) and, when the neighbour n is a voxel of the launch too, by thread (n, 26 - d), whose
+// neighbour is v again -- both store enc(n, count of n), the same value from the same table: no word ever receives two different values
+// in one launch, so nothing is ordered or atomic here.  Plain vector stores.
+#define SRL_NBREC_BLOCKS 2048
+__global__ void __launch_bounds__(256) k_nbrec_update(const int *seg_slot, const int *counters, int V, const SrlMapSlot *table, unsigned mask,
+                                                      const unsigned char *slabs, unsigned *rec) {
+    const long long S = seg_slot ? (long long)counters[0] : (long long)V;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < S * 27; i += (long long)gridDim.x * 256) {
+        const int s = (int)(i / 27), d = (int)(i - (long long)s * 27);
+        unsigned v, cnt_v;
+        unsigned long long key;
+        if (seg_slot) {
+            const int slot = seg_slot[s];
+            if (slot < 0) continue;
+            const SrlMapSlot me = table[slot];
+            v = me.slab; cnt_v = me.count; key = me.key;
+        } else {
+            const SrlSlab *sl = reinterpret_cast<const SrlSlab *>(slabs + (size_t)s * SRL_SLAB_BYTES);
+            v = (unsigned)s; cnt_v = sl->count; key = sl->key;
+        }
+        short kx, ky, kz;
+        srl_unpack_key(key, &kx, &ky, &kz);
+        const int dx = d / 9 - 1, dy = (d / 3) % 3 - 1, dz = d % 3 - 1;
+        const unsigned long long nkey = srl_pack_key((short)(kx + dx), (short)(ky + dy), (short)(kz + dz));
+        unsigned word = SRL_NBREC_NONE;
+        unsigned h = srl_hash_key(nkey) & mask;
+        for (unsigned probe = 0; probe <= mask; ++probe) {
+            const SrlMapSlot sl = table[h];
+            if (sl.key == nkey) {
+                word = srl_nbrec_enc(sl.slab, sl.count);
+                rec[(size_t)sl.slab * SRL_NBREC_WORDS + (26 - d)] = srl_nbrec_enc(v, cnt_v);
+                break;
+            }
+            if (sl.key == SRL_EMPTY_KEY) break;
+            h = (h + 1) & mask;
+        }
+        rec[(size_t)v * SRL_NBREC_WORDS + d] = word;
+    }
+}
+
 __global__ void k_fill_empty(SrlMapSlot *table, unsigned cap) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cap) return;
@@ -370,7 +416,37 @@ __global__ void __launch_bounds__(256) k_prune_compact(const unsigned char *slab
 
 unsigned next_pow2u(unsigned v) { unsigned p = 1; while (p < v) p <<= 1; return p; }
 
+// k_nbrec_update over `count` segments of an insertion (their number is read on the device: counters[0] <= count) or, seg_slot null,
+// over the `count` voxels of the map
+int nbrec_update(srl_ctx *ctx, const int *seg_slot, const int *counters, int count, hipStream_t st) {
+    if (count <= 0) return SRL_OK;
+    const long long blocks = ((long long)count * 27 + 255) / 256;
+    hipLaunchKernelGGL(k_nbrec_update, dim3((unsigned)std::min<long long>(blocks, SRL_NBREC_BLOCKS)), dim3(256), 0, st, seg_slot, counters, count, ctx->d_table,
+                       ctx->table_cap - 1, ctx->d_slabs, ctx->d_nbrec);
+    HIPCHK(ctx, hipGetLastError());
+    return SRL_OK;
+}
+
 }  // namespace
+
+// Storage of the neighbour records for `slab_cap` slabs (zeroed: the spare words of a record are never written); the records of the first
+// `keep_voxels` slabs move over -- slabs keep their indices when the storage grows.
+static_assert(SRL_MAX_SLABS < (1u << (32 - SRL_NBREC_COUNT_BITS)) - 1u, "every slab index fits a record's slab field, clear of SRL_NBREC_NONE");
+int srl_nbrec_alloc(srl_ctx *ctx, unsigned slab_cap, int keep_voxels) {
+    if (slab_cap > SRL_MAX_SLABS) { ctx->err = "map too large: a neighbour record holds 27-bit slab indices"; return SRL_ERR_UNSUPPORTED; }
+    unsigned *nr = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&nr, (size_t)slab_cap * SRL_NBREC_WORDS * sizeof(unsigned)));
+    HIPCHK(ctx, hipMemsetAsync(nr, 0, (size_t)slab_cap * SRL_NBREC_WORDS * sizeof(unsigned), ctx->stream));
+    if (ctx->d_nbrec && keep_voxels > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(nr, ctx->d_nbrec, (size_t)keep_voxels * SRL_NBREC_WORDS * sizeof(unsigned), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (the copy reads the buffer freed below; nothing to wait for when nothing moves over)
+    }
+    if (ctx->d_nbrec) HIPCHK(ctx, hipFree(ctx->d_nbrec));
+    ctx->d_nbrec = nr;
+    return SRL_OK;
+}
+// every record of the map from the table as it stands on the stream: after an upload, and wherever slabs are renumbered
+int srl_nbrec_rebuild(srl_ctx *ctx) { return nbrec_update(ctx, nullptr, nullptr, ctx->num_voxels, ctx->stream); }
 
 // lioOptimization::removePointsFarFromLocation (lioOptimization.cpp:556-572) on the device map.  The survivors keep their creation
 // order (slab index = rank among the survivors, so point ids stay slab * 20 + slot and equal those of a map rebuilt from the survivors);
@@ -421,6 +497,8 @@ extern "C" int srl_map_remove_far(srl_ctx *ctx, const double location[3], double
         hipLaunchKernelGGL(k_rebuild_table, dim3((V_new + 255) / 256), dim3(256), 0, st, ctx->d_slabs, V_new, ctx->d_table, ctx->table_cap - 1);
     HIPCHK(ctx, hipGetLastError());
     ctx->num_voxels = V_new;
+    { const int rcn = srl_nbrec_rebuild(ctx); if (rcn) return rcn; }      // the slabs were renumbered: every record anew (those behind V_new are
+                                                                          // rewritten whole when an insertion takes their slab)
     ctx->num_points -= pts_removed;
     ctx->bound_n = 0;                                   // fewer neighbours can only LENGTHEN a keypoint's K-th distance: the bounds would cull
     ctx->taps_valid = false;                            // the ids of an earlier pass refer to the old numbering
@@ -468,6 +546,8 @@ int srl_ctx_grow_map(srl_ctx *ctx, unsigned need_slabs, unsigned need_slots) {
     unsigned new_table_cap = ctx->table_cap;
     while (new_table_cap < need_slots || new_table_cap < SRL_TABLE_FACTOR * new_slab_cap) new_table_cap = next_pow2u(new_table_cap ? new_table_cap * 2u : 2048u);
     if (new_slab_cap != ctx->slab_cap) {
+        // the records first: if their allocation fails nothing has changed hands, and records for more slabs than slab_cap are harmless
+        { const int rcn = srl_nbrec_alloc(ctx, new_slab_cap, ctx->num_voxels); if (rcn) return rcn; }
         unsigned char *ns = nullptr;
         HIPCHK(ctx, hipMalloc((void **)&ns, ((size_t)new_slab_cap + 1) * SRL_SLAB_BYTES));          // + the all-inf slab
         HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)(ns + (size_t)new_slab_cap * SRL_SLAB_BYTES), 0x7f800000, SRL_SLAB_BYTES / 4, ctx->stream));
@@ -690,6 +770,8 @@ int srl_map_insert_impl(srl_ctx *ctx, const double *world_xyz, bool on_device, i
                            min_distance_points, min_num_points, cnt + 2, (unsigned char *)nullptr);
         HIPCHK(ctx, hipGetLastError());
     }
+    // the neighbour records of the voxels this batch touched and of their neighbours, behind the replay that settled their counts
+    { const int rcn = nbrec_update(ctx, b_slot.as<int>(), cnt, n, st); if (rcn) return rcn; }
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_insert_cnt, cnt, (report ? 4 : 3) * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipEventRecord(ctx->ev_insert, st));
     ctx->insert_pending = true;

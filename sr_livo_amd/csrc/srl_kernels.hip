@@ -13,7 +13,8 @@
 //                                   13-step ballot bisection on the per-lane minima -> conservative threshold -> ballot
 //                                   compaction of the ~25 survivors into LDS -> FP64 rank-by-counting, one finish per
 //                                   pair -> tie check -> libstdc++ heap replay when distances tie}
-//        phase 2  lane/keypoint   : computeNeighborhoodDistribution (optimize.cpp:316-353), weights,
+//        phase 2  LPK lanes per keypoint (p2_lanes_per_keypoint: 1 from 192 keypoints per workgroup on, 2 from 128, else 4):
+//                                   computeNeighborhoodDistribution (optimize.cpp:316-353), weights,
 //                                   plane, signed distance gate, Jacobian (optimize.cpp:42-53,85-105),
 //                                   then an in-order H^T H / H^T h partial per workgroup;
 //        fused final reduction (last workgroup of the grid), with or without the ordered cut (optimize.cpp:107).
@@ -1145,7 +1146,7 @@ __host__ __device__ inline LdsLayout lds_layout(int K, int nb_voxels, int kpw, i
     L.off_nfound = o;  o += up16(kpb * 4);
     L.off_ncand = o;   o += up16(kpb * 4);
     L.off_next = o;    o += 16;                                // workgroup counters: next pair, deferred keypoints, next deferred
-    L.off_defer = o;   o += up16(kpb * 2);                     // keypoints the fast path handed on (index | tie flag << 15)
+    L.off_defer = o;   o += up16(kpb * 2);                     // keypoints the fast path handed on (defer_encode)
     L.off_wave = o;
     int w = 0;
     L.off_vox = w;     w += (nb_voxels == 1 ? 64 : 128) * 8;   // r = 1: two 32-entry lists (a keypoint pair is probed at once)
@@ -1159,6 +1160,14 @@ __host__ __device__ inline LdsLayout lds_layout(int K, int nb_voxels, int kpw, i
     L.total = o;
     return L;
 }
+
+// s_winfo (LdsLayout::off_winfo) [w * WI_STRIDE + slot]: WI_FALLBACK is filed per wave (its phase-1 work), the others per phase-2 slot
+enum { WI_ACCEPTED = 0, WI_SUM_PK = 1, WI_NAN_FIRST = 2 /* 1 + keypoint inside the workgroup; 0: none */, WI_FALLBACK = 3, WI_PLANES = 4,
+       WI_MASK_LO = 5, WI_MASK_HI = 6 /* accepted keypoints of the slot, bit i = its keypoint i */, WI_STRIDE = 8 };
+// an entry of the deferred list: the keypoint (index inside the workgroup) the fast path handed on, and whether for a tie
+__device__ __forceinline__ unsigned short defer_encode(int kl, bool tie) { return (unsigned short)(kl | (tie ? 0x8000 : 0)); }
+struct Deferred { int kl; bool tie; };
+__device__ __forceinline__ Deferred defer_decode(int e) { Deferred d; d.kl = e & 0x7FFF; d.tie = (e & 0x8000) != 0; return d; }
 
 
 // FAST: 0 = general path only, 1 = FP32-prefilter fast path (r = 1: keypoint pairs, rounds in registers; r = 2: looped)
@@ -1174,6 +1183,22 @@ __host__ __device__ inline LdsLayout lds_layout(int K, int nb_voxels, int kpw, i
 typedef const __attribute__((address_space(4))) char *KargBytes;
 #else
 typedef const char *KargBytes;
+#endif
+// The pass's arguments RE-READ from the kernarg segment (the struct is the kernel's first argument) through a laundered pointer:
+// kept live across phase 1 they cost ~70 SGPRs and pushed the selection loop into SGPR spills (v_readlane / v_writelane), so
+// every step behind phase 1 asks again -- scalar loads from a segment that is in the constant cache anyway.
+// A POINTER, here and in the steps' parameters: a reference would tell the compiler that the whole struct may be loaded ahead of
+// the branches that ask for a member (dereferenceable), and it does so -- the same SGPRs again.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) SrlAssocArgs KernArgs;
+__device__ __forceinline__ KernArgs *kernarg_reread(KargBytes karg) {
+    KernArgs *p = (KernArgs *)karg;
+    asm volatile("" : "+s"(p));
+    return p;
+}
+#else
+typedef const SrlAssocArgs KernArgs;
+__device__ inline KernArgs *kernarg_reread(KargBytes karg) { return reinterpret_cast<KernArgs *>(karg); }   // (host pass: the plain argument)
 #endif
 // one 64-bit word as two tagged granules {tag, low half} {tag, high half} in ONE 16-byte system-scope store: the lanes of a wave
 // write consecutive 16-byte chunks, i.e. whole 64-byte lines (52 lanes = 13 lines) -- as 8-byte stores at stride 16 the same bytes
@@ -1294,9 +1319,7 @@ __device__ __forceinline__ void arm_stamp(KargBytes karg, int slot) {
 #if !defined(SRL_STAMP_DETAIL)
     if (slot >= 16) return;
 #endif
-    typedef const __attribute__((address_space(4))) SrlAssocArgs *KP;
-    KP q = (KP)karg;
-    asm volatile("" : "+s"(q));
+    KernArgs *q = kernarg_reread(karg);
     long long *st = q->stamps;
     if (st != nullptr && threadIdx.x == 0) {
         const bool first = blockIdx.x == 0, last = blockIdx.x == gridDim.x - 1;
@@ -1309,21 +1332,21 @@ __device__ __forceinline__ void arm_stamp(KargBytes karg, int slot) {
 __device__ inline void arm_stamp(KargBytes, int) {}
 #endif
 
-// Phase 2 geometry: lanes per keypoint and keypoints per phase-2 wave for a workgroup of kpb keypoints.  One lane per
-// keypoint from 48 keypoints on.  (Half-filled phase-2 waves -- 32 keypoints each, twice as many waves so that two dependent
-// FP64 chains interleave per SIMD -- were measured in round 3: no gain)
-#ifndef SRL_P2_POLICY
-#define SRL_P2_POLICY 1
-#endif
-#if SRL_P2_POLICY == 0
-__host__ __device__ constexpr int p2_lanes_per_keypoint(int kpb) { return kpb >= 48 ? 1 : (kpb >= 32 ? 2 : 4); }     // rounds 2-3
-#else
-// Round 4: small workgroups spread a keypoint over four lanes (the neighbour loops are a 20-deep FP64 dependency chain on a wave that
-// has its SIMD to itself; with four lanes it is 5 deep + two quad-permute steps, and the phase occupies 4-6 of the 16 waves instead
-// of 1-2).  Workgroups of >= 192 keypoints keep one lane per keypoint: there the phase is bound by instruction issue, not by the chain.
+// Phase 2 geometry for a workgroup of kpb keypoints: LPK lanes per keypoint, 64 / LPK keypoints per phase-2 wave.  Small workgroups
+// spread a keypoint over four lanes (the neighbour loops are a 20-deep FP64 dependency chain on a wave that has its SIMD to itself;
+// with four lanes it is 5 deep + two quad-permute steps, and the phase occupies 4-6 of the 16 waves instead of 1-2; the lanes of a
+// keypoint split its neighbours and butterfly the sums).  Workgroups of >= 192 keypoints keep ONE lane per keypoint, those of 128
+// take two: there the phase is bound by instruction issue, not by the chain.  With one lane per keypoint the neighbour-plane reads
+// are conflict-free and the barycentre / scatter sums run sequentially over the neighbours, the reference's own order
+// (optimize.cpp:320-337).
+// History: until round 2 every keypoint had four lanes that ran the scalar part -- eigen-decomposition, weights, gate, Jacobian:
+// most of this phase -- redundantly, so 16 keypoints cost a wave ~800 instructions: 16 waves x 800 per 256 keypoints against
+// 4 x ~700 afterwards (headline: -3 us).  Rounds 2-3 ran one lane per keypoint from 48 keypoints on (two / four for 32 / 16); the
+// rule above is round 4's.  Half-filled phase-2 waves -- 32 keypoints each, twice as many waves so that two dependent FP64 chains
+// interleave per SIMD -- were measured in round 3: no gain, DESIGN.md 9.
 __host__ __device__ constexpr int p2_lanes_per_keypoint(int kpb) { return kpb >= 192 ? 1 : (kpb >= 128 ? 2 : 4); }
-#endif
 __host__ __device__ constexpr int p2_keypoints_per_wave(int kpb) { return 64 / p2_lanes_per_keypoint(kpb); }
+__host__ __device__ constexpr int p2_waves(int kpb) { return (kpb + p2_keypoints_per_wave(kpb) - 1) / p2_keypoints_per_wave(kpb); }
 
 // ARMED = 1: the pass as an armed launch (assoc_body's prologue): the pose sits in LDS, not in the kernarg segment.
 // DBG = 1: the instantiation the profiling tools run (srl_debug_set_ablate: parts of the kernel switched off at run time, workgroup
@@ -1357,12 +1380,9 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
     VoxEnt *vox = reinterpret_cast<VoxEnt *>(wbase + L.off_vox);
     Surv *surv = reinterpret_cast<Surv *>(wbase + L.off_scratch);
     double *s_wpart = reinterpret_cast<double *>(smem + L.off_wpart);     // [4][32]
-    int *s_winfo = reinterpret_cast<int *>(smem + L.off_winfo);           // [WPB][8]: accepted, sum_pk, 1 + first NaN keypoint, fallback, planes
+    int *s_winfo = reinterpret_cast<int *>(smem + L.off_winfo);           // [WPB][WI_STRIDE]
 
     const long long dbg_t0 = (DBG && (abl & 128)) ? (long long)wall_clock64() : 0;   // debug: workgroup start (100 MHz clock)
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) SrlAssocArgs *KernargPtr;
-#endif
     double *s_pose = reinterpret_cast<double *>(smem + L.off_pose);       // armed launch: Rn[9] | R[9] | t[3] of this pass
     // keypoints of this pass: an armed launch learns the count with its pose (it may have been fired for ANOTHER sweep than the one it was
     // armed on -- srl_sweep_swap --, the grid stays the one it was launched with: workgroups behind the sweep's end find empty tiles).
@@ -1577,7 +1597,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
                         // (the candidate total P_k was filed by probe_finish -- every found voxel, also those the bounds let this pass skip;
                         //  the loads of cand_issue count only what was visited)
                     } else {
-                        s_defer[atomicAdd(s_next + 1, 1)] = (unsigned short)(kl | (done == SEL_TIE ? 0x8000 : 0));
+                        s_defer[atomicAdd(s_next + 1, 1)] = defer_encode(kl, done == SEL_TIE);
                     }
                 };
                 // ceil(nv / 3) for nv <= 27 as a multiply-shift (the signed / 3 went through s_mul_hi)
@@ -1597,8 +1617,8 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
                     (void)total_a; (void)total_b;
                     if (done != (SEL_DONE | (SEL_DONE << 8))) {
                         if (lane == 0) {
-                            if ((done & 0xFF) != SEL_DONE) s_defer[atomicAdd(s_next + 1, 1)] = (unsigned short)(kl | ((done & 0xFF) == SEL_TIE ? 0x8000 : 0));
-                            if ((done >> 8) != SEL_DONE) s_defer[atomicAdd(s_next + 1, 1)] = (unsigned short)((kl + 1) | ((done >> 8) == SEL_TIE ? 0x8000 : 0));
+                            if ((done & 0xFF) != SEL_DONE) s_defer[atomicAdd(s_next + 1, 1)] = defer_encode(kl, (done & 0xFF) == SEL_TIE);
+                            if ((done >> 8) != SEL_DONE) s_defer[atomicAdd(s_next + 1, 1)] = defer_encode(kl + 1, (done >> 8) == SEL_TIE);
                         }
                     }
                 } else {
@@ -1636,7 +1656,7 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
                         s_nfound[kl] = total < Kn ? total : Kn;
                         s_ncand[kl] = total;
                     } else {
-                        s_defer[atomicAdd(s_next + 1, 1)] = (unsigned short)(kl | (done == SEL_TIE ? 0x8000 : 0));
+                        s_defer[atomicAdd(s_next + 1, 1)] = defer_encode(kl, done == SEL_TIE);
                     }
                 }
             }
@@ -1651,8 +1671,8 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
             if (n_defer > 0) {
                 auto take2 = [&]() { int p = 0; if (lane == 0) p = atomicAdd(s_next + 2, 1); return __builtin_amdgcn_readfirstlane(p); };
                 for (int i = take2(); i < n_defer; i = take2()) {
-                    const int e = __builtin_amdgcn_readfirstlane((int)s_defer[i]);
-                    keypoint_general(e & 0x7FFF, (e & 0x8000) != 0);
+                    const Deferred d = defer_decode(__builtin_amdgcn_readfirstlane((int)s_defer[i]));
+                    keypoint_general(d.kl, d.tie);
                 }
             }
         }
@@ -1661,27 +1681,15 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
     tile_stamp(12);
 
     if (abl & 64) return true;                              // debug: phase 0 + loop skeleton only
-    // Phase 2 re-reads its parameters from the kernarg segment through a laundered pointer: kept live across phase 1
-    // they cost ~70 SGPRs and pushed the selection loop into SGPR spills (v_readlane / v_writelane).
-#if defined(__HIP_DEVICE_COMPILE__)
-    KernargPtr bp = (KernargPtr)karg;     // the struct is the kernel's first argument
-    asm volatile("" : "+s"(bp));
-    const __attribute__((address_space(4))) SrlAssocArgs &b = *bp;
-#else
-    const SrlAssocArgs &b = A;
-#endif
-    // ---------------- phase 2: plane fit + residual + Jacobian.  LPK lanes per keypoint: ONE when the workgroup has at least
-    // 48 keypoints (its KPB keypoints then fill ceil(KPB / 64) waves and the other waves have nothing to do here), two / four
-    // for workgroups of 32 / 16 keypoints (one wave either way; the lanes of a keypoint split its neighbours and butterfly the
-    // sums, so the serial chain stays short where there is nothing to amortise).  Until round 2 every keypoint had four
-    // lanes that ran the scalar part -- eigen-decomposition, weights, gate, Jacobian: most of this phase -- redundantly, so 16
-    // keypoints cost a wave ~800 instructions: 16 waves x 800 per 256 keypoints against 4 x ~700 now (headline: -3 us).
-    // Which waves work rotates with the workgroup index, so that the phase-2 waves of workgroups sharing a CU sit on
-    // different SIMDs.  With one lane per keypoint the neighbour-plane reads are conflict-free and the barycentre / scatter
-    // sums run sequentially over the neighbours, the reference's own order (optimize.cpp:320-337).
+    // Phase 2 re-reads its parameters from the kernarg segment (kernarg_reread): nothing of A stays live across phase 1
+    KernArgs &b = *kernarg_reread(karg);
+    // ---------------- phase 2: plane fit + residual + Jacobian, LPK lanes per keypoint (p2_lanes_per_keypoint above: one from 192
+    // keypoints per workgroup on, two from 128, else four; its KPB keypoints fill P2W waves and the other waves have nothing to do
+    // here).  Which waves work rotates with the workgroup index, so that the phase-2 waves of workgroups sharing a CU sit on
+    // different SIMDs.
     constexpr int LPK = p2_lanes_per_keypoint(KPB);                                  // lanes per keypoint
     constexpr int KP2 = p2_keypoints_per_wave(KPB);                                  // keypoints per phase-2 wave
-    constexpr int P2W = (KPB + KP2 - 1) / KP2;
+    constexpr int P2W = p2_waves(KPB);
     const int w2 = (wave + WPB - (int)(blockIdx.x % WPB)) % WPB;                    // phase-2 slot of this wave
     const bool p2_wave = w2 < P2W;
     const int klw = lane / LPK, sl = lane % LPK;                                    // keypoint inside this wave, sub-lane
@@ -1892,17 +1900,17 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) pk += __shfl_xor(pk, off);
         if (lane == 0) {
-            s_winfo[wave * 8 + 3] = n_fallback;                 // phase-1 work of THIS wave
+            s_winfo[wave * WI_STRIDE + WI_FALLBACK] = n_fallback;                 // phase-1 work of THIS wave
             if (p2_wave) {                                       // phase-2 results, filed under the phase-2 slot
-                s_winfo[w2 * 8 + 0] = __popcll(acc_mask);
-                s_winfo[w2 * 8 + 1] = pk;
+                s_winfo[w2 * WI_STRIDE + WI_ACCEPTED] = __popcll(acc_mask);
+                s_winfo[w2 * WI_STRIDE + WI_SUM_PK] = pk;
                 // first NaN keypoint of this wave as 1 + index inside the workgroup
-                s_winfo[w2 * 8 + 2] = nan_mask ? 1 + w2 * KP2 + (int)__builtin_ctzll(nan_mask) / LPK : 0;
-                s_winfo[w2 * 8 + 4] = __popcll(pln_mask);
+                s_winfo[w2 * WI_STRIDE + WI_NAN_FIRST] = nan_mask ? 1 + w2 * KP2 + (int)__builtin_ctzll(nan_mask) / LPK : 0;
+                s_winfo[w2 * WI_STRIDE + WI_PLANES] = __popcll(pln_mask);
                 // accepted keypoints of this wave (bit i = keypoint w2 * KP2 + i), as two 32-bit words
                 const unsigned long long km = per_keypoint(acc_mask);
-                s_winfo[w2 * 8 + 5] = (int)(unsigned)km;
-                s_winfo[w2 * 8 + 6] = (int)(unsigned)(km >> 32);
+                s_winfo[w2 * WI_STRIDE + WI_MASK_LO] = (int)(unsigned)km;
+                s_winfo[w2 * WI_STRIDE + WI_MASK_HI] = (int)(unsigned)(km >> 32);
             }
         }
     }
@@ -1923,11 +1931,11 @@ __device__ __forceinline__ bool assoc_tile(KargBytes karg, const SrlAssocArgs &A
         SrlBlockInfo bi;
         bi.accepted = 0; bi.sum_pk = 0; bi.nan_first = 0; bi.num_fallback = 0; bi.planes = 0;
         bi.pad[0] = bi.pad[1] = bi.pad[2] = 0;
-        for (int w = 0; w < WPB; ++w) bi.num_fallback += s_winfo[w * 8 + 3];
+        for (int w = 0; w < WPB; ++w) bi.num_fallback += s_winfo[w * WI_STRIDE + WI_FALLBACK];
         for (int w = 0; w < P2W; ++w) {
-            bi.accepted += s_winfo[w * 8 + 0]; bi.sum_pk += (unsigned)s_winfo[w * 8 + 1];
-            if (bi.nan_first == 0) bi.nan_first = s_winfo[w * 8 + 2];       // slots in keypoint order: the first one wins
-            bi.planes += s_winfo[w * 8 + 4];
+            bi.accepted += s_winfo[w * WI_STRIDE + WI_ACCEPTED]; bi.sum_pk += (unsigned)s_winfo[w * WI_STRIDE + WI_SUM_PK];
+            if (bi.nan_first == 0) bi.nan_first = s_winfo[w * WI_STRIDE + WI_NAN_FIRST];       // slots in keypoint order: the first one wins
+            bi.planes += s_winfo[w * WI_STRIDE + WI_PLANES];
         }
         b.binfo[blockIdx.x] = bi;
     }
@@ -1986,11 +1994,8 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int KPB = WPB * KPW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    typedef const __attribute__((address_space(4))) SrlAssocArgs *KernargPtr;
     typedef __attribute__((address_space(1))) unsigned long long gu64;
-    KernargPtr bq = (KernargPtr)karg;
-    asm volatile("" : "+s"(bq));
-    const __attribute__((address_space(4))) SrlAssocArgs &b = *bq;
+    KernArgs &b = *kernarg_reread(karg);
     const int tid = threadIdx.x;
     const int lane = lane_id();
     const int wave = tid >> 6;
@@ -2230,20 +2235,95 @@ __device__ __forceinline__ void finish_rows(KargBytes karg, const unsigned epoch
 #endif
 }
 
+// ---------------- fused final reduction: every workgroup publishes its row, the LAST workgroup of the grid finishes.
+// Row = 28 partial sums + {accepted, candidates visited, NaN flag, off-fast-path keypoints} carried as doubles (threads 0..31).
+// Hand-off across the 8 XCDs (private L2s) in the "data is the flag" form of guide G16 (R2): every double travels as
+// two 8-byte granules {epoch, 32-bit half}, stored write-through at agent scope -- ONE store instruction per workgroup,
+// no drain, no counter, no fence; the finisher re-reads the granules it needs (agent-scope loads) until every tag
+// carries this launch's epoch, then sums the rows in a fixed order.  (Round-2 first version: drained row + two-level
+// arrival counters = three dependent memory round trips behind the last workgroup, +5.6 us on the 64k launch.)
+// A stale granule has an older epoch (the epoch is the context's launch sequence number), so nothing is reset
+// between launches.  The finisher only waits for results every other workgroup produces without it: no co-residency
+// assumption; its spin is bounded (time-out marker in the mailbox, the host turns it into an error).
+
+// component tid < 32 of this workgroup's row.  reads: s_wpart, s_winfo
+template <int NB, int KPW, int WPB, int ARMED>
+__device__ __forceinline__ double tile_row(const int Kn, const int tid) {
+    constexpr int P2W = p2_waves(WPB * KPW);
+    double row_v = 0.0;
+    if (tid < 32) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+        const LdsLayout L = lds_layout(Kn, NB, KPW, WPB, ARMED);
+        const double *s_wpart = reinterpret_cast<const double *>(smem + L.off_wpart);     // [P2W][32]
+        const int *s_winfo = reinterpret_cast<const int *>(smem + L.off_winfo);           // [WPB][WI_STRIDE]
+        double v = 0.0;
+        if (tid < SRL_ROW_SUMS) {
+            v = s_wpart[tid];
+#pragma unroll
+            for (int w = 1; w < P2W; ++w) v += s_wpart[w * 32 + tid];
+        } else {
+            int acc = 0, pk = 0, nanf = 0, fb = 0;
+            for (int w = 0; w < WPB; ++w) fb += s_winfo[w * WI_STRIDE + WI_FALLBACK];
+            // nanf: 1 + index inside the tile of its first NaN-planarity keypoint (slots are in keypoint order), 0 = none
+            for (int w = 0; w < P2W; ++w) {
+                const int *wi = s_winfo + w * WI_STRIDE;
+                acc += wi[WI_ACCEPTED]; pk += wi[WI_SUM_PK]; if (nanf == 0) nanf = wi[WI_NAN_FIRST];
+            }
+            v = tid == SRL_ROW_ACCEPTED ? (double)acc : (tid == SRL_ROW_SUM_PK ? (double)(unsigned)pk : (tid == SRL_ROW_NAN ? (double)nanf : (double)fb));
+        }
+        row_v = v;
+    }
+    return row_v;
+}
+// files: the row (a finishing workgroup: in LDS at SRL_OWN_ROW_OFFSET), with an ordered cut also the accept-mask granules (reads s_winfo)
+template <int NB, int KPW, int WPB, int ARMED>
+__device__ __forceinline__ void publish_row(KernArgs *const bp, const int tid, const unsigned epoch, const bool finishes, const double row_v) {
+    KernArgs &b = *bp;
+    constexpr int KPB = WPB * KPW, KP2 = p2_keypoints_per_wave(KPB), P2W = p2_waves(KPB);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    typedef __attribute__((address_space(1))) unsigned long long gu64;
+    const LdsLayout L = lds_layout(b.K, NB, KPW, WPB, ARMED);
+    const int *s_winfo = reinterpret_cast<const int *>(smem + L.off_winfo);
+    if (tid < 32) {
+        // lane l publishes component l of the row (row_store: one 16-byte write-through store); the finishing workgroup keeps its own
+        // row in LDS -- read back through memory it was the row the finisher's first poll always missed
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (finishes) reinterpret_cast<double *>(smem + SRL_OWN_ROW_OFFSET)[tid] = row_v;
+        else row_store(rows_rsrc(b.granules), (int)blockIdx.x, tid, epoch, row_v);
+#endif
+    } else if (tid >= 64 && tid < 72 && b.cut_max > 0) {
+        // granules 64..71: which keypoints of this workgroup were accepted (bit i = keypoint i), 32 per granule
+        const int j = tid - 64;
+        unsigned word = 0u;
+        if (KP2 >= 32) {
+            const int w = (32 * j) / KP2;
+            if (w < P2W) word = (unsigned)s_winfo[w * WI_STRIDE + WI_MASK_LO + (((32 * j) % KP2) >> 5)];
+        } else {
+#pragma unroll
+            for (int t = 0; t < 32 / KP2; ++t) {
+                const int w = (32 * j) / KP2 + t;
+                if (w < P2W) word |= (unsigned)s_winfo[w * WI_STRIDE + WI_MASK_LO] << (t * KP2);
+            }
+        }
+        __hip_atomic_store((gu64 *)(b.granules + (size_t)blockIdx.x * SRL_ROW_GRANULES + tid), ((unsigned long long)epoch << 32) | word,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// One pass of one workgroup: (armed: the prologue that waits for the pose,) the tile, then -- unless the reduce kernel follows -- the
+// fused final reduction: tile_row, publish_row, finish_rows.
+// The LDS carve is re-derived from max_number_neighbors wherever it is needed, with the plain casts: kept in registers its dozen
+// offsets come out of the selection loop's budget (the kernel runs at 114-116 of 128 VGPRs and at the SGPR limit), and gathered into
+// one struct of typed pointers the same casts cost the r = 1 fast-path instantiations a VGPR and two to six SGPR spills (HISTORY.md).
 template <int NB, int FAST, int KPW, int WPB, int DBG = 0, int ARMED = 0>
 __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
-    constexpr int KPB = WPB * KPW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     if (a.ablate & 16) return;                                            // debug: launch/drain floor
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) SrlAssocArgs *KernargPtr;
-#endif
-    // the LDS carve is re-derived from max_number_neighbors wherever it is needed: kept in registers its dozen offsets come out of
-    // the selection loop's budget (the kernel runs at 121 of 128 VGPRs and at the SGPR limit)
-    auto carve = [&]() -> LdsLayout { return lds_layout(a.K, NB, KPW, WPB, ARMED); };
+    const KargBytes karg = (KargBytes)__builtin_amdgcn_kernarg_segment_ptr();
     if constexpr (ARMED) {
 #if defined(__HIP_DEVICE_COMPILE__)
+        constexpr int KPB = WPB * KPW;
         // ---- ARMED launch (srl_capi.cpp: arm_next): this kernel was enqueued while the pass before it was still running, before
         // its pose existed; its workgroups are resident and waiting when the host has finished the 17-dim update, so the launch call,
         // the dispatch and the ramp of this pass are off the per-iteration critical path.  The pose (Rn[9] R[9] t[3], the only
@@ -2254,7 +2334,7 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
         // A tag NEWER than this launch's epoch means the host has moved on: cancelled.  The wait is bounded (arm_linger_ticks of
         // the 100 MHz clock; the host never fires a launch that old, so the bound is a safety net, not a protocol step).
         typedef __attribute__((address_space(1))) unsigned long long gu64a;
-        const LdsLayout L = carve();
+        const LdsLayout L = lds_layout(a.K, NB, KPW, WPB, ARMED);
         double *s_pose = reinterpret_cast<double *>(smem + L.off_pose);
         int *s_ctrl = reinterpret_cast<int *>(s_pose + SRL_POSE_DOUBLES);
         arm_stamp((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), 0);
@@ -2376,86 +2456,20 @@ __device__ __forceinline__ void assoc_body(const SrlAssocArgs &a) {
         }
 #endif
     }
-    if (assoc_tile<NB, FAST, KPW, WPB, DBG, ARMED>((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), a, (int)blockIdx.x)) return;
-    double row_v = 0.0;                                                   // tid < 32: component tid of this workgroup's row
-    constexpr int P2W_T = (KPB + p2_keypoints_per_wave(KPB) - 1) / p2_keypoints_per_wave(KPB);
-    // ---- the workgroup's row: 28 partial sums + {accepted, candidates visited, NaN flag,
-    // off-fast-path keypoints} carried as doubles (threads 0..31)
-    if (tid < 32) {
-        const LdsLayout L = carve();
-        const double *s_wpart = reinterpret_cast<const double *>(smem + L.off_wpart);     // [P2W][32]
-        const int *s_winfo = reinterpret_cast<const int *>(smem + L.off_winfo);           // [WPB][8]: accepted, sum_pk, 1 + first NaN keypoint, fallback, planes
-        double v = 0.0;
-        if (tid < SRL_ROW_SUMS) {
-            v = s_wpart[tid];
-#pragma unroll
-            for (int w = 1; w < P2W_T; ++w) v += s_wpart[w * 32 + tid];
-        } else {
-            int acc = 0, pk = 0, nanf = 0, fb = 0;
-            for (int w = 0; w < WPB; ++w) fb += s_winfo[w * 8 + 3];
-            // nanf: 1 + index inside the tile of its first NaN-planarity keypoint (slots are in keypoint order), 0 = none
-            for (int w = 0; w < P2W_T; ++w) { acc += s_winfo[w * 8 + 0]; pk += s_winfo[w * 8 + 1]; if (nanf == 0) nanf = s_winfo[w * 8 + 2]; }
-            v = tid == SRL_ROW_ACCEPTED ? (double)acc : (tid == SRL_ROW_SUM_PK ? (double)(unsigned)pk : (tid == SRL_ROW_NAN ? (double)nanf : (double)fb));
-        }
-        row_v = v;
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-    KernargPtr bq = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(bq));
-    const __attribute__((address_space(4))) SrlAssocArgs &b = *bq;
-#else
-    const SrlAssocArgs &b = a;
-#endif
-    const LdsLayout L = lds_layout(b.K, NB, KPW, WPB, ARMED);
-    const int *s_winfo = reinterpret_cast<const int *>(smem + L.off_winfo);
-
-    // ---------------- fused final reduction: every workgroup publishes its row, the LAST workgroup of the grid finishes.
-    // Row = 28 partial sums + {accepted, candidates visited, NaN flag, off-fast-path keypoints} carried as doubles.
-    // Hand-off across the 8 XCDs (private L2s) in the "data is the flag" form of guide G16 (R2): every double travels as
-    // two 8-byte granules {epoch, 32-bit half}, stored write-through at agent scope -- ONE store instruction per workgroup,
-    // no drain, no counter, no fence; the finisher re-reads the granules it needs (agent-scope loads) until every tag
-    // carries this launch's epoch, then sums the rows in a fixed order.  (Round-2 first version: drained row + two-level
-    // arrival counters = three dependent memory round trips behind the last workgroup, +5.6 us on the 64k launch.)
-    // A stale granule has an older epoch (the epoch is the context's launch sequence number), so nothing is reset
-    // between launches.  The finisher only waits for results every other workgroup produces without it: no co-residency
-    // assumption; its spin is bounded (time-out marker in the mailbox, the host turns it into an error).
-    typedef __attribute__((address_space(1))) unsigned long long gu64;
+    if (assoc_tile<NB, FAST, KPW, WPB, DBG, ARMED>(karg, a, (int)blockIdx.x)) return;
+    const double row_v = tile_row<NB, KPW, WPB, ARMED>(a.K, tid);
+    KernArgs &b = *kernarg_reread(karg);
     const unsigned epoch = (unsigned)b.seq;
-    constexpr int KP2 = p2_keypoints_per_wave(KPB);                       // keypoints per phase-2 wave (as in phase 2)
-    constexpr int P2W = (KPB + KP2 - 1) / KP2;
     // the grid's last workgroup finishes; in a grid of more than two groups also the last workgroup of every group (two-level reduction)
     const bool finishes = blockIdx.x == gridDim.x - 1 ||
                           (b.cut_max == 0 && (int)gridDim.x > 2 * SRL_FUSED_GROUP && ((int)blockIdx.x % SRL_FUSED_GROUP) == SRL_FUSED_GROUP - 1);
-    if (tid < 32) {
-        // lane l publishes component l of the row (row_store: one 16-byte write-through store); the finishing workgroup keeps its own
-        // row in LDS -- read back through memory it was the row the finisher's first poll always missed
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (finishes) reinterpret_cast<double *>(smem + SRL_OWN_ROW_OFFSET)[tid] = row_v;
-        else row_store(rows_rsrc(b.granules), (int)blockIdx.x, tid, epoch, row_v);
-#endif
-    } else if (tid >= 64 && tid < 72 && b.cut_max > 0) {
-        // granules 64..71: which keypoints of this workgroup were accepted (bit i = keypoint i), 32 per granule
-        const int j = tid - 64;
-        unsigned word = 0u;
-        if (KP2 >= 32) {
-            const int w = (32 * j) / KP2;
-            if (w < P2W) word = (unsigned)s_winfo[w * 8 + 5 + (((32 * j) % KP2) >> 5)];
-        } else {
-#pragma unroll
-            for (int t = 0; t < 32 / KP2; ++t) {
-                const int w = (32 * j) / KP2 + t;
-                if (w < P2W) word |= (unsigned)s_winfo[w * 8 + 5] << (t * KP2);
-            }
-        }
-        __hip_atomic_store((gu64 *)(b.granules + (size_t)blockIdx.x * SRL_ROW_GRANULES + tid), ((unsigned long long)epoch << 32) | word,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if constexpr (ARMED) arm_stamp((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), 6);
+    publish_row<NB, KPW, WPB, ARMED>(&b, tid, epoch, finishes, row_v);
+    if constexpr (ARMED) arm_stamp(karg, 6);
     if (!finishes) return;
     int n_total = b.n;
-    if constexpr (ARMED) n_total = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(smem + L.off_pose + SRL_POSE_DOUBLES * 8)[1]);   // the count that came with the pose
-    finish_rows<KPW, WPB>((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), epoch, n_total);
-    if constexpr (ARMED) arm_stamp((KargBytes)__builtin_amdgcn_kernarg_segment_ptr(), 7);
+    if constexpr (ARMED) n_total = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(smem + lds_layout(b.K, NB, KPW, WPB, ARMED).off_pose + SRL_POSE_DOUBLES * 8)[1]);   // the count that came with the pose
+    finish_rows<KPW, WPB>(karg, epoch, n_total);
+    if constexpr (ARMED) arm_stamp(karg, 7);
 }
 
 template <int NB, int FAST, int KPW, int WPB, int DBG = 0>

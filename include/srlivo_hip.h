@@ -633,6 +633,84 @@ int srl_image_prepare_resized(srl_ctx *ctx, const uint8_t *raw_bgr, int src_rows
 int srl_image_prep_download(srl_ctx *ctx, int which /* 0 gray_eq, 1 bgr_eq */, uint8_t *out, int64_t row_stride_bytes);
 int srl_flow_track_prepared(srl_ctx *ctx, const float *prev_xy, int n, float *next_xy, uint8_t *status, int *n_tracked);
 
+/* ------------------------------------------------------------------ compressed camera frames: baseline JPEG into the image preparer
+ * replaces: lioOptimization::compressedImageHandler (lioOptimization.cpp:640-664), whose cv_bridge::toCvCopy(msg, BGR8) decodes a
+ * sensor_msgs/CompressedImage on the host.  The decode is split where the format splits: the entropy-coded scan is ONE sequential bit
+ * stream and is decoded on the host (srl_jpeg_parse, srl_jpeg_entropy_decode: plain C++, no device, no allocation); everything behind
+ * it is independent per block and per pixel and runs on the device.  The operations are libjpeg's default decode path -- JDCT_ISLOW,
+ * "fancy" triangle upsampling, the 16-bit fixed-point colour tables -- which is integer arithmetic from the coefficient to the byte and
+ * is restated here in full; tests/jpeg_checker.py restates it independently and is compared bytewise with libjpeg-turbo's decode.
+ * Accepted: SOF0 with 8-bit samples and 8-bit quantisation tables; one component, or three with luma sampling 1x1, 2x1 or 2x2 and
+ * chroma 1x1 (4:4:4, 4:2:2, 4:2:0); one scan that holds every component in the frame's order; any restart interval; APPn, COM and other
+ * segments with a length are skipped.  SRL_ERR_UNSUPPORTED: every other frame type (extended, progressive, lossless, arithmetic), another
+ * sample precision, 16-bit tables, two or four components, any other sampling (4:4:0, 4:1:1), a scan that holds fewer components than the
+ * frame, zero rows (DNL).  SRL_ERR_BAD_ARG, everything malformed: NULL arguments; no SOI; a segment length beyond the buffer; a marker
+ * that carries no segment in front of the scan; a second SOF0 or SOS before SOF0; zero columns or components; sampling factors outside
+ * 1 ... 4; table selectors above 3; Huffman counts that form no prefix code; a table the scan names but no segment defined; Ss, Se, Ah, Al
+ * other than 0, 63, 0; in the scan: a code that is in no table, a DC category above 15, a DC value leaving int16_t, a run past coefficient
+ * 63 (a ZRL that reaches it included), a restart marker that is missing, wrong, or preceded by a whole unread byte, data ending before
+ * the last MCU (after the last byte nothing is invented); capacity_blocks below info->total_blocks; an *info that is not this stream's.
+ * srl_jpeg_info: the sampling factors of one component read 1 x 1 (its scan is not interleaved); MCUs are 8 h[0] x 8 v[0] pixels;
+ * blocks[c] = mcus_per_row h[c] mcus_per_col v[c] blocks of 64 coefficients, the component plane padded to whole MCUs; scan_offset is
+ * the first entropy-coded byte.  A refused srl_jpeg_parse leaves *info untouched.
+ * srl_jpeg_entropy_decode writes the QUANTISED coefficients in natural (row-major) order, the zig-zag undone while storing: component
+ * after component, within one the blocks in raster order of its padded plane (block (by, bx) at by mcus_per_row h[c] + bx).  DC
+ * prediction per component, reset at every RSTn.  qt[c] is component c's quantisation table in natural order (rows of absent components
+ * are left alone).  Refusals found before the scan's first bit leave coef and qt untouched; a refusal inside the scan leaves coef partly
+ * decoded (it is decoded in place, in one pass) and qt untouched.  The decoder never reads at or beyond bytes + n.
+ *
+ * Device operations, integer arithmetic only, no atomics: the same bytes call after call.  >> is an arithmetic shift.
+ * (i) IDCT per block (jidctint.c), d[r][c] = coef[r][c] qt[r][c], CONST_BITS 13, PASS1_BITS 2, DESCALE(x, n) = (x + (1 << (n - 1))) >> n.
+ *     One 1-D pass on eight values d0 ... d7:
+ *       z1 = (d2 + d6) 4433; t2 = z1 - d6 15137; t3 = z1 + d2 6270; t0 = (d0 + d4) << 13; t1 = (d0 - d4) << 13;
+ *       t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2;
+ *       z1 = d7 + d1; z2 = d5 + d3; z3 = d7 + d3; z4 = d5 + d1; z5 = (z3 + z4) 9633;
+ *       o0 = d7 2446; o1 = d5 16819; o2 = d3 25172; o3 = d1 12299; z1 = -z1 7373; z2 = -z2 20995; z3 = -z3 16069 + z5; z4 = -z4 3196 + z5;
+ *       o0 += z1 + z3; o1 += z2 + z4; o2 += z2 + z3; o3 += z1 + z4;
+ *       out0, out7 = t10 +- o3; out1, out6 = t11 +- o2; out2, out5 = t12 +- o1; out3, out4 = t13 +- o0, each DESCALEd.
+ *     Pass 1 runs on every COLUMN with DESCALE by 11, pass 2 on every ROW of pass 1's results with DESCALE by 18 (the order is part of
+ *     the bytes: pass 1 rounds).  sample = limit(result & 0x3FF), libjpeg's range-limit table taken literally through its index:
+ *     index < 128: index + 128; < 512: 255; < 896: 0; otherwise index - 896 -- a clamp of result + 128 to 0 ... 255 for every stream
+ *     an encoder produces, and defined for every input.  The arithmetic is 64-bit (libjpeg's JLONG); 32-bit registers give the same
+ *     values while no intermediate leaves int32_t, which the library proves per frame from the largest block sum of |d| and
+ *     otherwise does not assume.  Sample (y, x) of a component plane comes from block (y / 8, x / 8).
+ * (ii) upsampling of the chroma planes on their REAL size cw = ceil(cols / 2) (and ch = ceil(rows / 2) at 2x2), never the padded one.
+ *     2x1 (h2v1 fancy), chroma row = image row: out[2 i] = (3 C[i] + C[i - 1] + 1) >> 2, out[2 i + 1] = (3 C[i] + C[i + 1] + 2) >> 2,
+ *     except out[0] = C[0] and out[2 cw - 1] = C[cw - 1].
+ *     2x2 (h2v2 fancy): image row y reads chroma rows near = y / 2 and far = near - 1 (y even) or near + 1 (y odd), far clamped to
+ *     0 ... ch - 1; S[i] = 3 C[near][i] + C[far][i]; out[2 i] = (3 S[i] + S[i - 1] + 8) >> 4, out[2 i + 1] = (3 S[i] + S[i + 1] + 7) >> 4,
+ *     except out[0] = (4 S[0] + 8) >> 4 and out[2 cw - 1] = (4 S[cw - 1] + 7) >> 4.  1x1: the sample itself.
+ * (iii) YCbCr -> BGR with FIX(x) = (int)(x 65536 + 0.5): R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16),
+ *     G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16), each clamped to 0 ... 255 and stored B, G, R.  One component:
+ *     B = G = R = Y (what toCvCopy(..., BGR8) makes of a gray image).
+ *
+ * srl_jpeg_decode parses and entropy-decodes into page-locked staging, makes ONE upload (the tables and the coefficients) and runs the
+ * kernels; the BGR frame, rows x cols x 3 packed, stays on the device.  Synchronous.  The decoder object belongs to the context: it comes
+ * with the first call, grows by doubling and goes with srl_ctx_destroy.  srl_jpeg_download returns the frame of the last successful
+ * decode (SRL_ERR_NO_SWEEP before it; SRL_ERR_BAD_ARG: NULL, a stride below 3 cols).
+ * srl_image_prepare_jpeg is srl_jpeg_decode followed by the preparer's chain on the decoded frame where it lies, no host round trip:
+ * srl_image_prepare's path when the frame has the preparer's size, srl_image_prepare_resized's otherwise.  Every stage and both results
+ * are bytewise what those calls give for the raw frame srl_jpeg_download returns.
+ * Refusals of all three, beside the stream's own above: NULL ctx or bytes, n < 2: SRL_ERR_BAD_ARG; rows or cols above
+ * SRL_FLOW_MAX_EXTENT or rows * cols > SRL_COLOR_IMAGE_MAX_PIXELS: SRL_ERR_UNSUPPORTED; more than one rank: SRL_ERR_UNSUPPORTED;
+ * srl_image_prepare_jpeg without a preparer: SRL_ERR_NO_MAP, before the stream is read.  A refused call zeroes *info
+ * and leaves the previous decoded frame and the previous prepared images in place.  Every call cancels an armed launch. */
+typedef struct srl_jpeg_info {
+    int32_t rows, cols, components;             /* components: 1 or 3 */
+    int32_t h[3], v[3];                         /* sampling factors; absent components 0 */
+    int32_t mcus_per_row, mcus_per_col;
+    int32_t restart_interval;                   /* MCUs between restart markers, 0: none */
+    int32_t reserved[2];
+    int64_t blocks[3], total_blocks;            /* 64-coefficient blocks per component (padded to whole MCUs) and their sum */
+    int64_t scan_offset;
+} srl_jpeg_info;
+int srl_jpeg_parse(const uint8_t *bytes, int64_t n, srl_jpeg_info *info);   /* host only */
+int srl_jpeg_entropy_decode(const uint8_t *bytes, int64_t n, const srl_jpeg_info *info, int16_t *coef /* capacity_blocks x 64 */, int64_t capacity_blocks,
+                            uint16_t qt[3][64]);   /* host only */
+int srl_jpeg_decode(srl_ctx *ctx, const uint8_t *bytes, int64_t n, srl_jpeg_info *info /* or NULL */);
+int srl_jpeg_download(srl_ctx *ctx, uint8_t *out /* rows x cols x 3, B G R */, int64_t row_stride_bytes);
+int srl_image_prepare_jpeg(srl_ctx *ctx, const uint8_t *bytes, int64_t n, srl_image_prep_info *info /* or NULL */);
+
 /* ------------------------------------------------------------------ colour voxel map: the coloured cloud
  * replaces: the loops of lioOptimization::pubColorPoints (lioOptimization.cpp:1210-1241), threadPubColorPoints (:1243-1344) and
  * saveColorPoints (:1386-1426) over rgb_points_vec: a point is left out iff N_rgb < pub_point_minimum_views (:1221, :1281, :1404), every

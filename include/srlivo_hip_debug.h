@@ -160,8 +160,14 @@ int srl_flow_download_level(srl_ctx *ctx, int which, int level, uint8_t *image_p
 enum { SRL_PREP_STAGE_UNDIST = 0, SRL_PREP_STAGE_GRAY = 1, SRL_PREP_STAGE_YCRCB = 2, SRL_PREP_STAGE_LUT_GRAY = 3, SRL_PREP_STAGE_LUT_Y = 4 };
 int srl_image_prep_download_stage(srl_ctx *ctx, int stage, uint8_t *out, int64_t capacity);
 /* parity tests of the resize (srl_image_prepare_resized): the frame the last image's remap read, rows x cols x 3 bytes of the preparer's
- * size -- the resized frame, or the uploaded one where no resize ran.  capacity, refusals: as above. */
+ * size -- the resized frame, or the uploaded one where no resize ran (behind srl_image_prepare_jpeg with a frame of the preparer's size:
+ * the decoded frame where it lies; SRL_ERR_NO_SWEEP once a later srl_jpeg_decode has replaced it).  capacity, refusals: as above. */
 int srl_image_prep_download_resized(srl_ctx *ctx, uint8_t *out, int64_t capacity);
+/* known-answer tests of the JPEG decode's IDCT (srl_jpeg_decode, operation (i)) on blocks no encoder produces: n_blocks blocks of 64
+ * quantised coefficients in natural order, one table in natural order, out: 64 samples per block, row-major.  The 32-bit form runs iff
+ * the largest block sum of |coef qt| is at most 14000, the 64-bit form otherwise, as for a frame.  Synchronous; cancels an armed launch.
+ * SRL_ERR_BAD_ARG: NULL arguments, n_blocks < 1 or > 2^20; more than one rank: SRL_ERR_UNSUPPORTED. */
+int srl_jpeg_idct_blocks(srl_ctx *ctx, const int16_t *coef, int64_t n_blocks, const uint16_t qt[64], uint8_t *out);
 /* tests of the consensus estimators (srl_consensus_fundamental, srl_consensus_pnp) on EVERY hypothesis: what this context's last call that
  * ran on the device (n >= 8 / n >= 4, not refused) left in the workspace.  Synchronous; cancels an armed launch.
  * info: model = SRL_CONSENSUS_FUNDAMENTAL / _PNP, hypotheses = H, n, slots = 3 / 4, usable = the number of usable points, norm = Hartley's

@@ -464,6 +464,23 @@ int srl_lio_run_measurement_image(srl_lio *lio, double time_frame, const double 
                                   const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
                                   const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_replay_result *out,
                                   srl_image_process_result *image_out /* or NULL */);
+/* Compressed camera frames: lioOptimization::compressedImageHandler (lioOptimization.cpp:640-664: toCvCopy(msg, BGR8) of a
+ * sensor_msgs/CompressedImage) followed by process.  srl_lio_image_process_jpeg is srl_lio_image_process on a baseline JPEG stream: rows
+ * and cols -- for image_scale_factor and for every projection test -- come from srl_jpeg_parse (host only: no device is asked for them),
+ * and the prepare step becomes the JPEG step, whose default is srl_image_prepare_jpeg: the stream is entropy-decoded on the host, the
+ * frame is built on the device and prepared where it lies; the resize runs whenever the frame's size differs from the preparer's, so
+ * image_resize_ratio only sets the preparer's size here.  Every other statement is srl_lio_image_process's, one body for both.
+ * srl_lio_image_set_jpeg_step replaces the step (NULL: the default again); it is not a member of srl_image_process_steps, whose layout
+ * stays as it is, and survives srl_lio_image_set_steps.  A host-only handle with the step at its default: SRL_ERR_NO_DEVICE, as for the
+ * table's members.  SRL_ERR_BAD_ARG: NULL lio or bytes, n < 2, options never set; a stream srl_jpeg_parse refuses returns its status
+ * (SRL_ERR_BAD_ARG or SRL_ERR_UNSUPPORTED) before any step runs, *out zeroed.
+ * srl_lio_run_measurement_image_jpeg is srl_lio_run_measurement_image with the frame given as such a stream (bytes == NULL: no image). */
+typedef int (*srl_image_jpeg_step)(const uint8_t *bytes, int64_t n, void *user);
+int srl_lio_image_set_jpeg_step(srl_lio *lio, srl_image_jpeg_step fn, void *user);
+int srl_lio_image_process_jpeg(srl_lio *lio, const uint8_t *bytes, int64_t n, double time_sweep_end, int frame_id, srl_image_process_result *out /* or NULL */);
+int srl_lio_run_measurement_image_jpeg(srl_lio *lio, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                       const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
+                                       const uint8_t *bytes, int64_t n, srl_replay_result *out, srl_image_process_result *image_out /* or NULL */);
 
 /* lioOptimization::searchNeighbors / computeNeighborhoodDistribution single-call forms */
 int srl_lio_search_neighbors(srl_lio *lio, const double point[3], int nb_voxels_visited, double size_voxel_map,

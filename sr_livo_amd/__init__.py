@@ -20,4 +20,5 @@ from .capi import (  # noqa: F401
     TIME_UNIT_SEC, TIME_UNIT_MS, TIME_UNIT_US, TIME_UNIT_NS,
     Pc2Layout, Pc2Opts, Pc2Report, PC2_POINT_DTYPES, PC2_DRIVER_LAYOUTS, LIDAR_LIVOX, LIDAR_VELO, LIDAR_OUST, LIDAR_ROBO,
     pc2_opts, pc2_message, pc2_yaw_angles,
+    JpegInfo, jpeg_parse, jpeg_entropy_decode,
 )

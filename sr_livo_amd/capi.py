@@ -183,6 +183,13 @@ class ImagePrepInfo(C.Structure):
         return tuple(getattr(self, f) for f, _ in self._fields_)
 
 
+class JpegInfo(C.Structure):
+    """srl_jpeg_info: what srl_jpeg_parse reads from a baseline JPEG stream's header"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("components", C.c_int32), ("h", C.c_int32 * 3), ("v", C.c_int32 * 3),
+                ("mcus_per_row", C.c_int32), ("mcus_per_col", C.c_int32), ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("blocks", C.c_int64 * 3), ("total_blocks", C.c_int64), ("scan_offset", C.c_int64)]
+
+
 SRL_PREP_GRAY_EQ, SRL_PREP_BGR_EQ = 0, 1
 SRL_PREP_STAGE_UNDIST, SRL_PREP_STAGE_GRAY, SRL_PREP_STAGE_YCRCB, SRL_PREP_STAGE_LUT_GRAY, SRL_PREP_STAGE_LUT_Y = 0, 1, 2, 3, 4
 
@@ -359,6 +366,7 @@ IMAGE_CONSENSUS_SETUP_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_
 IMAGE_SELECT_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorCamera), C.c_int, C.c_int, C.POINTER(ColorSelectOpts), C.c_int, C.c_void_p, C.c_int,
                                    C.POINTER(C.c_int), C.c_void_p)
 IMAGE_RENDER_STEP_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ColorCamera), C.c_double, C.POINTER(ColorRenderTotals), C.c_void_p)
+IMAGE_JPEG_STEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p)      # srl_image_jpeg_step: bytes, n, user
 
 
 class ImageProcessSteps(C.Structure):
@@ -433,6 +441,12 @@ def load_library():
         "srl_image_prep_download_resized": ([p, p, C.c_int64], C.c_int),
         "srl_image_prep_download": ([p, C.c_int, p, C.c_int64], C.c_int),
         "srl_image_prep_download_stage": ([p, C.c_int, p, C.c_int64], C.c_int),
+        "srl_jpeg_parse": ([p, C.c_int64, C.POINTER(JpegInfo)], C.c_int),
+        "srl_jpeg_entropy_decode": ([p, C.c_int64, C.POINTER(JpegInfo), p, C.c_int64, p], C.c_int),
+        "srl_jpeg_decode": ([p, p, C.c_int64, C.POINTER(JpegInfo)], C.c_int),
+        "srl_jpeg_download": ([p, p, C.c_int64], C.c_int),
+        "srl_image_prepare_jpeg": ([p, p, C.c_int64, C.POINTER(ImagePrepInfo)], C.c_int),
+        "srl_jpeg_idct_blocks": ([p, p, C.c_int64, p, p], C.c_int),
         "srl_flow_track_prepared": ([p, p, C.c_int, p, p, C.POINTER(C.c_int)], C.c_int),
         "srl_oft_use_prepared_image": ([p, C.c_int], C.c_int),
         "srl_consensus_opts_default": ([C.POINTER(ConsensusOpts), C.c_int], None),
@@ -617,6 +631,10 @@ def load_library():
         "srl_lio_image_set_options": ([p, C.POINTER(ImageProcessOpts)], C.c_int),
         "srl_lio_image_set_steps": ([p, C.POINTER(ImageProcessSteps)], C.c_int),
         "srl_lio_image_process": ([p, p, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, C.POINTER(ImageProcessResult)], C.c_int),
+        "srl_lio_image_set_jpeg_step": ([p, IMAGE_JPEG_STEP_FN, p], C.c_int),
+        "srl_lio_image_process_jpeg": ([p, p, C.c_int64, C.c_double, C.c_int, C.POINTER(ImageProcessResult)], C.c_int),
+        "srl_lio_run_measurement_image_jpeg": ([p, C.c_double, p, p, p, C.c_int, p, p, C.c_int, C.c_double, C.c_double, p, C.c_int64,
+                                                C.POINTER(ReplayResult), C.POINTER(ImageProcessResult)], C.c_int),
         "srl_lio_image_oft": ([p], C.c_void_p),
         "srl_lio_image_candidates": ([p, p, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "srl_lio_image_time_last_process": ([p, C.POINTER(C.c_double)], C.c_int),
@@ -797,6 +815,32 @@ def default_flow_opts(**kw):
     for k, v in kw.items():
         setattr(o, k, v)
     return o
+
+
+def _jpeg_bytes(jpeg):
+    return np.frombuffer(jpeg, dtype=np.uint8) if isinstance(jpeg, (bytes, bytearray, memoryview)) else np.ascontiguousarray(jpeg, dtype=np.uint8).reshape(-1)
+
+
+def jpeg_parse(jpeg):
+    """srl_jpeg_parse (host only): the JpegInfo of a baseline JPEG stream; raises SrlError where it refuses"""
+    d = _jpeg_bytes(jpeg)
+    info = JpegInfo()
+    rc = load_library().srl_jpeg_parse(_ptr(d), d.size, C.byref(info))
+    if rc:
+        raise SrlError(rc, "srl_jpeg_parse", "")
+    return info
+
+
+def jpeg_entropy_decode(jpeg, info=None):
+    """srl_jpeg_entropy_decode (host only): (coef (total_blocks, 64) int16 natural order, qt (components, 64) uint16 natural order)"""
+    d = _jpeg_bytes(jpeg)
+    info = info if info is not None else jpeg_parse(d)
+    coef = np.zeros((info.total_blocks, 64), dtype=np.int16)
+    qt = np.zeros((3, 64), dtype=np.uint16)
+    rc = load_library().srl_jpeg_entropy_decode(_ptr(d), d.size, C.byref(info), _ptr(coef), len(coef), _ptr(qt))
+    if rc:
+        raise SrlError(rc, "srl_jpeg_entropy_decode", "")
+    return coef, qt[:info.components]
 
 
 def default_image_prep_opts(**kw):
@@ -987,6 +1031,27 @@ class Context:
         if rc and rc not in ok:
             raise SrlError(rc, what, (self.lib.srl_last_error(self.h) or b"").decode())
         return rc
+
+    def jpeg_decode(self, jpeg):
+        """srl_jpeg_decode: a baseline JPEG stream (bytes or uint8 array) to a BGR frame that stays on the device.  Returns JpegInfo."""
+        d = _jpeg_bytes(jpeg)
+        info = JpegInfo()
+        self._chk(self.lib.srl_jpeg_decode(self.h, _ptr(d), d.size, C.byref(info)), "srl_jpeg_decode")
+        return info
+
+    def jpeg_download(self, rows, cols):
+        """srl_jpeg_download: the last decoded frame, (rows, cols, 3) uint8 B G R (rows, cols: JpegInfo's)"""
+        out = np.zeros((rows, cols, 3), dtype=np.uint8)
+        self._chk(self.lib.srl_jpeg_download(self.h, _ptr(out), out.strides[0]), "srl_jpeg_download")
+        return out
+
+    def jpeg_idct_blocks(self, coef, qt):
+        """srl_jpeg_idct_blocks (debug): coef (n, 64) int16 and qt (64,) uint16, both natural order -> (n, 64) uint8"""
+        c = np.ascontiguousarray(coef, dtype=np.int16).reshape(-1, 64)
+        q = np.ascontiguousarray(qt, dtype=np.uint16).reshape(64)
+        out = np.zeros((len(c), 64), dtype=np.uint8)
+        self._chk(self.lib.srl_jpeg_idct_blocks(self.h, _ptr(c), len(c), _ptr(q), _ptr(out)), "srl_jpeg_idct_blocks")
+        return out
 
     def map_upload(self, keys, counts, xyz, cap=20):
         keys = np.ascontiguousarray(keys, dtype=np.int16).reshape(-1, 3)
@@ -1819,6 +1884,14 @@ class ImagePrep:
                       "srl_image_prepare_resized")
         return info
 
+    def prepare_jpeg(self, jpeg):
+        """srl_image_prepare_jpeg: a baseline JPEG stream (bytes or uint8 array) decoded on the device and prepared where it lies, resized
+        when its size is not the preparer's.  Returns ImagePrepInfo."""
+        d = _jpeg_bytes(jpeg)
+        info = ImagePrepInfo()
+        self.ctx._chk(self.lib.srl_image_prepare_jpeg(self.ctx.h, _ptr(d), d.size, C.byref(info)), "srl_image_prepare_jpeg")
+        return info
+
     def download_resized(self):
         """srl_image_prep_download_resized: the frame the last image's remap read, (rows, cols, 3) uint8"""
         out = np.zeros((self.opts.rows, self.opts.cols, 3), dtype=np.uint8)
@@ -2236,6 +2309,22 @@ class Lio:
                                                       C.byref(res)), "srl_lio_image_process", ok)
         return (rc, res) if ok else res
 
+    def image_set_jpeg_step(self, fn=None):
+        """srl_lio_image_set_jpeg_step: fn(bytes_address, n, user) -> status as an IMAGE_JPEG_STEP_FN or a Python callable (kept alive here);
+        None puts srl_image_prepare_jpeg back"""
+        if fn is not None and not isinstance(fn, IMAGE_JPEG_STEP_FN):
+            fn = IMAGE_JPEG_STEP_FN(fn)
+        self._jpeg_step = fn
+        self._chk(self.lib.srl_lio_image_set_jpeg_step(self.h, fn if fn is not None else IMAGE_JPEG_STEP_FN(), None), "srl_lio_image_set_jpeg_step")
+
+    def image_process_jpeg(self, jpeg, time_sweep_end, frame_id, ok=()):
+        """srl_lio_image_process_jpeg: image_process on a baseline JPEG stream (bytes or uint8 array).  Returns as image_process does."""
+        d = _jpeg_bytes(jpeg)
+        res = ImageProcessResult()
+        rc = self._chk(self.lib.srl_lio_image_process_jpeg(self.h, _ptr(d), d.size, float(time_sweep_end), int(frame_id), C.byref(res)),
+                       "srl_lio_image_process_jpeg", ok)
+        return (rc, res) if ok else res
+
     def image_oft(self):
         """srl_lio_image_oft: the handle's tracker as an Oft that does not own it (read-backs: sizes, times, pose_map, tracked_for_vio)"""
         o = Oft.__new__(Oft)
@@ -2490,6 +2579,21 @@ class Lio:
         rc = self._chk(self.lib.srl_lio_run_measurement_image(self.h, float(time_frame), _ptr(it), _ptr(ia), _ptr(ig), len(it), _ptr(pr), _ptr(pt),
                                                               len(pr), float(time_sweep_begin), float(time_sweep_offset), _ptr(b), rows, cols, stride,
                                                               C.byref(out), C.byref(img)), "run_measurement_image", ok=allow)
+        return dict(rc=rc, processed=bool(out.processed), initialized=bool(out.initialized), index_frame=out.index_frame,
+                    success=bool(out.success), num_residuals=out.num_residuals_used, iters=out.iterations, frame_points=out.frame_points,
+                    keypoints=out.keypoints, points_added=out.points_added, state=np.array(out.state), image=img)
+
+    def run_measurement_image_jpeg(self, time_frame, imu_t, imu_acc, imu_gyr, pts_raw, pts_timestamp, time_sweep_begin, time_sweep_offset, jpeg,
+                                   allow=(SRL_ERR_NOT_ENOUGH_RESIDUALS,)):
+        """srl_lio_run_measurement_image_jpeg: run_measurement_image with the frame as a baseline JPEG stream (bytes or uint8 array), or None"""
+        it = _f64(imu_t); ia = _f64(imu_acc, (-1, 3)); ig = _f64(imu_gyr, (-1, 3))
+        pr = _f64(pts_raw, (-1, 3)); pt = _f64(pts_timestamp)
+        d = None if jpeg is None else _jpeg_bytes(jpeg)
+        out, img = ReplayResult(), ImageProcessResult()
+        rc = self._chk(self.lib.srl_lio_run_measurement_image_jpeg(self.h, float(time_frame), _ptr(it), _ptr(ia), _ptr(ig), len(it), _ptr(pr), _ptr(pt),
+                                                                   len(pr), float(time_sweep_begin), float(time_sweep_offset), _ptr(d),
+                                                                   0 if d is None else d.size, C.byref(out), C.byref(img)),
+                       "run_measurement_image_jpeg", ok=allow)
         return dict(rc=rc, processed=bool(out.processed), initialized=bool(out.initialized), index_frame=out.index_frame,
                     success=bool(out.success), num_residuals=out.num_residuals_used, iters=out.iterations, frame_points=out.frame_points,
                     keypoints=out.keypoints, points_added=out.points_added, state=np.array(out.state), image=img)

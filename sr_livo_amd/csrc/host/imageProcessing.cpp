@@ -185,7 +185,8 @@ int imageProcessing::process(cameraState &st, const imageFrame &frame, int numbe
     srl_image_process_result r = {};
     auto leave = [&](int rc) { status = rc; if (result) *result = r; return rc; };
     if (!op_tracker || !steps.prepCreate || !steps.prepare || !steps.consensusSetup || !steps.select || !steps.render) return leave(SRL_ERR_NO_DEVICE);
-    if (!frame.rgb_image || frame.image_rows < 1 || frame.image_cols < 1) return leave(SRL_ERR_BAD_ARG);
+    if (frame.jpeg && !steps.prepareJpeg) return leave(SRL_ERR_NO_DEVICE);
+    if ((!frame.rgb_image && !frame.jpeg) || frame.image_rows < 1 || frame.image_cols < 1) return leave(SRL_ERR_BAD_ARG);
     r.first_data = first_data ? 1 : 0;
 
     // :91-111.  The reference has no failing step; here one may fail, and the frame is then offered again.  So nothing of the first
@@ -220,7 +221,9 @@ int imageProcessing::process(cameraState &st, const imageFrame &frame, int numbe
 
     {                                                    // :113-125: the resize iff the ratio says so, then remap, gray + CLAHE, YCrCb
         const bool resized = std::fabs(image_resize_ratio - 1.0) > 1e-6;
-        const int rc = steps.prepare(frame.rgb_image, frame.image_rows, frame.image_cols, frame.row_stride_bytes, resized);
+        // (a compressed frame is decoded on the way, and resized whenever its size is not the preparer's)
+        const int rc = frame.jpeg ? steps.prepareJpeg(frame.jpeg, frame.jpeg_bytes)
+                                  : steps.prepare(frame.rgb_image, frame.image_rows, frame.image_cols, frame.row_stride_bytes, resized);
         if (rc != SRL_OK) return leave(rc);
     }
 

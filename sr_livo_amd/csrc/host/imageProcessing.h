@@ -24,6 +24,8 @@ namespace srlivo {
 // what process reads of its cloudFrame (lioOptimization.cpp:1079-1081): the raw image, its size, the sweep's end and the frame's number
 struct imageFrame {
     const uint8_t *rgb_image = nullptr;
+    const uint8_t *jpeg = nullptr;                         // compressedImageHandler's frame: a baseline JPEG stream instead of rgb_image;
+    int64_t jpeg_bytes = 0;                                // image_rows / image_cols are then what srl_jpeg_parse read from it
     int image_rows = 0, image_cols = 0;
     int64_t row_stride_bytes = 0;
     double time_sweep_end = 0.0;
@@ -36,6 +38,7 @@ struct imageFrame {
 struct processSteps {
     std::function<int(const srl_image_prep_opts &)> prepCreate;                                      // initUndistortRectifyMap (:103): srl_image_prep_create
     std::function<int(const uint8_t *raw, int rows, int cols, int64_t stride, bool resized)> prepare;      // :113-125: srl_image_prepare(_resized)
+    std::function<int(const uint8_t *bytes, int64_t n)> prepareJpeg;                                  // the same for a frame that came compressed: srl_image_prepare_jpeg
     std::function<int(const double *fx_fy_cx_cy)> consensusSetup;                                     // setIntrinsic (:106): useDeviceConsensus
     // selectPointsForProjection (:131) and, with refresh set, the one inside refreshPointsForProjection (:159)
     std::function<int(const srl_color_camera &, int rows, int cols, const srl_color_select_opts &, bool refresh, std::vector<srl_color_selected> &)> select;

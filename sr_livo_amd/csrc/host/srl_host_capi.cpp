@@ -25,6 +25,8 @@ struct srl_lio {
     // imageProcessing::process: the tracker it works on (made at the first frame) and the step table as given
     srl_oft *oft = nullptr;
     srl_image_process_steps image_steps = {};
+    srl_image_jpeg_step jpeg_step = nullptr;  // the prepare step of a compressed frame (not a member of the table: its layout stays)
+    void *jpeg_user = nullptr;
     bool image_options_set = false;
 };
 
@@ -958,14 +960,15 @@ int srl_lio_vio_photometric(srl_lio *h, const srl_color_vio_point *tracked, int 
 
 // ------------------------------------------------------------------ one camera frame end to end (imageProcessing::process)
 namespace {
-// the handle's step table as imageProcessing::process and the tracker take it: a member the caller gave, or the device call
-int image_install_steps(srl_lio *h) {
+// the handle's step table as imageProcessing::process and the tracker take it: a member the caller gave, or the device call.
+// jpeg: the frame comes compressed, so its own prepare step is needed too
+int image_install_steps(srl_lio *h, bool jpeg) {
     srl_ctx *ctx = h->lio->context();
     const srl_image_process_steps S = h->image_steps;
     void *user = S.user;
     const bool all = S.prep_create && S.prepare && S.consensus_setup && S.select && S.flow && S.fundamental && S.pnp && (S.rows || h->vio_provider) &&
                      S.render && S.track_update;
-    if (!ctx && !all) { h->err = "host-only handle: no device for the steps of imageProcessing::process left at their defaults"; return SRL_ERR_NO_DEVICE; }
+    if (!ctx && !(all && (!jpeg || h->jpeg_step))) { h->err = "host-only handle: no device for the steps of imageProcessing::process left at their defaults"; return SRL_ERR_NO_DEVICE; }
     if (!h->oft) h->oft = new srl_oft(ctx);
     opticalFlowTracker &t = h->oft->t;
     lioOptimization *L = h->lio;
@@ -977,6 +980,9 @@ int image_install_steps(srl_lio *h) {
     else P.prepare = [ctx](const uint8_t *raw, int rows, int cols, int64_t stride, bool resized) {
         return resized ? srl_image_prepare_resized(ctx, raw, rows, cols, stride, nullptr) : srl_image_prepare(ctx, raw, rows, cols, stride, nullptr);
     };
+    if (h->jpeg_step) { const srl_image_jpeg_step fn = h->jpeg_step; void *ju = h->jpeg_user; P.prepareJpeg = [fn, ju](const uint8_t *b, int64_t n) { return fn(b, n, ju); }; }
+    else if (ctx) P.prepareJpeg = [ctx](const uint8_t *b, int64_t n) { return srl_image_prepare_jpeg(ctx, b, n, nullptr); };
+    else P.prepareJpeg = nullptr;
     // The tracker's two consensus providers: the device's estimators on the intrinsics k (useDeviceConsensus installs both), then the
     // caller's on top where the table has them.  ONE function, run behind the consensus setup of the first data and again by every later
     // install, so that a replaced step holds from the first frame on and a member that went back to NULL gets the device call back.
@@ -1071,14 +1077,13 @@ int srl_lio_image_set_steps(srl_lio *h, const srl_image_process_steps *steps) {
     if (steps) h->image_steps = *steps; else h->image_steps = srl_image_process_steps();
     return SRL_OK;
 }
-int srl_lio_image_process(srl_lio *h, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end, int frame_id,
-                          srl_image_process_result *out) {
-    if (out) std::memset(out, 0, sizeof *out);
-    if (!h || !raw_bgr || rows < 1 || cols < 1 || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+}  // extern "C"
+
+namespace {
+// srl_lio_image_process and srl_lio_image_process_jpeg behind their argument checks: f holds the image, raw or compressed, and its size
+int image_process_frame(srl_lio *h, imageFrame f, double time_sweep_end, int frame_id, srl_image_process_result *out) {
     if (!h->image_options_set) { h->err = "srl_lio_image_process: no options (srl_lio_image_set_options)"; return SRL_ERR_BAD_ARG; }
-    { const int rc = image_install_steps(h); if (rc != SRL_OK) return rc; }
-    imageFrame f;
-    f.rgb_image = raw_bgr; f.image_rows = rows; f.image_cols = cols; f.row_stride_bytes = row_stride_bytes;
+    { const int rc = image_install_steps(h, f.jpeg != nullptr); if (rc != SRL_OK) return rc; }
     f.time_sweep_end = time_sweep_end; f.frame_id = frame_id;
     int rc;
     try { rc = h->vio.process(h->camera, f, h->lio->number_of_new_visited_voxel, out); }
@@ -1086,6 +1091,38 @@ int srl_lio_image_process(srl_lio *h, const uint8_t *raw_bgr, int rows, int cols
     if (rc == SRL_OK) h->lio->time_last_process = h->vio.time_last_process;      // what the next colour insertion reads; a frame that did not finish moves nothing
     if (rc != SRL_OK && h->lio->context()) { const char *m = srl_last_error(h->lio->context()); if (m && *m) h->err = m; }
     return rc;
+}
+// a compressed frame: its size from the stream's header alone (no device)
+int jpeg_frame(srl_lio *h, const uint8_t *bytes, int64_t n, imageFrame *f) {
+    srl_jpeg_info ji;
+    const int rc = srl_jpeg_parse(bytes, n, &ji);
+    if (rc != SRL_OK) { h->err = rc == SRL_ERR_UNSUPPORTED ? "JPEG: outside what srl_jpeg_parse accepts" : "JPEG: malformed header"; return rc; }
+    f->jpeg = bytes; f->jpeg_bytes = n; f->image_rows = ji.rows; f->image_cols = ji.cols;
+    return SRL_OK;
+}
+}  // namespace
+
+extern "C" {
+int srl_lio_image_process(srl_lio *h, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, double time_sweep_end, int frame_id,
+                          srl_image_process_result *out) {
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || !raw_bgr || rows < 1 || cols < 1 || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    imageFrame f;
+    f.rgb_image = raw_bgr; f.image_rows = rows; f.image_cols = cols; f.row_stride_bytes = row_stride_bytes;
+    return image_process_frame(h, f, time_sweep_end, frame_id, out);
+}
+int srl_lio_image_set_jpeg_step(srl_lio *h, srl_image_jpeg_step fn, void *user) {
+    if (!h) return SRL_ERR_BAD_ARG;
+    h->jpeg_step = fn; h->jpeg_user = fn ? user : nullptr;
+    return SRL_OK;
+}
+int srl_lio_image_process_jpeg(srl_lio *h, const uint8_t *bytes, int64_t n, double time_sweep_end, int frame_id, srl_image_process_result *out) {
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || !bytes || n < 2) return SRL_ERR_BAD_ARG;
+    if (!h->image_options_set) { h->err = "srl_lio_image_process_jpeg: no options (srl_lio_image_set_options)"; return SRL_ERR_BAD_ARG; }
+    imageFrame f;
+    { const int rc = jpeg_frame(h, bytes, n, &f); if (rc != SRL_OK) return rc; }
+    return image_process_frame(h, f, time_sweep_end, frame_id, out);
 }
 srl_oft *srl_lio_image_oft(srl_lio *h) {
     if (!h) return nullptr;
@@ -1101,16 +1138,15 @@ int srl_lio_image_candidates(srl_lio *h, srl_color_selected *out, int capacity, 
     if (!c.empty()) std::memcpy(out, c.data(), c.size() * sizeof(srl_color_selected));
     return SRL_OK;
 }
-int srl_lio_run_measurement_image(srl_lio *h, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
-                                  const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
-                                  const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_replay_result *out,
-                                  srl_image_process_result *image_out) {
-    if (image_out) std::memset(image_out, 0, sizeof *image_out);
-    if (!raw_bgr) return srl_lio_run_measurement(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, out);
-    if (out) std::memset(out, 0, sizeof *out);
-    if (!h || rows < 1 || cols < 1 || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+}  // extern "C"
+
+namespace {
+// srl_lio_run_measurement_image and its _jpeg twin behind their argument checks: `frame` holds the image, raw or compressed, and its size
+int run_measurement_frame(srl_lio *h, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                          const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
+                          const imageFrame &frame, srl_replay_result *out, srl_image_process_result *image_out) {
     if (!h->image_options_set) { h->err = "srl_lio_run_measurement_image: no options (srl_lio_image_set_options)"; return SRL_ERR_BAD_ARG; }
-    { const int rc = image_install_steps(h); if (rc != SRL_OK) return rc; }
+    { const int rc = image_install_steps(h, frame.jpeg != nullptr); if (rc != SRL_OK) return rc; }
     lioOptimization &L = *h->lio;
     int image_rc = SRL_OK;
     std::string image_err;
@@ -1124,8 +1160,7 @@ int srl_lio_run_measurement_image(srl_lio *h, double time_frame, const double *i
         c.rotation = p_frame->p_state->rotation; c.translation = p_frame->p_state->translation;
         c.q_world_camera = srl::Quat::fromRotationMatrix(c.rotation.toRotationMatrix() * c.R_imu_camera);      // :1073-1074
         c.t_world_camera = c.rotation.toRotationMatrix() * c.t_imu_camera + c.translation;
-        imageFrame f;                                     // :1077-1083
-        f.rgb_image = raw_bgr; f.image_rows = rows; f.image_cols = cols; f.row_stride_bytes = row_stride_bytes;
+        imageFrame f = frame;                             // :1077-1083
         f.time_sweep_end = p_frame->time_sweep_end; f.frame_id = p_frame->frame_id;
         try { image_rc = h->vio.process(c, f, L.number_of_new_visited_voxel, image_out); }
         catch (const std::exception &e) { image_rc = SRL_ERR_HIP; image_err = e.what(); }
@@ -1142,6 +1177,33 @@ int srl_lio_run_measurement_image(srl_lio *h, double time_frame, const double *i
         h->err = !image_err.empty() ? image_err : (m && *m ? m : "the camera frame of srl_lio_run_measurement_image failed");
     }
     return image_rc;
+}
+}  // namespace
+
+extern "C" {
+int srl_lio_run_measurement_image(srl_lio *h, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                  const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
+                                  const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_replay_result *out,
+                                  srl_image_process_result *image_out) {
+    if (image_out) std::memset(image_out, 0, sizeof *image_out);
+    if (!raw_bgr) return srl_lio_run_measurement(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, out);
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || rows < 1 || cols < 1 || row_stride_bytes < (int64_t)cols * 3) return SRL_ERR_BAD_ARG;
+    imageFrame f;
+    f.rgb_image = raw_bgr; f.image_rows = rows; f.image_cols = cols; f.row_stride_bytes = row_stride_bytes;
+    return run_measurement_frame(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, f, out, image_out);
+}
+int srl_lio_run_measurement_image_jpeg(srl_lio *h, double time_frame, const double *imu_t, const double *imu_acc, const double *imu_gyr, int n_imu,
+                                       const double *pts_raw, const double *pts_timestamp, int n_pts, double time_sweep_begin, double time_sweep_offset,
+                                       const uint8_t *bytes, int64_t n, srl_replay_result *out, srl_image_process_result *image_out) {
+    if (image_out) std::memset(image_out, 0, sizeof *image_out);
+    if (!bytes) return srl_lio_run_measurement(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, out);
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!h || n < 2) return SRL_ERR_BAD_ARG;
+    if (!h->image_options_set) { h->err = "srl_lio_run_measurement_image_jpeg: no options (srl_lio_image_set_options)"; return SRL_ERR_BAD_ARG; }
+    imageFrame f;
+    { const int rc = jpeg_frame(h, bytes, n, &f); if (rc != SRL_OK) return rc; }
+    return run_measurement_frame(h, time_frame, imu_t, imu_acc, imu_gyr, n_imu, pts_raw, pts_timestamp, n_pts, time_sweep_begin, time_sweep_offset, f, out, image_out);
 }
 int srl_lio_image_time_last_process(srl_lio *h, double *time_last_process) {
     if (!h || !time_last_process) return SRL_ERR_BAD_ARG;

@@ -187,6 +187,7 @@ int srl_ctx_destroy(srl_ctx *ctx) {
     if (ctx->prep) srl_image_prep_destroy(ctx);
     srl_consensus_release(ctx);
     srl_points_release(ctx);
+    srl_jpeg_release(ctx);
     if (ctx->pose_box_pinned) hipHostFree(ctx->pose_box_pinned);
     if (ctx->pose_box_dev) hipFree(ctx->pose_box_dev);
     if (ctx->d_pose_relay) hipFree(ctx->d_pose_relay);

@@ -160,6 +160,7 @@ struct srl_ctx {
     struct SrlColorMap *color = nullptr;   // the colour voxel map (srl_color_kernels.hip); nullptr until srl_color_map_create
     struct SrlFlow *flow = nullptr;        // the optical-flow tracker (srl_flow.hip); nullptr until srl_flow_create
     struct SrlImagePrep *prep = nullptr;   // the image preparer (srl_image_prep.hip); nullptr until srl_image_prep_create
+    struct SrlJpeg *jpeg = nullptr;        // the JPEG decoder (srl_jpeg.hip): made by the first srl_jpeg_decode, freed by srl_jpeg_release
     struct SrlConsensus *consensus = nullptr;   // workspace of srl_consensus_* (srl_consensus.hip): made by the first call, freed by srl_consensus_release
     // undistorted sweep (srl_frame_undistort): inputs, imu_point, corrected raw_point
     double *d_corr_in = nullptr, *d_corr_rel = nullptr, *d_corr_imu = nullptr, *d_corr_raw = nullptr;
@@ -338,6 +339,8 @@ extern "C" int srl_ctx_disarm(srl_ctx *ctx);
 extern "C" void srl_consensus_release(srl_ctx *ctx);
 // frees the device point queue (srl_points.hip); srl_ctx_destroy calls it
 extern "C" void srl_points_release(srl_ctx *ctx);
+// frees the JPEG decoder (srl_jpeg.hip); srl_ctx_destroy calls it
+extern "C" void srl_jpeg_release(srl_ctx *ctx);
 
 // frame pipeline stage stamps (only while srl_debug_frame_timing is on): close stage `slot` here
 #include <chrono>

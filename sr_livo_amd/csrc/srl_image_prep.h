@@ -21,7 +21,22 @@ struct SrlImagePrep {
     int *d_ofs_x = nullptr, *d_ofs_y = nullptr;                 // srl_image_resize_build_tables per column and per row of the preparer's size
     unsigned *d_coef_x = nullptr, *d_coef_y = nullptr;          // (coef[2 d], coef[2 d + 1]) as one dword
     int tab_rows = 0, tab_cols = 0;                             // the source size the tables on the device are for (0: none yet)
+    const unsigned char *d_frame = nullptr;                     // the frame the last chain's remap read: raw.d, or a decoded JPEG frame where it lies
 };
+
+// four consecutive pixels of the image taken as one flat array per lane (k_prep_pixel, k_prep_apply, k_resize_bgr, k_jpeg_color)
+struct PrepDims { int rows, cols, npix; };
+// pixel 4 g + k of the flat image; beyond the image: the last pixel again
+__device__ __forceinline__ void prep_first(const PrepDims &D, int g, int *x, int *y) {
+    long long i = (long long)g * 4;
+    if (i >= D.npix) i = D.npix - 1;
+    *y = (int)(i / D.cols);
+    *x = (int)(i - (long long)*y * D.cols);
+}
+__device__ __forceinline__ void prep_step(const PrepDims &D, int *x, int *y) {
+    if (++*x == D.cols) { *x = 0; ++*y; }
+    if (*y >= D.rows) { *y = D.rows - 1; *x = D.cols - 1; }
+}
 
 // the refusals of the preparer's entry points and of srl_flow_track_prepared: no preparer, no image yet; more than one rank
 inline int srl_prep_need(srl_ctx *ctx, bool image) {
@@ -33,6 +48,11 @@ inline int srl_prep_one_rank(srl_ctx *ctx) {
     if (ctx->nranks > 1) { ctx->err = "the image preparer is neither replicated nor sharded: one rank only"; return SRL_ERR_UNSUPPORTED; }
     return SRL_OK;
 }
+
+// srl_image_prep.hip: the body of srl_image_prepare / srl_image_prepare_resized behind their upload, on a packed BGR frame of src_rows x
+// src_cols that lies on the device (the uploaded one, or srl_jpeg.hip's decoded one): the resize into raw.d unless the frame has the
+// preparer's size, then the chain, the hand-over to the colour map and the wait.  The arguments have been checked by the caller.
+int srl_prep_run_device(srl_ctx *ctx, const unsigned char *d_bgr, int src_rows, int src_cols, srl_image_prep_info *info);
 
 // srl_color_render.hip: d_bgr (rows x cols x 3, packed, device) becomes the colour map's image as srl_color_image_upload would leave it
 int srl_color_image_install(srl_ctx *ctx, const unsigned char *d_bgr, int rows, int cols);

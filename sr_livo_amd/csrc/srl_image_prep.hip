@@ -64,8 +64,6 @@ bool prep_plan(const srl_image_prep_opts *o, PrepPlan *p) {
     return true;
 }
 
-struct PrepDims { int rows, cols, npix; };
-
 #define PREP_DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 __device__ __forceinline__ int prep_sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 // sat8(DESCALE(x, 14)) with the clamp made BEFORE the shift (the same value: the shift is monotonic).  Written as sat8(x >> 14) twice and
@@ -75,18 +73,6 @@ __device__ __forceinline__ int prep_sat8_descale14(int x) {
     x += 1 << 13;
     x = x < 0 ? 0 : (x > (256 << 14) - 1 ? (256 << 14) - 1 : x);
     return x >> 14;
-}
-
-// pixel 4 g + k of the flat image; beyond the image: the last pixel again
-__device__ __forceinline__ void prep_first(const PrepDims &D, int g, int *x, int *y) {
-    long long i = (long long)g * 4;
-    if (i >= D.npix) i = D.npix - 1;
-    *y = (int)(i / D.cols);
-    *x = (int)(i - (long long)*y * D.cols);
-}
-__device__ __forceinline__ void prep_step(const PrepDims &D, int *x, int *y) {
-    if (++*x == D.cols) { *x = 0; ++*y; }
-    if (*y >= D.rows) { *y = D.rows - 1; *x = D.cols - 1; }
 }
 
 struct PrepResizeArgs { PrepDims D; int src_rows, src_cols; };               // D: the destination, the preparer's size
@@ -391,15 +377,16 @@ extern "C" int srl_image_prep_destroy(srl_ctx *ctx) {
 
 namespace {
 
-// the three kernels over the frame in p->raw.d (uploaded, or resized into it), the hand-over to the colour map and the wait
-int prep_chain(srl_ctx *ctx, SrlImagePrep *p, srl_image_prep_info *info) {
+// the three kernels over `frame` (rows x cols x 3 of the preparer's size on the device: uploaded, resized into raw.d, or decoded), the
+// hand-over to the colour map and the wait
+int prep_chain(srl_ctx *ctx, SrlImagePrep *p, const unsigned char *frame, srl_image_prep_info *info) {
     hipStream_t st = ctx->stream;
     const int rows = p->rows, cols = p->cols;
     const size_t npix = (size_t)rows * (size_t)cols;
     const int ngroups = (int)((npix + 3) / 4);
     const unsigned nb = (unsigned)((ngroups + 255) / 256);
     const PrepDims D = {rows, cols, (int)npix};
-    hipLaunchKernelGGL(k_prep_pixel, dim3(nb), dim3(256), 0, st, p->raw.d, reinterpret_cast<const uint4 *>(p->d_map1), reinterpret_cast<const uint2 *>(p->d_map2),
+    hipLaunchKernelGGL(k_prep_pixel, dim3(nb), dim3(256), 0, st, frame, reinterpret_cast<const uint4 *>(p->d_map1), reinterpret_cast<const uint2 *>(p->d_map2),
                        reinterpret_cast<unsigned *>(p->d_undist), reinterpret_cast<unsigned *>(p->d_gray), reinterpret_cast<unsigned *>(p->d_y),
                        reinterpret_cast<uint2 *>(p->d_crcb), D, ngroups);
     PrepTileArgs TA;
@@ -421,6 +408,7 @@ int prep_chain(srl_ctx *ctx, SrlImagePrep *p, srl_image_prep_info *info) {
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     p->have_image = true;
+    p->d_frame = frame;
     prep_info(p, installed, info);
     return SRL_OK;
 }
@@ -446,6 +434,25 @@ int prep_resize_tables(srl_ctx *ctx, SrlImagePrep *p, int src_rows, int src_cols
 
 }  // namespace
 
+int srl_prep_run_device(srl_ctx *ctx, const unsigned char *d_bgr, int src_rows, int src_cols, srl_image_prep_info *info) {
+    SrlImagePrep *p = ctx->prep;
+    if (src_rows == p->rows && src_cols == p->cols) return prep_chain(ctx, p, d_bgr, info);      // the preparer's own size: no resize kernel
+    const bool half = src_cols == 2 * p->cols && src_rows == 2 * p->rows;
+    if (!half) { const int rc = prep_resize_tables(ctx, p, src_rows, src_cols); if (rc) return rc; }
+    const size_t npix = (size_t)p->rows * (size_t)p->cols;
+    const int ngroups = (int)((npix + 3) / 4);
+    const unsigned nb = (unsigned)((ngroups + 255) / 256);
+    PrepResizeArgs RA;
+    RA.D = {p->rows, p->cols, (int)npix}; RA.src_rows = src_rows; RA.src_cols = src_cols;
+    if (half)
+        hipLaunchKernelGGL(k_resize_bgr<true>, dim3(nb), dim3(256), 0, ctx->stream, d_bgr, p->d_ofs_x, p->d_coef_x, p->d_ofs_y, p->d_coef_y,
+                           reinterpret_cast<unsigned *>(p->raw.d), RA, ngroups);
+    else
+        hipLaunchKernelGGL(k_resize_bgr<false>, dim3(nb), dim3(256), 0, ctx->stream, d_bgr, p->d_ofs_x, p->d_coef_x, p->d_ofs_y, p->d_coef_y,
+                           reinterpret_cast<unsigned *>(p->raw.d), RA, ngroups);
+    return prep_chain(ctx, p, p->raw.d, info);
+}
+
 extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows, int cols, int64_t row_stride_bytes, srl_image_prep_info *info) {
     if (info) std::memset(info, 0, sizeof *info);
     if (!ctx || !raw_bgr) return SRL_ERR_BAD_ARG;
@@ -458,7 +465,7 @@ extern "C" int srl_image_prepare(srl_ctx *ctx, const uint8_t *raw_bgr, int rows,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // every call ends synchronised, so the staging block is free
     { const int rc = p->raw.upload(ctx, raw_bgr, rows, (size_t)cols * 3, row_stride_bytes); if (rc) return rc; }
-    return prep_chain(ctx, p, info);
+    return srl_prep_run_device(ctx, p->raw.d, rows, cols, info);
 }
 
 extern "C" int srl_image_resize_build_tables(int src_len, int dst_len, int32_t *ofs, int16_t *coef) {
@@ -492,25 +499,12 @@ extern "C" int srl_image_prepare_resized(srl_ctx *ctx, const uint8_t *raw_bgr, i
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (src_rows == p->rows && src_cols == p->cols) {          // the preparer's own size: srl_image_prepare, no resize kernel
         { const int rc = p->raw.upload(ctx, raw_bgr, src_rows, (size_t)src_cols * 3, row_stride_bytes); if (rc) return rc; }
-        return prep_chain(ctx, p, info);
+        return srl_prep_run_device(ctx, p->raw.d, src_rows, src_cols, info);
     }
-    const bool half = src_cols == 2 * p->cols && src_rows == 2 * p->rows;
-    if (!half) { const int rc = prep_resize_tables(ctx, p, src_rows, src_cols); if (rc) return rc; }
     const size_t src_bytes = (size_t)src_rows * (size_t)src_cols * 3;
     { const int rc = p->src.reserve(ctx, src_bytes, src_bytes); if (rc) return rc; }
     { const int rc = p->src.upload(ctx, raw_bgr, src_rows, (size_t)src_cols * 3, row_stride_bytes); if (rc) return rc; }
-    const size_t npix = (size_t)p->rows * (size_t)p->cols;
-    const int ngroups = (int)((npix + 3) / 4);
-    const unsigned nb = (unsigned)((ngroups + 255) / 256);
-    PrepResizeArgs RA;
-    RA.D = {p->rows, p->cols, (int)npix}; RA.src_rows = src_rows; RA.src_cols = src_cols;
-    if (half)
-        hipLaunchKernelGGL(k_resize_bgr<true>, dim3(nb), dim3(256), 0, ctx->stream, p->src.d, p->d_ofs_x, p->d_coef_x, p->d_ofs_y, p->d_coef_y,
-                           reinterpret_cast<unsigned *>(p->raw.d), RA, ngroups);
-    else
-        hipLaunchKernelGGL(k_resize_bgr<false>, dim3(nb), dim3(256), 0, ctx->stream, p->src.d, p->d_ofs_x, p->d_coef_x, p->d_ofs_y, p->d_coef_y,
-                           reinterpret_cast<unsigned *>(p->raw.d), RA, ngroups);
-    return prep_chain(ctx, p, info);
+    return srl_prep_run_device(ctx, p->src.d, src_rows, src_cols, info);
 }
 
 extern "C" int srl_image_prep_download(srl_ctx *ctx, int which, uint8_t *out, int64_t row_stride_bytes) {
@@ -553,9 +547,10 @@ extern "C" int srl_image_prep_download_resized(srl_ctx *ctx, uint8_t *out, int64
     SrlImagePrep *p = ctx->prep;
     const size_t need = (size_t)p->rows * (size_t)p->cols * 3;
     if (capacity < (int64_t)need) return SRL_ERR_BAD_ARG;
+    if (!p->d_frame) { ctx->err = "image preparer: the decoded frame the last chain read has been replaced since"; return SRL_ERR_NO_SWEEP; }
     SRL_DISARM(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, p->raw.d, need, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, p->d_frame, need, hipMemcpyDeviceToHost));
     return SRL_OK;
 }

@@ -572,8 +572,9 @@ int srl_consensus_pnp(srl_ctx *ctx, const float *xyz, const float *uv, int n, co
  * (f) CLAHE(plane, clip), clip = 3.0 for gray, 1.0 for Y (:124, :195).  T x T tiles, T = max((int)(cols 32.0 / 640), 4) (:169; both
  *     counts from cols) unless opts->tiles gives T.  If cols % T != 0 or rows % T != 0 the plane is extended on the right by T - cols % T
  *     and at the bottom by T - rows % T (a dimension that divided grows by a whole T) with reflect-101 (index 2 (n - 1) - k); otherwise
- *     not at all.  Tile tw x th = extended / T, area = tw th.  Per tile: the 256-bin histogram; limit = max((int)(clip area / 256), 1) in
- *     FP64; every bin above limit is cut to it, the cuts summed into excess; batch = excess / 256, res = excess - 256 batch; every bin
+ *     not at all.  Tile tw x th = extended / T, area = tw th.  Per tile: the 256-bin histogram;
+ *     limit = max((int)min(clip area / 256, 2147483647.0), 1) in FP64 (the min first: a large clip saturates at INT32_MAX, the cast is
+ *     never out of range); every bin above limit is cut to it, the cuts summed into excess; batch = excess / 256, res = excess - 256 batch; every bin
  *     + batch; if res > 0, step = max(256 / res, 1) and bin i gets + 1 iff i % step == 0 and i / step < res;
  *     lut[i] = sat8(rne((float)cumsum_i (255.0f / (float)area))), quotient and product FP32.  Per pixel (x, y) of the plane, all FP32:
  *     txf = (float)x (1.0f / (float)tw) - 0.5f, tx1 = floor(txf), xa = txf - (float)tx1, xa1 = 1.0f - xa, tx2 = tx1 + 1, then tx1 clamped

@@ -1,8 +1,8 @@
 """Independent NumPy restatement of the image preparation specified in include/srlivo_hip.h ("image preparation of the camera stage"):
 undistortion map, remap, gray, BGR <-> YCrCb and CLAHE.  Written from the specification, not from the kernels: integer arrays throughout,
 np.float64 for the map, np.float32 for CLAHE's two float steps, np.rint (round half to even) for every rounding.  It is the yardstick of
-tests/test_image_prep_abi.py (the map) and tests/test_gpu_image_prep.py (everything else); tests/test_imgprep_checker.py holds known
-answers for the checker itself.  NumPy evaluates every elementwise product and sum as a separate IEEE operation, so nothing here is
+tests/test_image_prep_abi.py (the map), tests/test_gpu_image_prep.py and tests/test_gpu_image_prep_envelope.py (everything else, the
+latter on the case grid of tests/imgprep_cases.py); tests/test_imgprep_checker.py holds known answers for the checker itself.  NumPy evaluates every elementwise product and sum as a separate IEEE operation, so nothing here is
 contracted."""
 import numpy as np
 
@@ -96,7 +96,7 @@ def tiling(rows, cols, tiles=0):
 
 
 def clip_limit(clip, area):
-    return max(int(np.float64(clip) * np.float64(area) / 256), 1)
+    return max(int(min(np.float64(clip) * np.float64(area) / 256, 2147483647.0)), 1)      # the min first: the cast stays inside int32
 
 
 def tile_lut(hist, limit, area):

@@ -1,5 +1,5 @@
 """The shapes and source images shared by tests/test_resize_checker.py (CPU) and tests/test_gpu_image_resize.py (GPU): the smallest at
-which lanes, tails and borders of the resize can go wrong.  Images are built like `_image` of tests/test_gpu_image_prep.py (gradients,
+which lanes, tails and borders of the resize can go wrong.  Images are built like `image` of tests/imgprep_cases.py (gradients,
 noise, saturated blocks, all 216 pixels of {0, 1, 127, 128, 254, 255}^3 where they fit), handed over with a row stride of 3 cols + 13
 bytes and a padding of 0xA5, read-only."""
 import functools

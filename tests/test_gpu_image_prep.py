@@ -7,43 +7,20 @@ seeded and structured (gradients, blocks of 0 and 255 that overflow the clip lim
 255}^3, and are handed over with row_stride_bytes > 3 cols and poisoned padding."""
 import ctypes as C
 import functools
-import itertools
 
 import numpy as np
 import pytest
 
 import imgprep_checker as ck
 import sr_livo_amd as srl
+from imgprep_cases import image as _image          # (rows, cols, seed): strided, poisoned padding, read-only
+from imgprep_device import check_all as _check_all, same as _same
 from sr_livo_amd import capi
 
 pytestmark = pytest.mark.gpu
 SRL_OK, SRL_ERR_BAD_ARG, SRL_ERR_UNSUPPORTED, SRL_ERR_NO_MAP, SRL_ERR_NO_SWEEP = 0, -3, -4, -5, -6
 MILD = (0.2, 0.05, 0.002, -0.003, 0.01)          # pincushion: the corners come from outside the image
 DISTORTIONS = {"zero": (0, 0, 0, 0, 0), "barrel": (-0.3, 0, 0, 0, 0), "pincushion with tangential": (0.3, 0.1, 0.01, -0.01, 0.02)}
-
-
-@functools.lru_cache(maxsize=None)
-def _image(rows, cols, seed):
-    """(rows, cols, 3) uint8 view with a stride of 3 cols + 13 bytes into a buffer whose padding is 0xA5; read-only"""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:rows, 0:cols]
-    img = np.stack([(xx * 255 // max(cols - 1, 1)), (yy * 255 // max(rows - 1, 1)), ((xx + yy) * 255 // (rows + cols - 2))], axis=-1).astype(np.int64)
-    img += rng.integers(-12, 13, size=img.shape)
-    for _ in range(max(4, rows * cols // 1500)):          # saturated blocks: their bins overflow the clip limit
-        r, c = rng.integers(0, rows), rng.integers(0, cols)
-        h, w = rng.integers(2, max(3, rows // 4)), rng.integers(2, max(3, cols // 4))
-        img[r:r + h, c:c + w] = rng.choice([0, 255], size=3) if rng.random() < 0.5 else rng.choice([0, 255])
-    img = np.clip(img, 0, 255).astype(np.uint8)
-    combos = np.array(list(itertools.product((0, 1, 127, 128, 254, 255), repeat=3)), np.uint8)
-    at = rng.choice(rows * cols, size=len(combos), replace=False)
-    img.reshape(-1, 3)[at] = combos
-    stride = 3 * cols + 13
-    buf = np.full(rows * stride, 0xA5, np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf, shape=(rows, cols, 3), strides=(stride, 3, 1))
-    view[...] = img
-    view.setflags(write=False)
-    buf.setflags(write=False)
-    return view
 
 
 def _opts(rows, cols, dist=MILD, tiles=0):
@@ -60,26 +37,6 @@ def _want(rows, cols, seed, dist=MILD, tiles=0):
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
     return w
-
-
-def _same(name, got, want):
-    want = np.ascontiguousarray(want)
-    assert got.size == want.size, (name, got.shape, want.shape)
-    bad = np.flatnonzero(got.ravel() != want.ravel())
-    assert bad.size == 0, (name, bad.size, bad[:8], got.ravel()[bad[:8]], want.ravel()[bad[:8]])
-
-
-def _check_all(prep, info, want, installed=0):
-    assert info.as_tuple() == want["info"] + (installed,), (info.as_tuple(), want["info"])
-    T = info.tiles
-    _same("undist", prep.download_stage(capi.SRL_PREP_STAGE_UNDIST, T), want["undist"])
-    _same("gray", prep.download_stage(capi.SRL_PREP_STAGE_GRAY, T), want["gray"])
-    ycrcb = np.concatenate([want["y"].ravel(), np.stack([want["cr"], want["cb"]], axis=-1).ravel()])
-    _same("ycrcb", prep.download_stage(capi.SRL_PREP_STAGE_YCRCB, T), ycrcb)
-    _same("lut_gray", prep.download_stage(capi.SRL_PREP_STAGE_LUT_GRAY, T), want["lut_gray"])
-    _same("lut_y", prep.download_stage(capi.SRL_PREP_STAGE_LUT_Y, T), want["lut_y"])
-    _same("gray_eq", prep.download(capi.SRL_PREP_GRAY_EQ), want["gray_eq"])
-    _same("bgr_eq", prep.download(capi.SRL_PREP_BGR_EQ), want["bgr_eq"])
 
 
 def _run(rows, cols, seed, dist=MILD, tiles=0):

@@ -95,6 +95,16 @@ def test_a_hand_computed_16_by_16_image_with_one_tile_over_the_limit():
     assert out[0, 0] == expect[10] and out[15, 15] == ramp_lut[63] and out[0, 15] == ramp_lut[7]
 
 
+def test_the_limit_saturates_at_int32_max_before_the_cast():
+    assert ck.clip_limit(1e12, 300) == 2147483647                  # 1 171 875 000 000 without the min
+    assert ck.clip_limit(1e300, 16) == 2147483647
+    assert ck.clip_limit(2147483647.0, 256) == 2147483647 and ck.clip_limit(2147483646.5, 256) == 2147483646      # the last values below it
+    assert ck.clip_limit(3.0, 140) == 1 and ck.clip_limit(1e-300, 256) == 1 and ck.clip_limit(40.0, 64) == 10     # truncated, raised to 1
+    # a tile under a saturated limit is never cut
+    lut, excess, batch, res, step = ck.tile_lut(np.bincount([7] * 300, minlength=256), ck.clip_limit(1e12, 300), 300)
+    assert (excess, batch, res, step) == (0, 0, 0, 0) and lut[6] == 0 and lut[7] == 255
+
+
 def test_the_extension_rule():
     assert ck.tiling(96, 160) == (8, 20, 12, 96, 160)              # both divide: no extension
     assert ck.tiling(96, 170) == (8, 22, 13, 104, 176)             # cols do not: rows grow by a whole T
